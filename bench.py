@@ -16,6 +16,12 @@ buffer fill levels evenly and then runs one full buffer cycle of ordinary window
 One process per GPU (torchrun env RANK/LOCAL_RANK/WORLD_SIZE); without a launcher `--gpus N` starts its own N ranks (self_launch).  After
 an N > 1 run every rank's reduced registers are checksummed and compared, and a small side configuration run through the same exchange is
 compared with a single-rank engine (`exchange_check` in the JSON line; a mismatch exits with status 5).  Rank 0 prints ONE JSON line.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline figure needs: set-up, warm-up, the N timed steps,
+the outputs of the last step when --dump-outputs DIR is given, and the JSON line (`value`, `ms_per_step`, the whole-step roofline).
+Everything else -- per-kernel HIP-event times and counter traffic, the t-digest rank-error check behind `parity_ok`, the quantile
+scan, the host-fed legs, the CPU baselines, the sub-runs of the other BASELINE configurations, the cross-rank checks of an N > 1 run
+and the detail file -- runs with --full only.
 """
 import argparse
 import json
@@ -47,6 +53,9 @@ def _mem_available_bytes():
 
 
 LINE_LIMIT = 4096  # the driver keeps an 8-KB tail of stdout: the LAST line must fit whole, with room to spare
+DETAIL_DEFAULT = os.path.join("bench_out", "bench_detail.json")  # where a --full run writes its full result unless --detail-out says otherwise
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all arrays together
+DUMP_BLOCK, DUMP_BLOCKS = 64, 64  # --dump-outputs: services sampled as 64 seeded blocks of 64 consecutive slots (all of them when there are fewer)
 
 
 def _r(x, nd=6):
@@ -370,6 +379,56 @@ def host_fed_l2_threads(nthreads=16, secs=2.0):
         return json.loads(r.stdout.strip().splitlines()[-1])
     except Exception as ex:  # optional leg: never take the JSON line down
         return {"error": str(ex)[:300]}
+
+
+def dump_slots(nsvc):
+    """service slots whose per-service state --dump-outputs writes: all of them up to DUMP_BLOCK x DUMP_BLOCKS, else DUMP_BLOCKS blocks of
+    DUMP_BLOCK consecutive slots at seeded places (the same for every run of the same shape)"""
+    if nsvc <= DUMP_BLOCK * DUMP_BLOCKS:
+        return np.arange(nsvc)
+    pick = np.sort(np.random.default_rng(0x6475).choice(nsvc // DUMP_BLOCK, DUMP_BLOCKS, replace=False))
+    return (pick[:, None] * DUMP_BLOCK + np.arange(DUMP_BLOCK)).ravel()
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy, integers widened to float64 (exact below 2^53), at most DUMP_LIMIT_BYTES in all"""
+    out = {k: np.ascontiguousarray(v, dtype=np.float32 if np.asarray(v).dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes, more than the {DUMP_LIMIT_BYTES} allowed")
+    os.makedirs(path, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    print(f"bench.py: {len(out)} output arrays ({total / 1e6:.1f} MB) written to {path}", file=sys.stderr)
+
+
+def resp_outputs(eng, wire, mine, svcs):
+    """what a caller of the response path receives after the last timed window: the HLL registers, both Count-Min tables, the all-service
+    histogram of the last finished window, and for the slots of dump_slots() the all-time histogram records, the t-digest clusters and
+    its p25 / p50 / p95 / p99"""
+    eng.sync()
+    gh = eng.export_global_hist()
+    a = {"hll": eng.export_hll().astype(np.float32), "cms0": eng.export_cms(0), "cms1": eng.export_cms(1),
+         "global_hist": np.array([(gh.stats[i].count, gh.stats[i].sum) for i in range(15)] + [(gh.total_count, gh.max_val_seen)], dtype=np.int64)}
+    nsvc = eng.num_services()
+    slots = dump_slots(nsvc)
+    hist, sums, cnts, mm = [], [], [], []
+    for first in slots[::DUMP_BLOCK]:  # (consecutive blocks of DUMP_BLOCK slots, the last one shorter when all slots are taken)
+        first, n = int(first), min(DUMP_BLOCK, nsvc - int(first))
+        hist.append(eng.export_hist(1, first, n))
+        s, c, m = eng.export_tdigest(first, n)
+        sums.append(s)
+        cnts.append(c)
+        mm.append(m)
+    qs = []
+    for slot in slots:  # bench.py registers host j's services s = 0 .. svcs - 1 at slots j * svcs + s
+        gid = int(wire.glob_id(np.array([mine[slot // svcs]]), np.array([slot % svcs]))[0])
+        if eng.lookup(gid) != slot:
+            raise RuntimeError(f"--dump-outputs: slot {slot} does not hold service {gid}")
+        qs.append(eng.quantiles(gid, [0.25, 0.5, 0.95, 0.99]))
+    a.update({"sample_slots": slots, "sample_hist_alltime": np.concatenate(hist), "sample_td_sums": np.concatenate(sums),
+              "sample_td_counts": np.concatenate(cnts), "sample_td_minmax": np.concatenate(mm), "sample_quantiles": np.array(qs)})
+    return a
 
 
 def _kernel_sources():
@@ -726,18 +785,35 @@ def run_conn(args, rank, world):
 
     for i in range(args.warmup):
         step(i)
-    eng.profile(True)
-    eng.profile_reset()
+    if args.full:
+        eng.profile(True)
+        eng.profile_reset()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
         step(args.warmup + i)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    prof = eng.profile_get()
-    eng.profile(False)
     step_s = dt / args.steps
     alg = 280 * nrec + 88 * len(ls)
+    if args.dump_outputs:
+        eng.sync()
+        write_outputs(args.dump_outputs, {"hll": eng.export_hll().astype(np.float32), "cms0": eng.export_cms(0), "cms1": eng.export_cms(1),
+                                          "svc_counters": eng.export_svc_counters(), "distinct_flows": np.array([eng.distinct_flows()])})
+    out = {"metric": "TCP_CONN_NOTIFY records/sec ingested into HLL + Count-Min (BASELINE config 2)", "value": nrec / step_s, "unit": "records/s",
+           "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": step_s * 1e3, "higher_is_better": True, "scaling": "weak",
+           "vs_baseline": None, "dtype": "int64", "data": "synthetic", "parity_ok": None, "device_code": _device_code(),
+           "config": {"workload": "C2: %d hosts x %d services, %d TCP_CONN_NOTIFY (280 B) + %d LISTENER_STATE_NOTIFY (88 B) records per window, "
+                                  "device resident, 1 window per step; record order: %s" % (nh, sp, nrec, len(ls),
+                                  "per-partha messages" if args.conn_stream == "messages" else "hosts mixed record by record")},
+           "roofline": {"bound": "hbm", "achieved": alg / step_s / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": alg / step_s / 1e9 / HBM_PEAK_GBS,
+                        "algorithmic_bytes_per_step": alg}}
+    if not args.full:
+        emit(out, args)
+        eng.close()
+        return
+    prof = eng.profile_get()
+    eng.profile(False)
     kms = {k: v[0] / args.steps for k, v in prof.items()}
     name = args.sub or "c2_conn"
     kernels = {}
@@ -769,20 +845,13 @@ def run_conn(args, rank, world):
     parity_ok = bool(checks["svc_nconn_equals_connection_table"] and checks["svc_nclose_equals_connection_table"] and checks["tallies_consistent"])
     conn_ent = kernels.get("conn", {})
     tr = conn_ent.get("traffic")
-    out = {"metric": "TCP_CONN_NOTIFY records/sec ingested into HLL + Count-Min (BASELINE config 2)", "value": nrec / step_s, "unit": "records/s",
-           "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": step_s * 1e3, "higher_is_better": True, "scaling": "weak",
-           "vs_baseline": None, "dtype": "int64", "data": "synthetic", "parity_ok": parity_ok, "checks": checks,
-           "device_code": _device_code(),
-           "config": {"workload": "C2: %d hosts x %d services, %d TCP_CONN_NOTIFY (280 B) + %d LISTENER_STATE_NOTIFY (88 B) records per window, "
-                                  "device resident, 1 window per step; record order: %s" % (nh, sp, nrec, len(ls),
-                                  "per-partha messages" if args.conn_stream == "messages" else "hosts mixed record by record")},
-           "roofline": {"bound": "hbm", "achieved": alg / step_s / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": alg / step_s / 1e9 / HBM_PEAK_GBS,
-                        "algorithmic_bytes_per_step": alg, "kernel": "conn", "kernel_avg_ms": kms.get("conn"), "kernel_frac": conn_ent.get("frac"),
-                        "kernel_frac_measured_bytes": (tr["bytes"] / (kms["conn"] * 1e-3) / 1e9 / HBM_PEAK_GBS) if tr and kms.get("conn") else None,
-                        "traffic": tr, "kernels": kernels,
-                        "note": "frac = (280 B x records + 88 B x listener records) / WHOLE step (SURVEY 8d: whole struct lines are fetched); kernel_frac = 280 B x "
-                                "records / k_conn_ingest's HIP-event time; kernel_frac_measured_bytes = the same kernel's counter traffic (FETCH_SIZE x 2 + "
-                                "WRITE_SIZE per step) / its time: k_conn_ingest asks for bytes [64, 224) and [264, 280) of each record only"}}
+    out["parity_ok"], out["checks"] = parity_ok, checks
+    out["roofline"].update({"kernel": "conn", "kernel_avg_ms": kms.get("conn"), "kernel_frac": conn_ent.get("frac"),
+                            "kernel_frac_measured_bytes": (tr["bytes"] / (kms["conn"] * 1e-3) / 1e9 / HBM_PEAK_GBS) if tr and kms.get("conn") else None,
+                            "traffic": tr, "kernels": kernels,
+                            "note": "frac = (280 B x records + 88 B x listener records) / WHOLE step (SURVEY 8d: whole struct lines are fetched); kernel_frac = 280 B x "
+                                    "records / k_conn_ingest's HIP-event time; kernel_frac_measured_bytes = the same kernel's counter traffic (FETCH_SIZE x 2 + "
+                                    "WRITE_SIZE per step) / its time: k_conn_ingest asks for bytes [64, 224) and [264, 280) of each record only"})
     if not args.no_cpu_baseline or args.sub:  # (a sub-run keeps this bounded CPU leg: ~2 s)
         try:
             est = None
@@ -830,12 +899,19 @@ def main():
                     "library's RCCL entry points are served by tests/cpp/fakerccl (RCCL refuses two ranks on one device); exercises the whole N > 1 flow")
     ap.add_argument("--selftest-launch", action="store_true", help="no GPU: only the launch path and the cross-rank checksum exchange (gloo)")
     ap.add_argument("--selftest-corrupt-rank", type=int, default=-1, help="--selftest-launch: this rank reports a wrong checksum (the run must fail)")
-    ap.add_argument("--sub", default="", help="this run is the sub-run <name> of a default line (run_sub_configs): no CPU baseline, no host-fed leg, no quantile scan")
+    ap.add_argument("--full", action="store_true", help="besides the headline figure, everything else the benchmark measures and checks: per-kernel times "
+                    "and counter traffic, the t-digest rank-error check (parity_ok), the quantile scan, host-fed legs, CPU baselines, the sub-runs "
+                    "of the other configurations (--configs), the cross-rank checks of an N > 1 run and the detail file (--detail-out)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last step computed as DIR/<name>.npy "
+                    "(float32 / float64, <= 64 MB; per-service state for a seeded sample of the services)")
+    ap.add_argument("--sub", default="", help="this run is the sub-run <name> of a --full line (run_sub_configs): measured as --full, but no CPU baseline, "
+                    "no host-fed leg, no quantile scan")
     ap.add_argument("--configs", default="auto", help="sub-runs of the other BASELINE configurations appended to the default line under `configs`: "
                     "'auto' = all of them when this is the default single-GPU workload, 'none', or a comma-separated list of c2_conn,c1,c5_zipf")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--detail-out", default=os.path.join("gpurun_out", "bench_detail.json"), help="the full result (per-kernel tables, counter traffic, host-fed legs, "
-                    "scans, sub-run lines, notes) as one strict-JSON file; 'none' = not written.  stdout's LAST line is the compact line (<= 4 KB)")
+    ap.add_argument("--detail-out", default=None, help="the full result (per-kernel tables, counter traffic, host-fed legs, scans, sub-run lines, notes) "
+                    "as one strict-JSON file; 'none' = not written; default: " + DETAIL_DEFAULT + " with --full, none without.  stdout's LAST line "
+                    "is the compact line (<= 4 KB)")
     ap.add_argument("--detail-stdout", action="store_true", help="also print the full result as an EARLIER stdout line")
     ap.add_argument("--selftest-line", default="", help="no GPU: read a full result from this JSON file and print the compact line made from it (tests/test_bench_line.py)")
     ap.add_argument("--no-quantile-check", action="store_true", help="skip the (untimed) t-digest rank-error check after the run")
@@ -852,11 +928,14 @@ def main():
     args = ap.parse_args()
 
     if args.selftest_line:
-        print(compact_line(_jsonable(json.load(open(args.selftest_line))), "gpurun_out/bench_detail.json"), flush=True)
+        print(compact_line(_jsonable(json.load(open(args.selftest_line))), DETAIL_DEFAULT), flush=True)
         return
     if args.sub:
+        args.full = True
         args.no_cpu_baseline = args.no_host_fed = True
         args.configs = "none"
+    if args.detail_out is None:
+        args.detail_out = DETAIL_DEFAULT if args.full else "none"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:  # no launcher around us: become one (one rank per GPU of this node)
         sys.exit(self_launch(args))
     rank = int(os.environ.get("RANK", "0"))
@@ -1039,9 +1118,10 @@ def main():
 
     for i in range(args.warmup):
         step(i)
-    eng.profile(True)
-    eng.profile_reset()
-    ctr0 = eng.counters()
+    if args.full:  # per-kernel HIP-event times of the timed windows
+        eng.profile(True)
+        eng.profile_reset()
+        ctr0 = eng.counters()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -1056,14 +1136,17 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    prof = eng.profile_get()
-    eng.profile(False)
-    ctr1 = eng.counters()
+    if args.full:
+        prof = eng.profile_get()
+        eng.profile(False)
+        ctr1 = eng.counters()
+    if rank == 0 and args.dump_outputs:  # (before anything below feeds the engine more events)
+        write_outputs(args.dump_outputs, resp_outputs(eng, wire, mine, args.svcs))
 
     # the exchange, checked (untimed): after the last window every rank must hold the same reduced registers, and a small side
     # configuration run through the same exchange must equal a single-rank engine fed all of its hosts
     xcheck = None
-    if world > 1 and not args.no_exchange_check:
+    if world > 1 and args.full and not args.no_exchange_check:
         regs = observe_registers(eng, ["cluster%d" % c for c in range(8)])
         matrix, same = verify_ranks(regs, world, cdev)
         side = exchange_side_check(args, rank, world, local_rank, L, eng, exchange, wire, SketchEngine, mid_buf, cdev)
@@ -1097,13 +1180,13 @@ def main():
         xcheck["ok"] = bool(int(okt.item()))
 
     qerr = None
-    if rank == 0 and not args.no_quantile_check and nsvc:
+    if rank == 0 and args.full and not args.no_quantile_check and nsvc:
         for b in range(nbuf):
             ingested.append([args.events, 0x67796565746121 + 1000 * rank + b, args.zipf_milli, buf_uses[b]])
         qh, qs = ([mine[0]], [0]) if nlocal == 1 else ([mine[0], mine[-1]], [0, nlocal - 1])  # first and last host of the rank (one host: once)
         qerr = quantile_error(eng, torch, ingested, nlocal, args.svcs, qh, qs, wire)
     scan = None
-    if rank == 0 and nsvc and not args.no_quantile_check and not args.sub:  # the per-key scan on the digests (a9): p25 / p95 / p99 of EVERY service, one pass
+    if rank == 0 and nsvc and args.full and not args.no_quantile_check and not args.sub:  # the per-key scan on the digests (a9): p25 / p95 / p99 of EVERY service, one pass
         eng.profile(True)
         eng.profile_reset()
         t0 = time.perf_counter()
@@ -1134,7 +1217,7 @@ def main():
         except Exception as ex:  # noqa: BLE001
             scan["global_rollup_error"] = str(ex)[:200]
     host_fed = None
-    if rank == 0 and world == 1 and not args.no_host_fed and nsvc:
+    if rank == 0 and world == 1 and args.full and not args.no_host_fed and nsvc:
         host_fed = host_fed_rate(eng, torch, min(args.events, 1 << 26), nlocal, args.svcs)
         host_fed["l2_threads"] = "deferred"
     if rank == 0:
@@ -1146,25 +1229,37 @@ def main():
         # (+ the 256-B window / all-time records it folds on the way); the per-service finalize pass reads one 4-B cursor per service.
         step_s = dt / args.steps
         alg_bytes = evb * args.events  # per step: every event of the window's batch is read exactly once
-        kms = {k: v[0] / max(args.steps, 1) for k, v in prof.items()}
-        merges_step = (ctr1["td_merges"] - ctr0["td_merges"]) / max(args.steps, 1)
-        mvals_step = (ctr1["td_merge_values"] - ctr0["td_merge_values"]) / max(args.steps, 1)
-        kalg = {"resp_host": alg_bytes + 4 * args.events,
-                "key_finalize": 4 * nsvc + 16 * nsvc * min(1.0, args.events / max(nsvc, 1)),
-                "digest_merge": merges_step * (2 * 12 * capi.TD_NB + 2 * 512 + 64 + 32) + 4 * mvals_step}
-        kernels = {}
-        for k, ms in kms.items():
-            ent = {"ms": ms, "launches_per_step": prof[k][1] / max(args.steps, 1)}
-            if k in kalg and ms > 0:
-                ent["algorithmic_bytes"] = kalg[k]
-                ent["achieved_GBps"] = kalg[k] / (ms * 1e-3) / 1e9
-                ent["frac"] = ent["achieved_GBps"] / HBM_PEAK_GBS
-            tr = workload_traffic(args.sub, k, args.events) if args.sub else (None if args.ipv6 else pmc_traffic(k, args.events, nsvc))  # (the committed passes are of the IPv4 stream)
-            if tr is not None:
-                ent["traffic"] = tr
-            kernels[k] = ent
-        dom = max(kms.items(), key=lambda kv: kv[1]) if kms else ("none", 0.0)
-        dom_ent = kernels.get(dom[0], {})
+        roofline = {"bound": "hbm", "achieved": alg_bytes / step_s / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": alg_bytes / step_s / 1e9 / HBM_PEAK_GBS,
+                    "algorithmic_bytes_per_step": alg_bytes,
+                    "note": "frac = %d B x events / WHOLE step (all kernels of the window); per-kernel figures under `kernels` (--full)" % evb}
+        if args.full:
+            kms = {k: v[0] / max(args.steps, 1) for k, v in prof.items()}
+            merges_step = (ctr1["td_merges"] - ctr0["td_merges"]) / max(args.steps, 1)
+            mvals_step = (ctr1["td_merge_values"] - ctr0["td_merge_values"]) / max(args.steps, 1)
+            kalg = {"resp_host": alg_bytes + 4 * args.events,
+                    "key_finalize": 4 * nsvc + 16 * nsvc * min(1.0, args.events / max(nsvc, 1)),
+                    "digest_merge": merges_step * (2 * 12 * capi.TD_NB + 2 * 512 + 64 + 32) + 4 * mvals_step}
+            kernels = {}
+            for k, ms in kms.items():
+                ent = {"ms": ms, "launches_per_step": prof[k][1] / max(args.steps, 1)}
+                if k in kalg and ms > 0:
+                    ent["algorithmic_bytes"] = kalg[k]
+                    ent["achieved_GBps"] = kalg[k] / (ms * 1e-3) / 1e9
+                    ent["frac"] = ent["achieved_GBps"] / HBM_PEAK_GBS
+                tr = workload_traffic(args.sub, k, args.events) if args.sub else (None if args.ipv6 else pmc_traffic(k, args.events, nsvc))  # (the committed passes are of the IPv4 stream)
+                if tr is not None:
+                    ent["traffic"] = tr
+                kernels[k] = ent
+            dom = max(kms.items(), key=lambda kv: kv[1]) if kms else ("none", 0.0)
+            dom_ent = kernels.get(dom[0], {})
+            roofline.update({"kernel": dom[0], "kernel_avg_ms": dom[1], "kernel_frac": dom_ent.get("frac"),
+                             # SURVEY 8(d)'s own figure for the dominant kernel: 24 B x events / its average launch time (kernel_frac counts the
+                             # 4-byte staged word the event kernel also writes per event: 28 B)
+                             "kernel_frac_24B": (alg_bytes / (dom[1] * 1e-3) / 1e9 / HBM_PEAK_GBS) if dom[0] == "resp_host" and dom[1] > 0 else None,
+                             "traffic": dom_ent.get("traffic"),
+                             "merges_per_step": merges_step, "merge_values_per_step": mvals_step,
+                             "kernels": kernels})
         tol = 0.01
         parity_ok = None if qerr is None else bool(qerr["p50_rank_err_max"] <= tol and qerr["p99_rank_err_max"] <= tol)
         try:  # BASELINE.json names the metric; `value` is its events/sec half, `quantile_error` its p50/p99 half
@@ -1192,17 +1287,7 @@ def main():
                        "exchange_requested": args.exchange if world > 1 else "none",
                        "exchange_fallback": bool(world > 1 and args.exchange == "rccl" and exchange != "rccl_in_library"),
                        "rccl_lib": os.environ.get("GYS_RCCL_LIB", "/opt/rocm/lib/librccl.so") if world > 1 else None},
-            "roofline": {"bound": "hbm", "achieved": alg_bytes / step_s / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": alg_bytes / step_s / 1e9 / HBM_PEAK_GBS,
-                         "algorithmic_bytes_per_step": alg_bytes,
-                         "note": "frac = %d B x events / WHOLE step (all kernels of the window); per-kernel figures under `kernels`" % evb,
-                         "kernel": dom[0], "kernel_avg_ms": dom[1], "kernel_frac": dom_ent.get("frac"),
-                         # SURVEY 8(d)'s own figure for the dominant kernel: 24 B x events / its average launch time (kernel_frac counts the
-                         # 4-byte staged word the event kernel also writes per event: 28 B)
-                         "kernel_frac_24B": (alg_bytes / (dom[1] * 1e-3) / 1e9 / HBM_PEAK_GBS) if dom[0] == "resp_host" and dom[1] > 0 else None,
-                         "traffic": dom_ent.get("traffic"),
-                         "merges_per_step": merges_step, "merge_values_per_step": mvals_step,
-                         "kernels": kernels},
+            "roofline": roofline,
         }
         if xcheck is not None:
             out["exchange_check"] = xcheck
@@ -1212,7 +1297,7 @@ def main():
             out["host_fed"] = host_fed
         if scan is not None:
             out["quantile_scan"] = scan
-        if not args.no_cpu_baseline and world == 1:  # the CPU legs are timed on rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU legs are timed on rank 0 at N = 1 only
             # the metric's own key count first (10^7 keys when the workload has them and the host has the memory: median of 5), then the
             # 10^6-key sample of the earlier rounds beside it
             legs = []
@@ -1260,7 +1345,7 @@ def main():
         # the other BASELINE configurations (C2 connection records, C1 and C5 shapes) as short sub-runs, each in its own process: appended to
         # the default single-GPU line only (a sub-run never changes `value`; its failure is reported inside `configs`)
         default_shape = (world == 1 and args.hosts == 10000 and args.svcs == 1000 and args.events == (1 << 29) and not args.zipf_milli and not args.levels and not args.ipv6)
-        if args.configs != "none" and (default_shape or args.configs != "auto"):
+        if args.full and args.configs != "none" and (default_shape or args.configs != "auto"):
             bufs.clear()  # (this run's resident event batches: the sub-runs bring their own)
             torch.cuda.empty_cache()
             out["configs"] = run_sub_configs([] if args.configs in ("auto", "all") else args.configs.split(","))

@@ -22,12 +22,18 @@ COMMIT_PATH = os.path.join(LIB_DIR, "build_commit.txt")
 
 def stamp_commit():
     """which source tree the library was built from (the GPU box gets the built .so but not .git): `git rev-parse HEAD` + "+dirty" when
-    tracked files differ from it; read back by bench.py (build_commit) and tools/pmc_traffic.py (source_commit of the counter passes)"""
+    tracked files differ from it; read back by bench.py (build_commit) and tools/pmc_traffic.py (source_commit of the counter passes).
+    A tree without usable git metadata (an exported source tree, a checkout owned by another user) is stamped "unknown": the source and
+    device-code hashes do not need git and are written all the same."""
+    root = os.path.dirname(HERE)
     try:
-        root = os.path.dirname(HERE)
         head = subprocess.check_output(["git", "-C", root, "rev-parse", "--short=12", "HEAD"], stderr=subprocess.DEVNULL).decode().strip()
         dirty = subprocess.call(["git", "-C", root, "diff", "--quiet", "HEAD", "--", "gyeeta_amd", "include", "bench.py"], stderr=subprocess.DEVNULL) != 0
-        open(COMMIT_PATH, "w").write(head + ("+dirty" if dirty else "") + " " + _hash_sources() + " " + (_hash_device_code(LIB_PATH) or "-") + "\n")
+        head += "+dirty" if dirty else ""
+    except Exception:
+        head = "unknown"
+    try:
+        open(COMMIT_PATH, "w").write(head + " " + _hash_sources() + " " + (_hash_device_code(LIB_PATH) or "-") + "\n")
     except Exception:
         pass
 

@@ -45,12 +45,12 @@ import pytest  # noqa: E402
 
 @pytest.mark.gpu
 def test_bench_two_ranks_on_one_device_whole_flow():
-    """`python bench.py --gpus 2 --share-device`: the whole N > 1 flow of the bench on a one-GPU box -- self-launch, host-hash sharding,
+    """`python bench.py --gpus 2 --share-device --full`: the whole N > 1 flow of the bench on a one-GPU box -- self-launch, host-hash sharding,
     communicator join through the C ABI, gys_window_close_rccl in every window (RCCL entry points served by tests/cpp/fakerccl, both ranks
     on device 0), the cross-rank register check and the side configuration compared with a single-rank engine"""
     import tempfile
     detail = os.path.join(tempfile.mkdtemp(prefix="gys_bench_detail_"), "detail.json")
-    r = _run("--gpus", "2", "--share-device", "--hosts", "400", "--svcs", "100", "--events", str(1 << 22), "--steps", "4", "--warmup", "1",
+    r = _run("--gpus", "2", "--share-device", "--full", "--hosts", "400", "--svcs", "100", "--events", str(1 << 22), "--steps", "4", "--warmup", "1",
              "--prime-windows", "2", "--no-cpu-baseline", "--no-host-fed", "--strict-exchange", "--detail-out", detail, timeout=900)
     assert r.returncode == 0, (r.returncode, r.stdout[-1500:], r.stderr[-3000:])
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]

@@ -17,7 +17,7 @@ bench)
 	out=$2; shift 2; mkdir -p $out; cd $R
 	for lib in gyeeta_amd/lib/libgysketch.so $(ls gyeeta_amd/lib/libgysketch_*.so 2>/dev/null); do
 		tag=$(basename $lib .so)
-		GYS_LIB=$R/$lib timeout 120 python bench.py --no-cpu-baseline --no-host-fed --no-quantile-check --detail-out $out/$tag.json "$@" > $out/$tag.line 2> $out/$tag.err
+		GYS_LIB=$R/$lib timeout 120 python bench.py --full --no-cpu-baseline --no-host-fed --no-quantile-check --detail-out $out/$tag.json "$@" > $out/$tag.line 2> $out/$tag.err
 		python - $out/$tag.json $tag <<'PY'
 import json, sys
 try:

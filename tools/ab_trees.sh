@@ -12,7 +12,7 @@ for t in "$@"; do
 	cd $GRAFT_REPO_ROOT
 	echo "=== tree $name"
 	(timeout 500 python -m pytest tests -m gpu -x -q 2>&1 | tail -6) | tee $OUT/$name.pytest.log
-	timeout 200 python bench.py --no-cpu-baseline --no-host-fed --steps 10 --warmup 2 > $OUT/$name.bench.json 2> $OUT/$name.bench.err
+	timeout 200 python bench.py --full --no-cpu-baseline --no-host-fed --steps 10 --warmup 2 > $OUT/$name.bench.json 2> $OUT/$name.bench.err
 	python - $OUT/$name.bench.json <<'PY'
 import json, sys
 try:
