@@ -4004,9 +4004,11 @@ static int rollup_run(gys_ctx *c, int kind, const RollupChunk *d_chunks, uint32_
 	rp.ngroups = ngroups;
 	{
 		ProfScope ps(c, kind == 0 ? "rollup_services" : "rollup_slabs");
-		const size_t words = (size_t)ngroups * GYS_RB_STRIDE;
+		const size_t words = (size_t)ngroups * (GYS_RB_HDR + 1u);
 		hipLaunchKernelGGL(k_rollup_init, dim3((uint32_t)std::min<size_t>((words + 255) / 256, (size_t)c->ncu * 16)), dim3(256), 0, c->stream, c->rb_bins, ngroups);
 		if (nchunks) hipLaunchKernelGGL(k_rollup_accum, dim3(std::min<uint32_t>(nchunks, (uint32_t)c->ncu * 16)), dim3(GYS_RB_NT), 0, c->stream, rp);
+		hipLaunchKernelGGL(k_rollup_mark, dim3(std::min<uint32_t>(ngroups, (uint32_t)c->ncu * 8)), dim3(256), 0, c->stream, rp);
+		if (nchunks) hipLaunchKernelGGL(k_rollup_refine, dim3(std::min<uint32_t>(nchunks, (uint32_t)c->ncu * 16)), dim3(GYS_RB_NT), 0, c->stream, rp);
 		hipLaunchKernelGGL(k_rollup_cluster, dim3(std::min<uint32_t>(ngroups, (uint32_t)c->ncu * 8)), dim3(256), 0, c->stream, rp);
 	}
 	HIPCHK(hipGetLastError());

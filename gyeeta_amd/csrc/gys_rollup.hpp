@@ -10,15 +10,29 @@
 //   order, are laid on the rank axis: bin b (weight w, W = weight of the bins below) occupies the unit mid-points 2 (W + r) + 1,
 //   r < w; point r belongs to the cluster every merge of the engine would give that mid-point; the points r0 <= r < r1 of a bin that
 //   fall into one cluster bring it floor(sum r1 / w) - floor(sum r0 / w) of the bin's sum (128-bit product).
-// Two kernels: k_rollup_accum (HBM-bound: 12 bytes per cluster, 4 bytes per buffered value, one LDS atomic or two per item; a
-// workgroup's LDS bins go to the group's bins in HBM with one 64-bit atomic pair per non-empty bin) and k_rollup_cluster (one
-// workgroup per group, 32 KB in, one slab out).  A roll-up of roll-ups (hosts -> cluster / global, ranks -> all) is the same pair
-// over the members' clusters.
+//   REFINEMENT: a bin of 1024 and above that a cluster boundary cuts (its first and last points in different clusters) and that holds more
+//   than 1 / 1024 of the weight is MARKED (at most 199; narrow groups: one or two).  A second pass over the members adds every item whose bin
+//   is marked to its fine cell: 1920 cells per group, per = 1920 / (marked bins) of them to each marked bin, which uses min(per, width) cells
+//   of equal width (down to one millisecond).  The finish lays out the cells of a marked bin in its place, by the same rule.  Without it
+//   a heavy bin 16 ms wide at 1.5 s (8 s at 600 s) was cut into clusters of one and the same mean: p25 / p75 of a group at a fixed 1.5 s
+//   were off by a quarter of the ranks.
+// Five kernels: k_rollup_init; k_rollup_accum (HBM-bound: 12 bytes per cluster, 4 bytes per buffered value, one LDS atomic or two per item;
+// a workgroup's LDS bins go to the group's bins in HBM with one 64-bit atomic pair per non-empty bin); k_rollup_mark (one workgroup per
+// group); k_rollup_refine (the members again, for the groups with marked bins only); k_rollup_cluster (one workgroup per group, one slab
+// out).  A roll-up of roll-ups (hosts -> cluster / global, ranks -> all) is the same over the members' clusters.
 #pragma once
 
 namespace gys {
 
-#define GYS_RB_STRIDE (2u * GYS_MB_BINS + 2u) // 64-bit words of a group's bins in HBM: cnt[2048], sum[2048], vmin, vmax
+// 64-bit words of a group's scratch in HBM (8195 words, 64 KB): cnt[2048], sum[2048], vmin, vmax; the refinement's header (marked bins |
+// cells per marked bin << 32), the mark of every bin (one byte: 0 or 1 + its index among the marked), fine cnt[1920], fine sum[1920]
+#define GYS_RB_FINE 1920u
+#define GYS_RB_HEAVY 1024u // a bin is marked only when it holds more than 1 / GYS_RB_HEAVY of the group's weight
+#define GYS_RB_HDR (2u * GYS_MB_BINS + 2u)
+#define GYS_RB_MARK (GYS_RB_HDR + 1u)
+#define GYS_RB_FCNT (GYS_RB_MARK + GYS_MB_BINS / 8u)
+#define GYS_RB_FSUM (GYS_RB_FCNT + GYS_RB_FINE)
+#define GYS_RB_STRIDE (GYS_RB_FSUM + GYS_RB_FINE)
 #ifndef GYS_RB_NT
 #define GYS_RB_NT 1024u                       // threads of an accumulating workgroup: 16 waves, each walks members of its own (two workgroups per CU share its LDS)
 #endif
@@ -48,12 +62,14 @@ struct RollupP {
 	uint32_t ngroups;
 };
 
+// the bins, extremes and refinement header (no marked bin) of every group; the marks and the fine cells are written by k_rollup_mark
 __global__ __launch_bounds__(256) void k_rollup_init(unsigned long long *bins, uint32_t ngroups)
 {
-	const size_t n = (size_t)ngroups * GYS_RB_STRIDE;
+	const size_t n = (size_t)ngroups * (GYS_RB_HDR + 1u);
 	for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (size_t)gridDim.x * 256u) {
-		const uint32_t k = (uint32_t)(i % GYS_RB_STRIDE);
-		bins[i] = k == 2u * GYS_MB_BINS ? (unsigned long long)(long long)INT32_MAX : k == 2u * GYS_MB_BINS + 1u ? (unsigned long long)(long long)INT32_MIN : 0ull;
+		const uint32_t k = (uint32_t)(i % (GYS_RB_HDR + 1u));
+		bins[i / (GYS_RB_HDR + 1u) * GYS_RB_STRIDE + k] =
+			k == 2u * GYS_MB_BINS ? (unsigned long long)(long long)INT32_MAX : k == 2u * GYS_MB_BINS + 1u ? (unsigned long long)(long long)INT32_MIN : 0ull;
 	}
 }
 
@@ -274,10 +290,149 @@ __device__ __forceinline__ uint32_t cluster_of_u64(const uint64_t *T, uint64_t m
 	return a;
 }
 
+// the fine cells of marked bin b (>= GYS_MB_EXACT, width 2^sh): min(per, 2^sh) cells of equal width; value v of the bin is in cell (v - lo) c / 2^sh
+__device__ __forceinline__ uint32_t rb_ncell(uint32_t b, uint32_t per) { return min(per, 1u << (4u + (b - GYS_MB_EXACT) / 64u)); }
+__device__ __forceinline__ uint32_t rb_cell(uint32_t v, uint32_t b, uint32_t per)
+{
+	const uint32_t sh = 4u + (b - GYS_MB_EXACT) / 64u, lo = (64u + ((b - GYS_MB_EXACT) & 63u)) << sh;
+	return ((v - lo) * rb_ncell(b, per)) >> sh;
+}
+
+// between the two passes, one workgroup per group: the marked bins -- 1024 and above, their first and last unit points in different clusters,
+// more than 1 / GYS_RB_HEAVY of the weight (every cluster boundary cuts one bin at most: <= 199) --, their indices in bin order, the header;
+// the fine cells they use are zeroed.  The same rank axis as k_rollup_cluster.
+__global__ __launch_bounds__(256) void k_rollup_mark(RollupP q)
+{
+	__shared__ uint64_t s_T[GYS_NBP];
+	__shared__ uint64_t s_ww[4];
+	__shared__ uint32_t s_wm[4];
+	const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+
+	for (uint32_t g = blockIdx.x; g < q.ngroups; g += gridDim.x) {
+		unsigned long long *gb = q.bins + (size_t)g * GYS_RB_STRIDE;
+		uint64_t cn[GYS_MB_BPT], own = 0; // thread t: bins [8 t, 8 t + 8)
+#pragma unroll
+		for (uint32_t k = 0; k < GYS_MB_BPT; ++k) {
+			cn[k] = gb[GYS_MB_BPT * tid + k];
+			own += cn[k];
+		}
+		const uint64_t inc = wave_incl_scan_u64(own);
+		if (lane == 63u) s_ww[wave] = inc;
+		__syncthreads();
+		uint64_t W = inc - own, N = 0;
+#pragma unroll
+		for (uint32_t k = 0; k < 4u; ++k) {
+			if (k < wave) W += s_ww[k];
+			N += s_ww[k];
+		}
+		s_T[tid] = (tid >= 1u && tid < GYS_TD_NB) ? td_threshold(c_td_bnd[tid], 2ull * N) : (tid ? ~0ull : 0ull);
+		__syncthreads();
+		uint32_t mk = 0;
+#pragma unroll
+		for (uint32_t k = 0; k < GYS_MB_BPT; ++k) {
+			const uint64_t w = cn[k];
+			if (GYS_MB_BPT * tid + k >= GYS_MB_EXACT && w > N / GYS_RB_HEAVY &&
+			    cluster_of_u64(s_T, 2ull * W + 1ull) != cluster_of_u64(s_T, 2ull * (W + w - 1ull) + 1ull))
+				mk |= 1u << k;
+			W += w;
+		}
+		const uint32_t nm = (uint32_t)__popc(mk), minc = wave_incl_scan_u32(nm);
+		if (lane == 63u) s_wm[wave] = minc;
+		__syncthreads();
+		uint32_t idx = minc - nm, total = 0;
+#pragma unroll
+		for (uint32_t k = 0; k < 4u; ++k) {
+			if (k < wave) idx += s_wm[k];
+			total += s_wm[k];
+		}
+		unsigned long long word = 0;
+#pragma unroll
+		for (uint32_t k = 0; k < GYS_MB_BPT; ++k)
+			if (mk & (1u << k)) word |= (unsigned long long)(++idx) << (8u * k);
+		gb[GYS_RB_MARK + tid] = word;
+		const uint32_t per = total ? GYS_RB_FINE / total : 0u;
+		if (tid == 0) gb[GYS_RB_HDR] = (unsigned long long)total | ((unsigned long long)per << 32);
+		for (uint32_t k = tid; k < total * per; k += 256u) {
+			gb[GYS_RB_FCNT + k] = 0ull;
+			gb[GYS_RB_FSUM + k] = 0ull;
+		}
+		__syncthreads();
+	}
+}
+
+// the second pass over the members (the same chunks as k_rollup_accum): every cluster and buffered value whose bin is marked goes to its fine
+// cell -- in LDS, then one pair of 64-bit adds per non-empty cell into the group's.  A group without marked bins is skipped.
+__global__ __launch_bounds__(GYS_RB_NT) void k_rollup_refine(RollupP q)
+{
+	const DigestP &p = q.d;
+	__shared__ unsigned long long f_cnt[GYS_RB_FINE], f_sum[GYS_RB_FINE];
+	__shared__ unsigned long long s_mark[GYS_MB_BINS / 8u];
+	const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+	constexpr uint32_t NW = GYS_RB_NT / 64u;
+
+	for (uint32_t c = blockIdx.x; c < q.nchunks; c += gridDim.x) {
+		const RollupChunk ck = q.chunks[c];
+		unsigned long long *gb = q.bins + (size_t)ck.group * GYS_RB_STRIDE;
+		const unsigned long long hdr = gb[GYS_RB_HDR];
+		const uint32_t per = (uint32_t)(hdr >> 32), ncell = (uint32_t)hdr * per;
+		if (!ncell) continue; // (the same for the whole workgroup)
+		for (uint32_t k = tid; k < GYS_MB_BINS / 8u; k += GYS_RB_NT) s_mark[k] = gb[GYS_RB_MARK + k];
+		for (uint32_t k = tid; k < ncell; k += GYS_RB_NT) {
+			f_cnt[k] = 0;
+			f_sum[k] = 0;
+		}
+		__syncthreads();
+		const uint8_t *mark = (const uint8_t *)s_mark;
+		auto put = [&](uint32_t v, uint64_t cn, uint64_t sm) {
+			v = min(v, (1u << 26) - 1u);
+			const uint32_t b = mb_bin(v), m = mark[b];
+			if (m) {
+				const uint32_t cell = (m - 1u) * per + rb_cell(v, b, per);
+				atomicAdd(&f_cnt[cell], (unsigned long long)cn);
+				atomicAdd(&f_sum[cell], (unsigned long long)sm);
+			}
+		};
+		for (uint32_t mi = ck.m0 + wave; mi < ck.m1; mi += NW) {
+			const uint32_t mem = q.members[mi];
+#pragma unroll
+			for (uint32_t k = 0; k < (GYS_TD_NB + 63u) / 64u; ++k) {
+				const uint32_t j = lane + 64u * k;
+				uint64_t cn = 0, sm = 0;
+				if (j < GYS_TD_NB) {
+					if (q.kind == 0) {
+						cn = p.td_cnt[(size_t)mem * GYS_TD_NB + j];
+						sm = (uint64_t)p.td_sum[(size_t)mem * GYS_TD_NB + j];
+					} else {
+						cn = q.in[mem].cnt[j];
+						sm = (uint64_t)q.in[mem].sum[j];
+					}
+				}
+				if (cn) put(ceil_div_wide(sm, cn), cn, sm);
+			}
+			if (q.kind != 0) continue;
+			const uint32_t npend = min(p.td_meta[mem].npend, p.pend_cap);
+			const uint32_t *pend = p.td_pend + (size_t)mem * p.pcap;
+			for (uint32_t i = lane; i < npend; i += 64u) {
+				const uint32_t word = pend[i];
+				if (word >= (GYS_MB_EXACT << GYS_ROW_BITS)) put(word >> GYS_ROW_BITS, 1ull, word >> GYS_ROW_BITS); // (below 1024: never marked)
+			}
+		}
+		__syncthreads();
+		for (uint32_t k = tid; k < ncell; k += GYS_RB_NT) {
+			if (f_cnt[k]) {
+				atomicAdd(&gb[GYS_RB_FCNT + k], f_cnt[k]);
+				atomicAdd(&gb[GYS_RB_FSUM + k], f_sum[k]);
+			}
+		}
+		__syncthreads();
+	}
+}
+
 __global__ __launch_bounds__(256) void k_rollup_cluster(RollupP q)
 {
 	__shared__ uint64_t s_T[GYS_NBP];
 	__shared__ unsigned long long o_sum[GYS_NBP], o_cnt[GYS_NBP];
+	__shared__ unsigned long long f_cnt[GYS_RB_FINE], f_sum[GYS_RB_FINE]; // the group's fine cells
 	__shared__ uint64_t s_ww[4];
 	const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
 
@@ -289,6 +444,13 @@ __global__ __launch_bounds__(256) void k_rollup_cluster(RollupP q)
 			cn[k] = gb[GYS_MB_BPT * tid + k];
 			sm[k] = gb[GYS_MB_BINS + GYS_MB_BPT * tid + k];
 			own += cn[k];
+		}
+		const unsigned long long hdr = gb[GYS_RB_HDR];
+		const uint32_t per = (uint32_t)(hdr >> 32), ncell = (uint32_t)hdr * per;
+		const unsigned long long mword = ncell ? gb[GYS_RB_MARK + tid] : 0ull; // (no marked bin: the map is not read)
+		for (uint32_t k = tid; k < ncell; k += 256u) {
+			f_cnt[k] = gb[GYS_RB_FCNT + k];
+			f_sum[k] = gb[GYS_RB_FSUM + k];
 		}
 		const uint64_t inc = wave_incl_scan_u64(own);
 		if (lane == 63u) s_ww[wave] = inc;
@@ -303,30 +465,40 @@ __global__ __launch_bounds__(256) void k_rollup_cluster(RollupP q)
 		}
 		s_T[tid] = (tid >= 1u && tid < GYS_TD_NB) ? td_threshold(c_td_bnd[tid], 2ull * N) : (tid ? ~0ull : 0ull);
 		__syncthreads();
+		// a unit -- a bin, or a cell of a marked bin -- of weight w and sum s after W: its points into their clusters
+		auto unit = [&](uint64_t w, uint64_t s) {
+			if (!w) return;
+			uint32_t a = cluster_of_u64(s_T, 2ull * W + 1ull);
+			uint64_t r = 0, given = 0;
+			while (r < w) { // (nearly always one round: a cluster spans far more ranks than a bin holds)
+				const uint64_t Tn = s_T[a + 1u]; // first mid-point of the next cluster (~0 after the last)
+				uint64_t r1 = w;
+				if (Tn != ~0ull) {
+					const uint64_t x = Tn > 2ull * W ? (Tn - 2ull * W) >> 1 : 0ull; // points with 2 (W + r) + 1 < Tn
+					r1 = x < w ? x : w;
+				}
+				if (r1 > r) {
+					const uint64_t upto = r1 == w ? s : mul_div_floor(s, r1, w);
+					atomicAdd(&o_sum[a], (unsigned long long)(upto - given));
+					atomicAdd(&o_cnt[a], (unsigned long long)(r1 - r));
+					given = upto;
+					r = r1;
+				}
+				++a;
+			}
+			W += w;
+		};
 		if (N) {
 #pragma unroll 1
 			for (uint32_t k = 0; k < GYS_MB_BPT; ++k) {
-				const uint64_t w = cn[k], s = sm[k];
-				if (!w) continue;
-				uint32_t a = cluster_of_u64(s_T, 2ull * W + 1ull);
-				uint64_t r = 0, given = 0;
-				while (r < w) { // (nearly always one round: a cluster spans far more ranks than a bin holds)
-					const uint64_t Tn = s_T[a + 1u]; // first mid-point of the next cluster (~0 after the last)
-					uint64_t r1 = w;
-					if (Tn != ~0ull) {
-						const uint64_t x = Tn > 2ull * W ? (Tn - 2ull * W) >> 1 : 0ull; // points with 2 (W + r) + 1 < Tn
-						r1 = x < w ? x : w;
-					}
-					if (r1 > r) {
-						const uint64_t upto = r1 == w ? s : mul_div_floor(s, r1, w);
-						atomicAdd(&o_sum[a], (unsigned long long)(upto - given));
-						atomicAdd(&o_cnt[a], (unsigned long long)(r1 - r));
-						given = upto;
-						r = r1;
-					}
-					++a;
+				const uint32_t m = (uint32_t)(mword >> (8u * k)) & 255u;
+				if (!m) {
+					unit(cn[k], sm[k]);
+					continue;
 				}
-				W += w;
+				const uint32_t c0 = (m - 1u) * per, c1 = c0 + rb_ncell(GYS_MB_BPT * tid + k, per);
+#pragma unroll 1
+				for (uint32_t c = c0; c < c1; ++c) unit(f_cnt[c], f_sum[c]);
 			}
 		}
 		__syncthreads();

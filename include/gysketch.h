@@ -367,7 +367,9 @@ int gys_scan_quantiles_dev(gys_ctx *ctx, const double *q, uint32_t nq, double *d
  * no longer an ordered fold): the UNION BY VALUE BIN -- every member's non-empty clusters go, whole, into the value bin (one per millisecond
  * below 1024, 64 cells per octave above) of the integer threshold of their mean, a service's buffered values into the bin of the value; the
  * bins' exact 64-bit {sum, count} are then laid on the rank axis in order and cut into the 200 clusters by the engine's cluster rule, a bin
- * that spans a cluster boundary sharing its sum in proportion (exact integers).  The result does not depend on the order of the members.  A
+ * that spans a cluster boundary sharing its sum in proportion (exact integers).  A bin of 1024 ms and above that a boundary cuts and that
+ * holds more than 1 / 1024 of the weight is refined first: a second pass over the members puts its share into up to 1920 / (refined bins)
+ * cells of equal width (down to 1 ms), which take the bin's place in the layout.  The result does not depend on the order of the members.  A
  * roll-up digest as a member contributes its clusters the same way.  Fixed-size slab = the unit a multi-rank job all-gathers (ncclAllGather
  * of sizeof(gys_tdigest_slab) bytes per rank) and rolls up with gys_tdigest_merge_slabs_dev. */
 typedef struct {

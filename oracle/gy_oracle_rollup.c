@@ -30,6 +30,14 @@
  *            (Integer shares: the pieces of one bin have means that differ by less than one unit per point of the piece and are not
  *            ordered among themselves; all lie inside the bin.)  A bin's mass is thereby spread evenly over its ranks: a heavy value (30 % of all responses take 5 ms) is split over the
  *            clusters its ranks span instead of making one oversized cluster.
+ *     refine a bin k >= 1024 whose first and last unit points fall into different clusters and whose weight exceeds N / 1024 (integer
+ *            division) is MARKED, numbered 1, 2, ... in bin order (every cluster boundary cuts one bin at most: <= 199).  per = 1920 / marked.
+ *            A second pass over the members puts every item (a cluster at ceil(sum / cnt), a buffered value at its value) whose bin is
+ *            marked into a fine cell: marked bin k of width 2^sh and lower edge lo has c = min(per, 2^sh) cells, the item at v goes to cell
+ *            ((v - lo) c) >> sh of them.  In the finish, a marked bin is replaced by its cells, in order, each laid out as a bin.  (Round 6
+ *            had no refinement: a heavy bin 16 ms wide at 1.5 s was cut into clusters of one mean, the quantiles of a group at a fixed
+ *            1.5 s collapsed onto it -- rank errors up to 0.49.)  Here the second pass replays the items of 1024 and above that
+ *            gyo_tdbins_add_* recorded (gy_oracle.h); the kernels read the members again (k_rollup_refine).
  *     vmin / vmax: over the members that contribute clusters (their own extremes) and over the buffered values.
  *   A roll-up of roll-ups (cluster = its hosts' slabs, global = all host slabs of the rank, all ranks = the ranks' global slabs) is the same
  *   operation on the members' clusters.  Values are at most one bin away from where they were (below 1024 ms: exact to the millisecond
@@ -195,31 +203,95 @@ uint32_t gyo_td_value_bin(uint32_t v)
 	return 1024u + (msb - 10u) * 64u + ((v >> (msb - 6u)) & 63u);
 }
 
+/* ---- the record of a group's items in bins of 1024 and above, kept per gyo_td_bins by address (gy_oracle.h) */
+typedef struct {
+	uint32_t v; /* the value the item was binned at (< 2^26) */
+	uint64_t sum, cnt;
+} tdbins_item;
+
+typedef struct tdbins_rec {
+	const gyo_td_bins *key;
+	tdbins_item *it;
+	size_t n, cap;
+	struct tdbins_rec *next;
+} tdbins_rec;
+
+static tdbins_rec *tdbins_recs;
+
+static tdbins_rec *rec_find(const gyo_td_bins *b)
+{
+	for (tdbins_rec *r = tdbins_recs; r; r = r->next)
+		if (r->key == b) return r;
+	return NULL;
+}
+
+static void rec_drop(const gyo_td_bins *b)
+{
+	for (tdbins_rec **pr = &tdbins_recs; *pr; pr = &(*pr)->next) {
+		if ((*pr)->key != b) continue;
+		tdbins_rec *r = *pr;
+		*pr = r->next;
+		free(r->it);
+		free(r);
+		return;
+	}
+}
+
+static void rec_add(const gyo_td_bins *b, uint32_t v, uint64_t sum, uint64_t cnt)
+{
+	tdbins_rec *r = rec_find(b);
+
+	if (!r) {
+		r = (tdbins_rec *)calloc(1, sizeof(*r));
+		if (!r) abort();
+		r->key = b;
+		r->next = tdbins_recs;
+		tdbins_recs = r;
+	}
+	if (r->n == r->cap) {
+		r->cap = r->cap ? 2 * r->cap : 1024;
+		r->it = (tdbins_item *)realloc(r->it, r->cap * sizeof(tdbins_item));
+		if (!r->it) abort();
+	}
+	r->it[r->n].v = v;
+	r->it[r->n].sum = sum;
+	r->it[r->n].cnt = cnt;
+	r->n++;
+}
+
 void gyo_tdbins_init(gyo_td_bins *b)
 {
+	rec_drop(b);
 	memset(b, 0, sizeof(*b));
 	b->vmin = INT_MAX;
 	b->vmax = INT_MIN;
 }
 
+/* an item of weight cnt and sum at the integer value v: into the bin of v (and into the record when that bin may be refined) */
+static void tdbins_put(gyo_td_bins *b, uint32_t v, uint64_t sum, uint64_t cnt)
+{
+	uint32_t k;
+
+	if (v >= (1u << 26)) v = (1u << 26) - 1u;
+	k = gyo_td_value_bin(v);
+	b->sum[k] += sum;
+	b->cnt[k] += cnt;
+	if (k >= 1024u) rec_add(b, v, sum, cnt);
+}
+
 static void tdbins_add_cluster(gyo_td_bins *b, int64_t sum, uint64_t cnt)
 {
 	uint64_t thr;
-	uint32_t k;
 
 	if (!cnt) return;
 	thr = sum <= 0 ? 0 : ((uint64_t)sum + cnt - 1) / cnt; /* ceil of the mean */
-	k = gyo_td_value_bin(thr > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)thr);
-	b->sum[k] += (uint64_t)sum;
-	b->cnt[k] += cnt;
+	tdbins_put(b, thr > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)thr, (uint64_t)sum, cnt);
 }
 
 void gyo_tdbins_add_values(gyo_td_bins *b, const int32_t *vals, size_t m)
 {
 	for (size_t i = 0; i < m; i++) {
-		const uint32_t k = gyo_td_value_bin(vals[i] < 0 ? 0u : (uint32_t)vals[i]);
-		b->sum[k] += (uint64_t)(int64_t)vals[i];
-		b->cnt[k] += 1;
+		tdbins_put(b, vals[i] < 0 ? 0u : (uint32_t)vals[i], (uint64_t)(int64_t)vals[i], 1);
 		if (vals[i] < b->vmin) b->vmin = vals[i];
 		if (vals[i] > b->vmax) b->vmax = vals[i];
 	}
@@ -258,34 +330,101 @@ void gyo_tdbins_add_td64(gyo_td_bins *b, const gyo_td64 *o)
 	}
 }
 
+/* ---- the refinement: which bins are marked, and their fine cells */
+typedef struct {
+	uint32_t nmark, per;       /* marked bins; fine cells per marked bin */
+	uint8_t mark[GYO_TD_BINS]; /* 0: not marked, else 1 + the bin's index among the marked ones (<= 199) */
+	uint64_t fcnt[GYO_TD_FINE], fsum[GYO_TD_FINE];
+} tdbins_fine;
+
+/* marked bin k (>= 1024, width 2^sh, lower edge lo) has min(per, 2^sh) cells of equal width; value v of the bin is in cell ((v - lo) c) >> sh */
+static uint32_t tdbins_ncell(const tdbins_fine *f, uint32_t k)
+{
+	const uint32_t sh = 4u + (k - 1024u) / 64u;
+	return f->per < (1u << sh) ? f->per : (1u << sh);
+}
+
+static uint32_t tdbins_cell(const tdbins_fine *f, uint32_t v, uint32_t k)
+{
+	const uint32_t sh = 4u + (k - 1024u) / 64u, lo = (64u + ((k - 1024u) & 63u)) << sh;
+	return (uint32_t)(f->mark[k] - 1u) * f->per + (((v - lo) * tdbins_ncell(f, k)) >> sh);
+}
+
+/* marked: a bin of 1024 and above whose first and last unit points fall into different clusters and that holds more than 1 / GYO_TD_HEAVY of
+ * the group's weight (every cluster boundary cuts one bin at most: <= GYO_TD_NB - 1 marked bins); then the recorded items of the marked bins
+ * into their cells -- the second pass over the members */
+static void tdbins_refine(const gyo_td_bins *b, uint64_t N, const tdbins_rec *r, tdbins_fine *f)
+{
+	uint64_t W = 0;
+
+	memset(f, 0, sizeof(*f));
+	if (!r) return;
+	for (int k = 0; k < GYO_TD_BINS; k++) {
+		const uint64_t w = b->cnt[k];
+		if (k >= 1024 && w > N / GYO_TD_HEAVY && gyo_td_cluster(2 * W + 1, 2 * N) != gyo_td_cluster(2 * (W + w - 1) + 1, 2 * N))
+			f->mark[k] = (uint8_t)++f->nmark;
+		W += w;
+	}
+	if (!f->nmark) return;
+	f->per = GYO_TD_FINE / f->nmark;
+	for (size_t i = 0; i < r->n; i++) {
+		const uint32_t k = gyo_td_value_bin(r->it[i].v);
+		if (!f->mark[k]) continue;
+		const uint32_t c = tdbins_cell(f, r->it[i].v, k);
+		f->fsum[c] += r->it[i].sum;
+		f->fcnt[c] += r->it[i].cnt;
+	}
+}
+
+/* a unit (a bin, or a cell of a marked bin) of weight w and sum s whose points start after W on the rank axis of N */
+static void tdbins_cut(gyo_td64 *out, uint64_t w, uint64_t s, uint64_t W, uint64_t N)
+{
+	uint64_t r = 0, given = 0;
+
+	while (r < w) {
+		const uint32_t a = gyo_td_cluster(2 * (W + r) + 1, 2 * N);
+		uint64_t lo = r + 1, hi = w, upto; /* r1 = first point after r that is not in cluster a (w when there is none) */
+		while (lo < hi) {
+			const uint64_t mid = lo + (hi - lo) / 2;
+			if (gyo_td_cluster(2 * (W + mid) + 1, 2 * N) != a) hi = mid; else lo = mid + 1;
+		}
+		upto = (uint64_t)(((unsigned __int128)s * lo) / w); /* floor(s r1 / w); == s at r1 == w */
+		out->sum[a] += (int64_t)(upto - given);
+		out->cnt[a] += lo - r;
+		given = upto;
+		r = lo;
+	}
+}
+
 void gyo_tdbins_finish(const gyo_td_bins *b, gyo_td64 *out)
 {
 	uint64_t N = 0, W = 0;
+	tdbins_fine *f;
 
 	gyo_td64_init(out);
 	out->vmin = b->vmin;
 	out->vmax = b->vmax;
 	for (int k = 0; k < GYO_TD_BINS; k++) N += b->cnt[k];
-	if (!N) return;
-	for (int k = 0; k < GYO_TD_BINS; k++) {
-		const uint64_t w = b->cnt[k], s = b->sum[k];
-		uint64_t r = 0, given = 0;
-
-		while (r < w) {
-			const uint32_t a = gyo_td_cluster(2 * (W + r) + 1, 2 * N);
-			uint64_t lo = r + 1, hi = w, upto; /* r1 = first point after r that is not in cluster a (w when there is none) */
-			while (lo < hi) {
-				const uint64_t mid = lo + (hi - lo) / 2;
-				if (gyo_td_cluster(2 * (W + mid) + 1, 2 * N) != a) hi = mid; else lo = mid + 1;
-			}
-			upto = (uint64_t)(((unsigned __int128)s * lo) / w); /* floor(s r1 / w); == s at r1 == w */
-			out->sum[a] += (int64_t)(upto - given);
-			out->cnt[a] += lo - r;
-			given = upto;
-			r = lo;
-		}
-		W += w;
+	if (!N) {
+		rec_drop(b);
+		return;
 	}
+	f = (tdbins_fine *)malloc(sizeof(*f));
+	if (!f) abort();
+	tdbins_refine(b, N, rec_find(b), f);
+	for (int k = 0; k < GYO_TD_BINS; k++) {
+		if (!f->mark[k]) {
+			tdbins_cut(out, b->cnt[k], b->sum[k], W, N);
+			W += b->cnt[k];
+			continue;
+		}
+		for (uint32_t c = (uint32_t)(f->mark[k] - 1u) * f->per, e = c + tdbins_ncell(f, (uint32_t)k); c < e; c++) {
+			tdbins_cut(out, f->fcnt[c], f->fsum[c], W, N);
+			W += f->fcnt[c];
+		}
+	}
+	free(f);
+	rec_drop(b);
 }
 
 /* the same interpolation as gyo_td_quantile (gy_oracle.c:669-715) on the wide counters; only + - * / on doubles */

@@ -1,7 +1,8 @@
 // TEST INFRASTRUCTURE (CPU): the LOGIC of the roll-up digests k_rollup_accum / k_rollup_cluster (gyeeta_amd/csrc/gys_rollup.hpp) under the CPU
 // stand-in of the device model: the digest of a GROUP of services (kind 0: the union by value bin of the members' clusters and buffered values)
 // and of a group of roll-up slabs (kind 1: the cross-rank / cluster / global roll-up), with 64-bit counters -- groups of 0, 1 and many members,
-// members without clusters, without buffered values and without anything, all-equal values, values >= 1024 ms, a group whose weight passes
+// members without clusters, without buffered values and without anything, all-equal values, values >= 1024 ms, narrow ranges in wide bins
+// (the marked bins, the second pass into their fine cells), a group whose weight passes
 // 2^32, groups cut into several chunks (several workgroups add to one group's bins), a buffer stride that is not a multiple of four words
 // (argument 2) -- equal, cluster by cluster, to the oracle's gyo_tdbins_* (oracle/gy_oracle_rollup.c), minimum / maximum included, and
 // independent of the order of the members.  Build + run: tests/test_kernel_logic_cpu.py.
@@ -82,7 +83,8 @@ int main(int argc, char **argv)
 			const uint32_t nbatches = s % 7 == 0 ? 1u : 2u + rng() % 6u; // (one small batch: buffered values only, no clusters yet)
 			for (uint32_t k = 0; k < nbatches; ++k) {
 				std::vector<int32_t> v(s % 7 == 0 ? 40u : 100u + rng() % 700u);
-				for (auto &x : v) x = s == 8 ? 37 : draw(rng, mu, sigma); // service 8: all values equal
+				for (auto &x : v) // service 8: all values equal; 15 and 22: a few milliseconds wide at 1.5 s and 600 s (bins cut into fine cells)
+					x = s == 8 ? 37 : s == 15 ? 1497 + (int32_t)(rng() % 7u) : s == 22 ? 600000 + (int32_t)(rng() % 5001u) : draw(rng, mu, sigma);
 				gyo_tdb_add_batch(&b, v.data(), v.size());
 			}
 			if (s % 7 == 1) { // no buffered values: everything merged
@@ -102,7 +104,7 @@ int main(int argc, char **argv)
 		minmax[s] = gyo_td_total(&b.d) ? make_int2(b.d.vmin, b.d.vmax) : make_int2(INT32_MAX, INT32_MIN);
 	}
 	// groups of services: empty, one member, a few, many, one with the three heavy services (5, 12, 19, 26, 33 are heavy)
-	std::vector<std::vector<uint32_t>> groups = {{}, {4}, {3}, {0, 1, 2}, {5, 12, 19, 26}, {8, 8, 9}, {}};
+	std::vector<std::vector<uint32_t>> groups = {{}, {4}, {3}, {0, 1, 2}, {5, 12, 19, 26}, {8, 8, 9}, {}, {15}, {22, 15, 16}};
 	{
 		std::vector<uint32_t> all(S);
 		for (uint32_t s = 0; s < S; ++s) all[s] = s;
@@ -159,6 +161,8 @@ int main(int argc, char **argv)
 		q.ngroups = NG;
 		kemu::launch(2, 256, 0, [&] { k_rollup_init(q.bins, NG); });
 		kemu::launch(3, GYS_RB_NT, 0, [&] { k_rollup_accum(q); }); // (fewer workgroups than chunks: they loop)
+		kemu::launch(2, 256, 0, [&] { k_rollup_mark(q); });
+		kemu::launch(3, GYS_RB_NT, 0, [&] { k_rollup_refine(q); });
 		kemu::launch(2, 256, 0, [&] { k_rollup_cluster(q); });
 		for (uint32_t g = 0; g < NG; ++g) compare(per == 5u ? "services in chunks of 5" : "services", g, slabs[g], want[g]);
 	}
@@ -179,7 +183,7 @@ int main(int argc, char **argv)
 		slabs.push_back(odd);
 		want.push_back(oddw);
 	}
-	std::vector<std::vector<uint32_t>> sg = {{3, 4, 7}, {7, 0, 4, 3}, {0}, {}, {8, 7}, {7, 8}, {NG}, {3, NG, 4}};
+	std::vector<std::vector<uint32_t>> sg = {{3, 4, 7}, {7, 0, 4, 3}, {0}, {}, {8, 7}, {7, 8}, {NG}, {3, NG, 4}, {7, 8, 7, 8}, {9, 10, 8}};
 	std::vector<uint32_t> soff(1, 0), smem;
 	for (auto &g : sg) {
 		smem.insert(smem.end(), g.begin(), g.end());
@@ -201,6 +205,8 @@ int main(int argc, char **argv)
 		q2.ngroups = (uint32_t)sg.size();
 		kemu::launch(1, 256, 0, [&] { k_rollup_init(q2.bins, q2.ngroups); });
 		kemu::launch(4, GYS_RB_NT, 0, [&] { k_rollup_accum(q2); });
+		kemu::launch(3, 256, 0, [&] { k_rollup_mark(q2); });
+		kemu::launch(4, GYS_RB_NT, 0, [&] { k_rollup_refine(q2); });
 		kemu::launch((uint32_t)sg.size(), 256, 0, [&] { k_rollup_cluster(q2); });
 		for (uint32_t g = 0; g < sg.size(); ++g) {
 			gyo_td_bins *b = new gyo_td_bins;

@@ -25,9 +25,10 @@ def register_world(eng, orc, hosts, svcs_per_host, cluster_of=None):
     return info, gids
 
 
-def make_resp_events(rng, h, n, svcs_per_host, lat_mu=3.0, lat_sigma=1.5, bad_frac=0.02, unknown_frac=0.02, zero_ip_frac=0.01):
+def make_resp_events(rng, h, n, svcs_per_host, lat_mu=3.0, lat_sigma=1.5, bad_frac=0.02, unknown_frac=0.02, zero_ip_frac=0.01, lat=None):
     """numpy RESP_EVENT batch for synthetic host h with the edge cases the reference filters: negative / > 1e6 latencies
-    (common/gy_socket_stat.cc:1521-1524), events for ports without a listener, and 0.0.0.0 client addresses (get_as_inaddr quirk)."""
+    (common/gy_socket_stat.cc:1521-1524), events for ports without a listener, and 0.0.0.0 client addresses (get_as_inaddr quirk).
+    lat (optional): the latencies in ms instead of the lognormal draw -- n values, or a function of the events' service indices that returns them."""
     ev = np.zeros(n, dtype=wire.RESP_EVENT)
     s = rng.integers(0, svcs_per_host, n)
     ev["saddr"] = int.from_bytes((0x0A000000 | (h & 0xFFFFFF)).to_bytes(4, "big"), "little")  # 10.x.y.z as ip32_be
@@ -35,7 +36,11 @@ def make_resp_events(rng, h, n, svcs_per_host, lat_mu=3.0, lat_sigma=1.5, bad_fr
     ev["netns"] = wire.listener_netns(h, s)
     ev["sport_be"] = wire.listener_port(s)
     ev["dport_be"] = rng.integers(16000, 65536, n)
-    lat = np.minimum(np.floor(rng.lognormal(lat_mu, lat_sigma, n)), 1e6).astype(np.uint32)
+    if lat is None:
+        lat = np.minimum(np.floor(rng.lognormal(lat_mu, lat_sigma, n)), 1e6).astype(np.uint32)
+    else:
+        lat = np.asarray(lat(s) if callable(lat) else lat, dtype=np.uint32)
+        assert lat.shape == (n,)
     lrcv = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
     bad = rng.random(n) < bad_frac
     lat = np.where(bad & (rng.random(n) < 0.5), np.uint32(1000001) + rng.integers(0, 1000, n).astype(np.uint32), lat)

@@ -30,8 +30,8 @@ the hot kernels run on synthetic input:
     k_svc_aggr on random records / filters / sorts / maxrecs against the oracle's serial walk (oracle/gy_oracle_query.c);
   * the listener's state decision k_listener_decide (tests/cpp/kemu/test_ldecide.cc): TCP_LISTENER::get_curr_state's decision tree on random
     scan records and task / host inputs, the history bytes carried over six rounds, against oracle/gy_oracle_lstate.c;
-  * the roll-up digests k_rollup_accum / k_rollup_cluster (tests/cpp/kemu/test_rollup.cc): groups of services and groups of slabs, the union by value bin, 64-bit
-    weights beyond 2^32, members without clusters / without buffered values / empty.
+  * the roll-up digests k_rollup_accum / k_rollup_mark / k_rollup_refine / k_rollup_cluster (tests/cpp/kemu/test_rollup.cc): groups of services and groups of
+    slabs, the union by value bin and its refined bins, 64-bit weights beyond 2^32, members without clusters / without buffered values / empty.
 This does not replace the -m gpu parity tests (no memory model, no execution masks, no timing): it catches logic errors in kernel
 changes before GPU minutes are spent on them.  The programs are built and run side by side once per session (they mostly wait in
 barriers); each test below looks at one of them."""
