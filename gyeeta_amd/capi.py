@@ -183,6 +183,11 @@ SIGNATURES = {
     "gys_tdigest_merge_slabs_dev": (C.c_int, [vp, vp, C.c_uint32, vp]),
     "gys_tdigest_slab_quantiles": (C.c_int, [vp, vp, f64p, C.c_uint32, f64p]),
     "gys_num_clusters": (C.c_uint32, [vp]),
+    "gys_scan_distinct_dev": (C.c_int, [vp, vp]),
+    "gys_query_distinct": (C.c_int, [vp, C.c_uint64, f64p]),
+    "gys_hll_file_bytes": (C.c_uint32, [vp]),
+    "gys_hll_rollup_dev": (C.c_int, [vp, C.c_int, vp, vp]),
+    "gys_hll_merge_files_dev": (C.c_int, [vp, vp, C.c_uint32, vp, vp]),
     "gys_ingest_active_conns": (C.c_int, [vp, mid, vp, C.c_uint32, vp]),
     "gys_ingest_active_conns_dev": (C.c_int, [vp, vp, C.c_uint32]),
     "gys_query_pair_cms": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_int, u64p]),
@@ -194,6 +199,7 @@ SIGNATURES = {
     "gys_window_close_rccl": (C.c_int, [vp, vp, C.c_uint64]),
     "gys_window_close": (C.c_int, [vp, C.c_uint64]),
     "gys_tdigest_global_rccl": (C.c_int, [vp, vp, vp]),
+    "gys_hll_global_rccl": (C.c_int, [vp, vp, vp, vp]),
     "gys_tdigest_sql_text": (C.c_int, [vp, C.c_uint64, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "gys_tdigest_sql_binary": (C.c_int, [vp, C.c_uint64, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "gys_query_hist_level_stats": (C.c_int, [vp, C.c_uint64, C.c_int, C.c_uint64, C.POINTER(TimeHistVal), C.c_uint32, i64p, i64p, f64p]),

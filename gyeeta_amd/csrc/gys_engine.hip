@@ -28,6 +28,7 @@
 
 #include "gys_kernels.hpp"
 #include "gys_rollup.hpp"
+#include "gys_hllroll.hpp"
 #include "gys_huge.hpp"
 #include "gys_svcquery.hpp"
 
@@ -422,6 +423,15 @@ struct gys_ctx {
 	uint32_t *rb_host_members = nullptr;
 	RollupChunk *rb_host_chunks = nullptr;
 	uint32_t rb_host_nsvc = ~0u, rb_host_nh = ~0u, rb_host_nchunks = 0;
+	RollupChunk *rb_host_gchunks = nullptr; // [hosts] {host, first chunk, end chunk} of rb_host_chunks: a host's chunks as the members of a second pass
+	// distinct counts (gys_hllroll.hpp): the clusters' host lists (rebuilt when a host's cluster changed) and one scratch buffer (grows:
+	// a file per chunk, per host and per group -- first call / after a registration only)
+	uint32_t *hl_cl_members = nullptr;
+	RollupChunk *hl_cl_chunks = nullptr, *hl_cl_gchunks = nullptr;
+	uint32_t hl_cl_nchunks = 0, hl_cl_ncl = ~0u;
+	std::vector<uint32_t> hl_cl_snap; // host_cluster_h the lists were built from
+	uint8_t *hl_buf = nullptr;
+	size_t hl_buf_bytes = 0;
 	uint8_t *svc_bithist = nullptr; // [max_services][2] TCP_LISTENER::issue_bit_hist_ / high_resp_bit_hist_ (gys_decide_listener_state_dev; allocated on first use)
 	uint32_t lvl_last_epoch = 0;
 	int64_t *lvl_first = nullptr;     // [max_services] time (s) of the service's first window close (firstTime_ of its series), 0: none yet
@@ -2676,7 +2686,7 @@ void gys_destroy(gys_ctx *c)
 			c->batch_cnt, c->batch_off, c->scan_block_sums, c->ev_kv, c->staged, c->huge_scratch, c->huge_acc, c->huge_tail, c->huge_tb_list, c->huge_bm, c->huge_chunk_off, c->huge_fb_list, c->hll32, c->svc_ctr, c->svc_win, c->svc_state, c->svc_claim, c->svc_hll, c->host_summ_win, c->host_summ_last, c->host_state,
 			c->host_state_epoch, c->host_cluster, c->counters, c->misc, c->htbl, c->hlst, c->hdesc, c->wire_jump[0], c->wire_jump[1], c->wire_cnt,
 			c->wire_rank, c->wire_bsums, c->wire_status, c->wire_mark, c->wire_flags, c->wire_msgs, c->last, c->last_act32, c->last_act64, c->ring_act32, c->ring_act64, c->act_live, c->q_cand_key, c->q_out_keys, c->q_cand_slot, c->q_misc, c->q_host_mask, c->q_slot_list, c->q_set, c->q_out_rows, c->q_acc, c->q_cnt, c->dev_staging, c->dev_offsets, c->csr_off, c->csr_mem, c->svc_act, c->d_epoch, c->topn_slot,
-			c->topn_metric, c->dev_pcts, c->zipf_cdf, c->lvl_snap, c->lvl_last, c->lvl_last_tag, c->svc_bithist, c->rb_bins, c->rb_host_members, c->rb_host_chunks, c->lvl_first, c->qps_hist, c->act_hist, c->cand_pool, c->own_arena ? c->arena : nullptr};
+			c->topn_metric, c->dev_pcts, c->zipf_cdf, c->lvl_snap, c->lvl_last, c->lvl_last_tag, c->svc_bithist, c->rb_bins, c->rb_host_members, c->rb_host_chunks, c->rb_host_gchunks, c->hl_cl_members, c->hl_cl_chunks, c->hl_cl_gchunks, c->hl_buf, c->lvl_first, c->qps_hist, c->act_hist, c->cand_pool, c->own_arena ? c->arena : nullptr};
 	for (void *p : ptrs)
 		if (p) hipFree(p);
 	if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
@@ -3977,6 +3987,17 @@ static void rollup_chunks(const std::vector<uint32_t> &off, uint32_t per, std::v
 		for (uint32_t m = off[g]; m < off[g + 1]; m += per) chunks.push_back(RollupChunk{g, m, std::min(off[g + 1], m + per), 0u});
 }
 
+// the chunks of group g (rollup_chunks lays them out group after group) as ONE chunk of a second pass: {g, first chunk, end chunk}
+static void rollup_group_chunks(const std::vector<RollupChunk> &chunks, uint32_t ngroups, std::vector<RollupChunk> &gchunks)
+{
+	size_t i = 0;
+	for (uint32_t g = 0; g < ngroups; ++g) {
+		const uint32_t c0 = (uint32_t)i;
+		while (i < chunks.size() && chunks[i].group == g) ++i;
+		gchunks.push_back(RollupChunk{g, c0, (uint32_t)i, 0u});
+	}
+}
+
 // bins of `ngroups` groups <- the members the chunks name; slabs out.  d_chunks / d_members: DEVICE arrays.
 static int rollup_run(gys_ctx *c, int kind, const RollupChunk *d_chunks, uint32_t nchunks, const uint32_t *d_members, uint32_t ngroups,
 		      const gys_tdigest_slab *d_in, gys_tdigest_slab *d_out)
@@ -4035,6 +4056,43 @@ static int rollup_slabs(gys_ctx *c, const std::vector<uint32_t> &off, const std:
 	return rc;
 }
 
+// host level: members = the host's services.  The lists stay on the device until a service or a host is registered (10^7 services: 40 MB).
+// rb_host_gchunks names each host's range of chunks (the distinct-count roll-up joins a host's chunk files in a second pass).
+static int rollup_host_lists(gys_ctx *c)
+{
+	const uint32_t nh = (uint32_t)c->hosts.size();
+	if (c->rb_host_nsvc != c->nsvc || c->rb_host_nh != nh) {
+		std::vector<uint32_t> off(nh + 1, 0), members;
+		members.reserve(c->nsvc);
+		for (uint32_t h = 0; h < nh; ++h) {
+			const std::vector<uint32_t> &sl = c->host_lst[h].all_slots;
+			members.insert(members.end(), sl.begin(), sl.end());
+			off[h + 1] = (uint32_t)members.size();
+		}
+		std::vector<RollupChunk> chunks, gchunks;
+		rollup_chunks(off, GYS_RB_CHUNK_SERVICES, chunks);
+		rollup_group_chunks(chunks, nh, gchunks);
+		HIPCHK(hipStreamSynchronize(c->stream));
+		if (c->rb_host_members) HIPCHK(hipFree(c->rb_host_members));
+		if (c->rb_host_chunks) HIPCHK(hipFree(c->rb_host_chunks));
+		if (c->rb_host_gchunks) HIPCHK(hipFree(c->rb_host_gchunks));
+		c->rb_host_members = nullptr;
+		c->rb_host_chunks = nullptr;
+		c->rb_host_gchunks = nullptr;
+		c->rb_host_nsvc = ~0u;
+		HIPCHK(hipMalloc((void **)&c->rb_host_members, std::max<size_t>(members.size(), 1) * 4));
+		HIPCHK(hipMalloc((void **)&c->rb_host_chunks, std::max<size_t>(chunks.size(), 1) * sizeof(RollupChunk)));
+		HIPCHK(hipMalloc((void **)&c->rb_host_gchunks, std::max<size_t>(gchunks.size(), 1) * sizeof(RollupChunk)));
+		if (!members.empty()) HIPCHK(hipMemcpy(c->rb_host_members, members.data(), members.size() * 4, hipMemcpyHostToDevice));
+		if (!chunks.empty()) HIPCHK(hipMemcpy(c->rb_host_chunks, chunks.data(), chunks.size() * sizeof(RollupChunk), hipMemcpyHostToDevice));
+		if (!gchunks.empty()) HIPCHK(hipMemcpy(c->rb_host_gchunks, gchunks.data(), gchunks.size() * sizeof(RollupChunk), hipMemcpyHostToDevice));
+		c->rb_host_nchunks = (uint32_t)chunks.size();
+		c->rb_host_nsvc = c->nsvc;
+		c->rb_host_nh = nh;
+	}
+	return GYS_OK;
+}
+
 int gys_tdigest_rollup_dev(gys_ctx *c, int scope, gys_tdigest_slab *d_out)
 try {
 	GYS_ENTER(c);
@@ -4045,30 +4103,9 @@ try {
 		if (scope == GYS_ROLLUP_GLOBAL) HIPCHK(hipMemsetAsync(d_out, 0, sizeof(gys_tdigest_slab), c->stream));
 		return GYS_OK;
 	}
-	// host level: members = the host's services.  The lists stay on the device until a service or a host is registered (10^7 services: 40 MB).
-	if (c->rb_host_nsvc != c->nsvc || c->rb_host_nh != nh) {
-		std::vector<uint32_t> off(nh + 1, 0), members;
-		members.reserve(c->nsvc);
-		for (uint32_t h = 0; h < nh; ++h) {
-			const std::vector<uint32_t> &sl = c->host_lst[h].all_slots;
-			members.insert(members.end(), sl.begin(), sl.end());
-			off[h + 1] = (uint32_t)members.size();
-		}
-		std::vector<RollupChunk> chunks;
-		rollup_chunks(off, GYS_RB_CHUNK_SERVICES, chunks);
-		HIPCHK(hipStreamSynchronize(c->stream));
-		if (c->rb_host_members) HIPCHK(hipFree(c->rb_host_members));
-		if (c->rb_host_chunks) HIPCHK(hipFree(c->rb_host_chunks));
-		c->rb_host_members = nullptr;
-		c->rb_host_chunks = nullptr;
-		c->rb_host_nsvc = ~0u;
-		HIPCHK(hipMalloc((void **)&c->rb_host_members, std::max<size_t>(members.size(), 1) * 4));
-		HIPCHK(hipMalloc((void **)&c->rb_host_chunks, std::max<size_t>(chunks.size(), 1) * sizeof(RollupChunk)));
-		if (!members.empty()) HIPCHK(hipMemcpy(c->rb_host_members, members.data(), members.size() * 4, hipMemcpyHostToDevice));
-		if (!chunks.empty()) HIPCHK(hipMemcpy(c->rb_host_chunks, chunks.data(), chunks.size() * sizeof(RollupChunk), hipMemcpyHostToDevice));
-		c->rb_host_nchunks = (uint32_t)chunks.size();
-		c->rb_host_nsvc = c->nsvc;
-		c->rb_host_nh = nh;
+	{
+		const int rcl = rollup_host_lists(c);
+		if (rcl) return rcl;
 	}
 	gys_tdigest_slab *d_hosts = d_out;
 	if (scope != GYS_ROLLUP_HOST) HIPCHK(hipMalloc((void **)&d_hosts, sizeof(gys_tdigest_slab) * nh));
@@ -4324,6 +4361,229 @@ try {
 	}
 	if (rc == GYS_OK) rc = gys_tdigest_merge_slabs_dev(c, d_all, (uint32_t)nranks, d_out); // (synchronises the stream)
 	hipFree(d_all);
+	return rc;
+} GYS_CATCH_ALL
+
+// ------------------------------------------------------------------------------------------------ distinct counts (gys_hllroll.hpp)
+#define HLL_CHECK()                                                                       \
+	if (!c->svc_hll) {                                                                \
+		set_err("per-service HyperLogLog is off (gys_config.svc_hll_p = 0)");     \
+		return GYS_ERR_STATE;                                                     \
+	}
+#define HLL_ALIGNED(ptr) (((uintptr_t)(ptr) & 15u) == 0)
+
+// the scratch buffer: [partial files: one per chunk][host files][group files], each part 256-byte aligned.  Grows, never shrinks; its
+// size follows from the registered services / hosts / clusters (chunks <= services / 1024 + hosts), not from how often it is asked for.
+static int hll_scratch(gys_ctx *c, size_t nparts, size_t nhostfiles, size_t ngroupfiles, uint8_t **parts, uint8_t **hostfiles, uint8_t **groupfiles)
+{
+	const size_t m = (size_t)1 << c->cfg.svc_hll_p;
+	const size_t a = align_up(std::max<size_t>(nparts, 1) * m, 256), b = align_up(nhostfiles * m, 256), g = align_up(ngroupfiles * m, 256);
+	if (c->hl_buf_bytes < a + b + g) {
+		if (c->hl_buf) {
+			HIPCHK(hipStreamSynchronize(c->stream));
+			HIPCHK(hipFree(c->hl_buf));
+			c->hl_buf = nullptr;
+			c->hl_buf_bytes = 0;
+		}
+		HIPCHK(hipMalloc((void **)&c->hl_buf, a + b + g));
+		c->hl_buf_bytes = a + b + g;
+	}
+	*parts = c->hl_buf;
+	if (hostfiles) *hostfiles = c->hl_buf + a;
+	if (groupfiles) *groupfiles = c->hl_buf + a + b;
+	return GYS_OK;
+}
+
+static void hll_union_launch(gys_ctx *c, const HllUnionP &q)
+{
+	if (q.nchunks) hipLaunchKernelGGL(k_hll_union, dim3(std::min<uint32_t>(q.nchunks, (uint32_t)c->ncu * 8)), dim3(GYS_HLL_NT), 0, c->stream, q);
+}
+static void hll_estimate_launch(gys_ctx *c, const uint8_t *files, uint32_t n, double *d_out)
+{
+	const uint64_t pieces = (uint64_t)n << (c->cfg.svc_hll_p - 4);
+	if (n) hipLaunchKernelGGL(k_hll_estimate, dim3((uint32_t)std::min<uint64_t>((pieces + GYS_HLL_NT - 1) / GYS_HLL_NT, (uint64_t)c->ncu * 16)), dim3(GYS_HLL_NT), 0, c->stream,
+				  files, n, (uint32_t)c->cfg.svc_hll_p, d_out);
+}
+// dst[0] = union of the n contiguous files at src: chunks of GYS_RB_CHUNK_SERVICES files into `parts`, then the chunks' files
+static void hll_union_contiguous(gys_ctx *c, const uint8_t *src, uint32_t n, uint8_t *parts, uint8_t *dst)
+{
+	const uint32_t p = c->cfg.svc_hll_p, nch = (n + GYS_RB_CHUNK_SERVICES - 1) / GYS_RB_CHUNK_SERVICES;
+	if (nch <= 1) {
+		hll_union_launch(c, HllUnionP{src, dst, nullptr, nullptr, 1u, n, std::max(n, 1u), p});
+		return;
+	}
+	hll_union_launch(c, HllUnionP{src, parts, nullptr, nullptr, nch, n, GYS_RB_CHUNK_SERVICES, p});
+	hll_union_launch(c, HllUnionP{parts, dst, nullptr, nullptr, 1u, nch, nch, p});
+}
+
+// the clusters' host lists on the device: rebuilt when a host was registered or moved to another cluster
+static int hll_cluster_lists(gys_ctx *c)
+{
+	const uint32_t ncl = (uint32_t)c->cluster_names.size();
+	if (c->hl_cl_ncl == ncl && c->hl_cl_snap == c->host_cluster_h) return GYS_OK;
+	const uint32_t nh = (uint32_t)c->hosts.size();
+	std::vector<uint32_t> off(ncl + 1, 0), members;
+	members.reserve(nh);
+	{
+		std::vector<uint32_t> cnt(ncl + 1, 0);
+		for (uint32_t h = 0; h < nh; ++h)
+			if (c->host_cluster_h[h] < ncl) cnt[c->host_cluster_h[h] + 1]++;
+		for (uint32_t cl = 0; cl < ncl; ++cl) off[cl + 1] = off[cl] + cnt[cl + 1];
+		members.resize(off[ncl]);
+		std::vector<uint32_t> at(off.begin(), off.end() - 1);
+		for (uint32_t h = 0; h < nh; ++h)
+			if (c->host_cluster_h[h] < ncl) members[at[c->host_cluster_h[h]]++] = h;
+	}
+	std::vector<RollupChunk> chunks, gchunks;
+	rollup_chunks(off, GYS_RB_CHUNK_SERVICES, chunks);
+	rollup_group_chunks(chunks, ncl, gchunks);
+	HIPCHK(hipStreamSynchronize(c->stream));
+	if (c->hl_cl_members) HIPCHK(hipFree(c->hl_cl_members));
+	if (c->hl_cl_chunks) HIPCHK(hipFree(c->hl_cl_chunks));
+	if (c->hl_cl_gchunks) HIPCHK(hipFree(c->hl_cl_gchunks));
+	c->hl_cl_members = nullptr;
+	c->hl_cl_chunks = nullptr;
+	c->hl_cl_gchunks = nullptr;
+	c->hl_cl_ncl = ~0u;
+	HIPCHK(hipMalloc((void **)&c->hl_cl_members, std::max<size_t>(members.size(), 1) * 4));
+	HIPCHK(hipMalloc((void **)&c->hl_cl_chunks, std::max<size_t>(chunks.size(), 1) * sizeof(RollupChunk)));
+	HIPCHK(hipMalloc((void **)&c->hl_cl_gchunks, std::max<size_t>(gchunks.size(), 1) * sizeof(RollupChunk)));
+	if (!members.empty()) HIPCHK(hipMemcpy(c->hl_cl_members, members.data(), members.size() * 4, hipMemcpyHostToDevice));
+	if (!chunks.empty()) HIPCHK(hipMemcpy(c->hl_cl_chunks, chunks.data(), chunks.size() * sizeof(RollupChunk), hipMemcpyHostToDevice));
+	if (!gchunks.empty()) HIPCHK(hipMemcpy(c->hl_cl_gchunks, gchunks.data(), gchunks.size() * sizeof(RollupChunk), hipMemcpyHostToDevice));
+	c->hl_cl_nchunks = (uint32_t)chunks.size();
+	c->hl_cl_snap = c->host_cluster_h;
+	c->hl_cl_ncl = ncl;
+	return GYS_OK;
+}
+
+int gys_scan_distinct_dev(gys_ctx *c, double *d_out)
+try {
+	GYS_ENTER(c);
+	if (!c || !d_out) return GYS_ERR_INVAL;
+	HLL_CHECK();
+	{
+		ProfScope ps(c, "hll_scan");
+		hll_estimate_launch(c, c->svc_hll, c->nsvc, d_out);
+	}
+	HIPCHK(hipGetLastError());
+	return GYS_OK;
+} GYS_CATCH_ALL
+
+int gys_query_distinct(gys_ctx *c, uint64_t glob_id, double *out)
+try {
+	GYS_ENTER(c);
+	if (!c || !out) return GYS_ERR_INVAL;
+	HLL_CHECK();
+	auto it = c->gid_map_h.find(glob_id);
+	if (it == c->gid_map_h.end()) {
+		set_err("unknown glob_id %016llx", (unsigned long long)glob_id);
+		return GYS_ERR_INVAL;
+	}
+	uint8_t *d_tmp = nullptr;
+	{
+		const int rcs = hll_scratch(c, 1, 0, 0, &d_tmp, nullptr, nullptr);
+		if (rcs) return rcs;
+	}
+	// the scan's kernel on this one slot: the same code turns the same bytes into the same double
+	hll_estimate_launch(c, c->svc_hll + ((size_t)it->second << c->cfg.svc_hll_p), 1u, (double *)d_tmp);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(out, d_tmp, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	return GYS_OK;
+} GYS_CATCH_ALL
+
+uint32_t gys_hll_file_bytes(gys_ctx *c) { return c && c->cfg.svc_hll_p ? 1u << c->cfg.svc_hll_p : 0u; }
+
+int gys_hll_rollup_dev(gys_ctx *c, int scope, uint8_t *d_regs, double *d_est)
+try {
+	GYS_ENTER(c);
+	if (!c || (!d_regs && !d_est) || scope < GYS_ROLLUP_HOST || scope > GYS_ROLLUP_GLOBAL || !HLL_ALIGNED(d_regs)) {
+		set_err("gys_hll_rollup_dev: null outputs, an output that is not 16-byte aligned or an unknown scope");
+		return GYS_ERR_INVAL;
+	}
+	HLL_CHECK();
+	const uint32_t p = c->cfg.svc_hll_p, nh = (uint32_t)c->hosts.size(), ncl = (uint32_t)c->cluster_names.size();
+	const size_t m = (size_t)1 << p;
+	const uint32_t ngroups = scope == GYS_ROLLUP_HOST ? nh : (scope == GYS_ROLLUP_CLUSTER ? ncl : 1u);
+	if (!ngroups) return GYS_OK;
+	int rc = rollup_host_lists(c);
+	if (rc == GYS_OK && scope == GYS_ROLLUP_CLUSTER) rc = hll_cluster_lists(c);
+	if (rc) return rc;
+	const uint32_t nparts = std::max(std::max(c->rb_host_nchunks, scope == GYS_ROLLUP_CLUSTER ? c->hl_cl_nchunks : 0u), (nh + GYS_RB_CHUNK_SERVICES - 1) / GYS_RB_CHUNK_SERVICES);
+	uint8_t *parts = nullptr, *hostfiles = nullptr, *groupfiles = nullptr;
+	rc = hll_scratch(c, nparts, scope == GYS_ROLLUP_HOST && d_regs ? 0 : nh, scope == GYS_ROLLUP_HOST || d_regs ? 0 : ngroups, &parts, &hostfiles, &groupfiles);
+	if (rc) return rc;
+	if (scope == GYS_ROLLUP_HOST && d_regs) hostfiles = d_regs;
+	uint8_t *out = scope == GYS_ROLLUP_HOST ? hostfiles : (d_regs ? d_regs : groupfiles);
+	{
+		ProfScope ps(c, "hll_rollup_hosts"); // the services' files -> one file per chunk -> one per host
+		hll_union_launch(c, HllUnionP{c->svc_hll, parts, c->rb_host_chunks, c->rb_host_members, c->rb_host_nchunks, 0u, 0u, p});
+		hll_union_launch(c, HllUnionP{parts, hostfiles, c->rb_host_gchunks, nullptr, nh, 0u, 0u, p});
+	}
+	if (scope != GYS_ROLLUP_HOST) {
+		ProfScope ps(c, "hll_union_files");
+		if (scope == GYS_ROLLUP_GLOBAL) {
+			if (nh) hll_union_contiguous(c, hostfiles, nh, parts, out);
+			else HIPCHK(hipMemsetAsync(out, 0, m, c->stream));
+		} else {
+			hll_union_launch(c, HllUnionP{hostfiles, parts, c->hl_cl_chunks, c->hl_cl_members, c->hl_cl_nchunks, 0u, 0u, p});
+			hll_union_launch(c, HllUnionP{parts, out, c->hl_cl_gchunks, nullptr, ncl, 0u, 0u, p});
+		}
+	}
+	if (d_est) {
+		ProfScope ps(c, "hll_estimate_groups");
+		hll_estimate_launch(c, out, ngroups, d_est);
+	}
+	HIPCHK(hipGetLastError());
+	return GYS_OK;
+} GYS_CATCH_ALL
+
+int gys_hll_merge_files_dev(gys_ctx *c, const uint8_t *d_in, uint32_t n, uint8_t *d_out, double *d_est)
+try {
+	GYS_ENTER(c);
+	if (!c || !d_in || (!d_out && !d_est) || n == 0 || !HLL_ALIGNED(d_in) || !HLL_ALIGNED(d_out)) {
+		set_err("gys_hll_merge_files_dev: null pointers, a pointer that is not 16-byte aligned or n = 0");
+		return GYS_ERR_INVAL;
+	}
+	HLL_CHECK();
+	uint8_t *parts = nullptr, *groupfiles = nullptr;
+	const int rc = hll_scratch(c, (n + GYS_RB_CHUNK_SERVICES - 1) / GYS_RB_CHUNK_SERVICES, 0, d_out ? 0 : 1, &parts, nullptr, &groupfiles);
+	if (rc) return rc;
+	uint8_t *out = d_out ? d_out : groupfiles;
+	{
+		ProfScope ps(c, "hll_union_files");
+		hll_union_contiguous(c, d_in, n, parts, out);
+	}
+	if (d_est) hll_estimate_launch(c, out, 1u, d_est);
+	HIPCHK(hipGetLastError());
+	return GYS_OK;
+} GYS_CATCH_ALL
+
+int gys_hll_global_rccl(gys_ctx *c, void *comm, uint8_t *d_regs, double *d_est)
+try {
+	GYS_ENTER(c);
+	if (!c || !comm || (!d_regs && !d_est)) return GYS_ERR_INVAL;
+	HLL_CHECK();
+	int nranks = 1, rank = 0;
+	RCCL_API(R);
+	NCCLCHK(R->CommCount((ncclComm_t)comm, &nranks));
+	NCCLCHK(R->CommUserRank((ncclComm_t)comm, &rank));
+	const size_t m = (size_t)1 << c->cfg.svc_hll_p;
+	uint8_t *d_all = nullptr;
+	HIPCHK(hipMalloc((void **)&d_all, m * (size_t)nranks));
+	int rc = gys_hll_rollup_dev(c, GYS_ROLLUP_GLOBAL, d_all + m * (size_t)rank, nullptr); // in place: this rank's file sits at its own position
+	if (rc == GYS_OK) {
+		const ncclResult_t r = R->AllGather(d_all + m * (size_t)rank, d_all, m, ncclUint8, (ncclComm_t)comm, c->stream);
+		if (r != ncclSuccess) {
+			set_err("ncclAllGather failed: %s", R->GetErrorString(r));
+			rc = GYS_ERR_HIP;
+		}
+	}
+	if (rc == GYS_OK) rc = gys_hll_merge_files_dev(c, d_all, (uint32_t)nranks, d_regs, d_est);
+	const hipError_t es = hipStreamSynchronize(c->stream); // d_all is freed below
+	hipFree(d_all);
+	if (rc == GYS_OK) HIPCHK(es);
 	return rc;
 } GYS_CATCH_ALL
 

@@ -341,6 +341,60 @@ class SketchEngine:
         self.sync()
         return out, np.frombuffer(out.cpu().numpy().tobytes(), dtype=self.SLAB_DT)[0]
 
+    # ---------------------------------------------------------------- distinct-flow counts from the per-service HyperLogLog registers (svc_hll_p)
+    def scan_distinct(self):
+        """the distinct-flow estimate of EVERY service in one device pass: [nsvc] float64 (gys_scan_distinct_dev; the open window)"""
+        n = self.num_services()
+        out = self.torch.zeros(max(n, 1), dtype=self.torch.float64, device=self.device)
+        self.order()
+        capi.check(self.L.gys_scan_distinct_dev(self.h, C.c_void_p(out.data_ptr())))
+        self.sync()
+        return out[:n].cpu().numpy()
+
+    def query_distinct(self, glob_id):
+        """one service's distinct-flow estimate (gys_query_distinct): the same bits as scan_distinct()[slot]"""
+        out = C.c_double()
+        capi.check(self.L.gys_query_distinct(self.h, int(glob_id), C.byref(out)))
+        return out.value
+
+    def _hll_groups(self, scope):
+        return {capi.ROLLUP_HOST: self.L.gys_num_hosts(self.h), capi.ROLLUP_CLUSTER: self.L.gys_num_clusters(self.h), capi.ROLLUP_GLOBAL: 1}.get(scope, 1)
+
+    def hll_rollup(self, scope, want_regs=True):
+        """register files and estimates of the hosts / clusters / the rank (gys_hll_rollup_dev): (files (ngroups, m) uint8 or None when
+        want_regs is False, estimates (ngroups,) float64)"""
+        n, m = self._hll_groups(scope), self.L.gys_hll_file_bytes(self.h)
+        regs = self.torch.zeros(max(n * m, 16), dtype=self.torch.uint8, device=self.device) if want_regs else None
+        est = self.torch.zeros(max(n, 1), dtype=self.torch.float64, device=self.device)
+        self.order()
+        capi.check(self.L.gys_hll_rollup_dev(self.h, scope, C.c_void_p(regs.data_ptr()) if want_regs else None, C.c_void_p(est.data_ptr())))
+        self.sync()
+        return (regs[:n * m].cpu().numpy().reshape(n, m) if want_regs else None), est[:n].cpu().numpy()
+
+    def hll_merge_files(self, regs):
+        """the union of register files (numpy (n, m) uint8, or a torch uint8 device tensor of n * m bytes) and its estimate
+        (gys_hll_merge_files_dev): ((m,) uint8, float)"""
+        m = self.L.gys_hll_file_bytes(self.h)
+        if not self.torch.is_tensor(regs):
+            regs = self.torch.from_numpy(np.ascontiguousarray(regs, dtype=np.uint8).reshape(-1)).to(self.device)
+        n = regs.numel() // m if m else 0
+        out = self.torch.zeros(max(m, 16), dtype=self.torch.uint8, device=self.device)
+        est = self.torch.zeros(1, dtype=self.torch.float64, device=self.device)
+        self.order()
+        capi.check(self.L.gys_hll_merge_files_dev(self.h, C.c_void_p(regs.data_ptr()), n, C.c_void_p(out.data_ptr()), C.c_void_p(est.data_ptr())))
+        self.sync()
+        return out[:m].cpu().numpy(), float(est.cpu().numpy()[0])
+
+    def hll_global_rccl(self):
+        """the all-rank register file and its estimate (gys_hll_global_rccl; join_rccl first): ((m,) uint8, float), the same on every rank"""
+        m = self.L.gys_hll_file_bytes(self.h)
+        out = self.torch.zeros(max(m, 16), dtype=self.torch.uint8, device=self.device)
+        est = self.torch.zeros(1, dtype=self.torch.float64, device=self.device)
+        self.order()
+        capi.check(self.L.gys_hll_global_rccl(self.h, self.comm, C.c_void_p(out.data_ptr()), C.c_void_p(est.data_ptr())))
+        self.sync()
+        return out[:m].cpu().numpy(), float(est.cpu().numpy()[0])
+
     def slab_quantiles(self, dev_slab, qs, index=0):
         qa = (C.c_double * len(qs))(*qs)
         out = (C.c_double * len(qs))()

@@ -389,6 +389,34 @@ int gys_tdigest_slab_quantiles(gys_ctx *ctx, const gys_tdigest_slab *d_slab, con
 uint32_t gys_num_clusters(gys_ctx *ctx);
 
 /* -------------------------------------------------------------------------------------------------------------------
+ * Distinct-flow counts per service, host, cluster and rank from the per-service HyperLogLog registers (gys_config.svc_hll_p = 4 .. 10;
+ * GYS_ERR_STATE when it is 0).  Definitions (oracle/gy_oracle.h: gyo_hll_merge, gyo_hll_estimate):
+ *   a register FILE is 1 << svc_hll_p bytes, byte i = the largest rank seen for register i (one row of gys_export_svc_hll);
+ *   the file of a GROUP (a host = its services, a cluster = its hosts, global = all hosts of this rank, any list of files) is the
+ *   byte-wise maximum of its members' files; it does not depend on their order; without members, or without events: all zero;
+ *   the ESTIMATE of a file is Flajolet's raw estimator alpha m^2 / sum 2^-rank, and linear counting m ln(m / zeros) when the raw value
+ *   is <= 2.5 m and a register is zero.  The all-zero file gives exactly 0.  It is a function of the file's bytes alone: the per-service
+ *   scan, the one-service query and the roll-ups return bit-identical doubles for identical files.
+ * THE OPEN WINDOW: every call reads the per-service registers as gys_export_svc_hll returns them at the same moment -- the window being
+ * filled; closing a window clears them (ask before the close, as for gys_scan_listener_state_dev) -- and modifies no engine state.
+ * DEVICE pointers to files must be 16-byte aligned (any device allocation is).  Asynchronous on the context stream like the other
+ * *_dev calls (gys_sync to wait), except gys_query_distinct and gys_hll_global_rccl, which return when the result is there. */
+/* the estimate of EVERY registered service in one pass: d_out (DEVICE) [gys_num_services] doubles */
+int gys_scan_distinct_dev(gys_ctx *ctx, double *d_out);
+/* one service, result in HOST memory: the same device code on one slot, bit-identical to that slot of gys_scan_distinct_dev.
+ * GYS_ERR_INVAL for an unknown glob_id */
+int gys_query_distinct(gys_ctx *ctx, uint64_t glob_id, double *out);
+/* bytes of one register file of this context (1 << svc_hll_p; 0 when svc_hll_p is 0) */
+uint32_t gys_hll_file_bytes(gys_ctx *ctx);
+/* group files and / or their estimates; scope = GYS_ROLLUP_HOST: one per host slot [gys_num_hosts]; _CLUSTER: one per registered cluster
+ * [gys_num_clusters]; _GLOBAL: one.  d_regs (DEVICE, ngroups * gys_hll_file_bytes) and d_est (DEVICE, ngroups doubles): either may be
+ * NULL, not both.  The hosts' member lists are those of gys_tdigest_rollup_dev (kept on the device, rebuilt after a registration). */
+int gys_hll_rollup_dev(gys_ctx *ctx, int scope, uint8_t *d_regs, double *d_est);
+/* the union of the n files d_in (DEVICE, contiguous, not overlapping the outputs) into d_out[0] and / or its estimate into d_est[0]
+ * (either may be NULL, not both): the cross-rank step after an all-gather, or any caller-defined group */
+int gys_hll_merge_files_dev(gys_ctx *ctx, const uint8_t *d_in, uint32_t n, uint8_t *d_out, double *d_est);
+
+/* -------------------------------------------------------------------------------------------------------------------
  * The window exchange inside the library (RCCL over xGMI; no torch, no caller-written collective).  Replaces
  * MCONN_HANDLER::send_cluster_state -> SHCONN_HANDLER::aggregate_cluster_state (server/gy_mconnhdlr.cc:16052-16118,
  * server/gy_shconnhdlr.cc:4583-4720): one process per GPU, every rank calls gys_window_close_rccl at the 5-s boundary.
@@ -405,6 +433,9 @@ int gys_window_close_rccl(gys_ctx *ctx, void *comm, uint64_t tusec);
 /* the global response-time digest across ranks: this rank's GYS_ROLLUP_GLOBAL slab, ncclAllGather of the fixed-size slabs, their
  * roll-up (gys_tdigest_merge_slabs_dev) into d_out[0] (DEVICE) -- the same slab on every rank */
 int gys_tdigest_global_rccl(gys_ctx *ctx, void *comm, gys_tdigest_slab *d_out);
+/* the distinct-flow count across ranks: this rank's GYS_ROLLUP_GLOBAL file, ncclAllGather of one file per rank, their union
+ * (gys_hll_merge_files_dev) into d_regs[0] / its estimate into d_est[0] (DEVICE; either may be NULL, not both) -- the same on every rank */
+int gys_hll_global_rccl(gys_ctx *ctx, void *comm, uint8_t *d_regs, double *d_est);
 
 /* -------------------------------------------------------------------------------------------------------------------
  * a service's response-time t-digest in the external forms of the Postgres tdigest type, so that the reference's SQL
