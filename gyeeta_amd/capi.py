@@ -21,7 +21,7 @@ class Config(C.Structure):
                 ("enable_tdigest", C.c_uint32), ("svc_hll_p", C.c_uint32), ("resp_path", C.c_uint32),
                 ("max_batch_events", C.c_uint64), ("stream", C.c_void_p), ("reduce_arena", C.c_void_p),
                 ("reduce_arena_bytes", C.c_uint64), ("enable_levels", C.c_uint32), ("td_buf_values", C.c_uint32),
-                ("conn_pair_cms", C.c_uint32), ("td_pend_cap", C.c_uint32)]
+                ("conn_pair_cms", C.c_uint32), ("td_pend_cap", C.c_uint32), ("svc_hll_levels", C.c_uint32)]
 
 
 class ListenerInfo(C.Structure):
@@ -188,6 +188,9 @@ SIGNATURES = {
     "gys_hll_file_bytes": (C.c_uint32, [vp]),
     "gys_hll_rollup_dev": (C.c_int, [vp, C.c_int, vp, vp]),
     "gys_hll_merge_files_dev": (C.c_int, [vp, vp, C.c_uint32, vp, vp]),
+    "gys_scan_distinct_level_dev": (C.c_int, [vp, C.c_int, C.c_uint64, vp]),
+    "gys_query_distinct_level": (C.c_int, [vp, C.c_uint64, C.c_int, C.c_uint64, f64p]),
+    "gys_hll_rollup_level_dev": (C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, vp, vp]),
     "gys_ingest_active_conns": (C.c_int, [vp, mid, vp, C.c_uint32, vp]),
     "gys_ingest_active_conns_dev": (C.c_int, [vp, vp, C.c_uint32]),
     "gys_query_pair_cms": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_int, u64p]),
@@ -235,6 +238,7 @@ SIGNATURES = {
     "gys_export_svc_counters": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
     "gys_export_global_hist": (C.c_int, [vp, C.POINTER(HistRec)]),
     "gys_export_svc_hll": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
+    "gys_export_svc_hll_level": (C.c_int, [vp, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, vp]),
     "gys_get_counters": (C.c_int, [vp, C.POINTER(Counters)]),
     "gys_resp_queue_pending": (C.c_int, [vp, u64p]),
     "gys_hist_init_dev": (C.c_int, [vp, C.c_int, vp, C.c_uint32]),

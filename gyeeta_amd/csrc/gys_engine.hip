@@ -432,6 +432,13 @@ struct gys_ctx {
 	std::vector<uint32_t> hl_cl_snap; // host_cluster_h the lists were built from
 	uint8_t *hl_buf = nullptr;
 	size_t hl_buf_bytes = 0;
+	// distinct counts of the closed windows (cfg.svc_hll_levels; "levels" in gys_hllroll.hpp)
+	uint8_t *hl_lvl = nullptr;        // [GYS_HLL_LVL_FILES][max_services] files: last, the two rings, all
+	uint8_t *hl_view = nullptr;       // a level's files of every service, materialised for gys_hll_rollup_level_dev (nsvc files; grows)
+	size_t hl_view_bytes = 0;
+	int64_t hl_t_last = -1;           // close time (s) of the last window rolled into hl_lvl, -1: none yet
+	uint32_t hl_roll_epoch = 0xFFFFFFFEu; // the window rolled last (a finish step that is retried after a failure further down must not roll twice)
+	int64_t hl_close_t = 0;           // close time (s) the prepared window was given (gys_window_prepare; the roll runs in gys_window_finish)
 	uint8_t *svc_bithist = nullptr; // [max_services][2] TCP_LISTENER::issue_bit_hist_ / high_resp_bit_hist_ (gys_decide_listener_state_dev; allocated on first use)
 	uint32_t lvl_last_epoch = 0;
 	int64_t *lvl_first = nullptr;     // [max_services] time (s) of the service's first window close (firstTime_ of its series), 0: none yet
@@ -1495,6 +1502,44 @@ inline int64_t level_bucket_start(int64_t t, int64_t dur, uint32_t j)
 
 inline uint32_t level_bucket_idx(int64_t t, int64_t dur) { return (uint32_t)((t % dur) * GYS_LEVEL_RING / dur); }
 
+inline uint8_t *hll_level_array(gys_ctx *c, uint32_t f) { return c->hl_lvl + (((uint64_t)f * c->cfg.max_services) << c->cfg.svc_hll_p); }
+
+// window close at c->hl_close_t: the open window's registers enter `last`, the two current ring buckets and `all`, and are cleared
+// (k_hll_level_roll).  The ring arithmetic is level_roll's: a bucket whose start was crossed since the previous close expires.
+int hll_level_roll(gys_ctx *c)
+{
+	if (c->hl_roll_epoch == c->epoch) return GYS_OK; // once per window
+	c->hl_roll_epoch = c->epoch;
+	const int64_t tnow = std::max(c->hl_close_t, c->hl_t_last); // time does not go backwards
+	const uint32_t p = c->cfg.svc_hll_p;
+	uint32_t mask[2] = {0, 0}, cur[2];
+	for (int li = 0; li < 2; ++li) {
+		const int64_t dur = LEVEL_SECS[li + 1];
+		for (uint32_t j = 0; j < GYS_LEVEL_RING; ++j)
+			if (c->hl_t_last >= 0 && level_bucket_start(tnow, dur, j) > c->hl_t_last) mask[li] |= 1u << j;
+		cur[li] = level_bucket_idx(tnow, dur);
+	}
+	c->hl_t_last = tnow;
+	if (!c->nsvc) return GYS_OK; // (slots above nsvc have never been written: nothing to clear)
+	ProfScope ps(c, "hll_level_roll");
+	for (int li = 0; li < 2; ++li)
+		for (uint32_t j = 0; j < GYS_LEVEL_RING; ++j)
+			if (((mask[li] >> j) & 1u) && j != cur[li])
+				HIPCHK(hipMemsetAsync(hll_level_array(c, GYS_HLL_LVL_RING + (uint32_t)li * GYS_LEVEL_RING + j), 0, (uint64_t)c->nsvc << p, c->stream));
+	HllLevelRollP q{};
+	q.open = (uint4 *)c->svc_hll;
+	q.last = (uint4 *)hll_level_array(c, GYS_HLL_LVL_LAST);
+	q.ring1 = (uint4 *)hll_level_array(c, GYS_HLL_LVL_RING + cur[0]);
+	q.ring2 = (uint4 *)hll_level_array(c, GYS_HLL_LVL_RING + GYS_LEVEL_RING + cur[1]);
+	q.all = (uint4 *)hll_level_array(c, GYS_HLL_LVL_ALL);
+	q.npieces = (uint64_t)c->nsvc << (p - 4u);
+	q.fresh1 = (mask[0] >> cur[0]) & 1u;
+	q.fresh2 = (mask[1] >> cur[1]) & 1u;
+	hipLaunchKernelGGL(k_hll_level_roll, dim3(grid_for(q.npieces, GYS_HLL_NT, (uint32_t)c->ncu * 16)), dim3(GYS_HLL_NT), 0, c->stream, q);
+	HIPCHK(hipGetLastError());
+	return GYS_OK;
+}
+
 // window close at tusec: remember the closing window as level 0 and snapshot the cumulative records into every ring bucket whose
 // start was crossed since the previous close
 int level_roll(gys_ctx *c, uint64_t tusec)
@@ -2377,7 +2422,7 @@ try {
 		return GYS_ERR_INVAL;
 	}
 	if (!cfg->max_hosts || !cfg->max_services || cfg->max_hosts > 65534 || !cfg->max_clusters || cfg->nranks == 0 || cfg->rank >= cfg->nranks ||
-	    (cfg->svc_hll_p && (cfg->svc_hll_p < 4 || cfg->svc_hll_p > 10)) ||
+	    (cfg->svc_hll_p && (cfg->svc_hll_p < 4 || cfg->svc_hll_p > 10)) || cfg->svc_hll_levels > 1 || (cfg->svc_hll_levels && !cfg->svc_hll_p) ||
 	    (cfg->td_pend_cap && (cfg->td_pend_cap < 64u || cfg->td_pend_cap > GYS_TD_PEND_CAP_MAX)) ||
 	    (cfg->td_buf_values && (cfg->td_buf_values < (cfg->td_pend_cap ? cfg->td_pend_cap : GYS_TD_PEND_CAP) + 64u || cfg->td_buf_values > GYS_PCAP_MAX))) {
 		set_err("bad config values");
@@ -2481,6 +2526,7 @@ try {
 	HIPCHK((resp_host_lds_attr<8, true, true, 2>(&c->resp_dyn_max)));
 	c->host_seen.reserve(H);
 	if (cfg->svc_hll_p) ALLOC(c->svc_hll, S << cfg->svc_hll_p);
+	if (cfg->svc_hll_levels) ALLOC(c->hl_lvl, ((uint64_t)GYS_HLL_LVL_FILES * S) << cfg->svc_hll_p);
 	if (cfg->enable_levels) {
 		ALLOC(c->lvl_snap, 2 * GYS_LEVEL_RING * S);
 		ALLOC(c->lvl_last, cfg->enable_levels == 1 ? S : 1);
@@ -2686,7 +2732,7 @@ void gys_destroy(gys_ctx *c)
 			c->batch_cnt, c->batch_off, c->scan_block_sums, c->ev_kv, c->staged, c->huge_scratch, c->huge_acc, c->huge_tail, c->huge_tb_list, c->huge_bm, c->huge_chunk_off, c->huge_fb_list, c->hll32, c->svc_ctr, c->svc_win, c->svc_state, c->svc_claim, c->svc_hll, c->host_summ_win, c->host_summ_last, c->host_state,
 			c->host_state_epoch, c->host_cluster, c->counters, c->misc, c->htbl, c->hlst, c->hdesc, c->wire_jump[0], c->wire_jump[1], c->wire_cnt,
 			c->wire_rank, c->wire_bsums, c->wire_status, c->wire_mark, c->wire_flags, c->wire_msgs, c->last, c->last_act32, c->last_act64, c->ring_act32, c->ring_act64, c->act_live, c->q_cand_key, c->q_out_keys, c->q_cand_slot, c->q_misc, c->q_host_mask, c->q_slot_list, c->q_set, c->q_out_rows, c->q_acc, c->q_cnt, c->dev_staging, c->dev_offsets, c->csr_off, c->csr_mem, c->svc_act, c->d_epoch, c->topn_slot,
-			c->topn_metric, c->dev_pcts, c->zipf_cdf, c->lvl_snap, c->lvl_last, c->lvl_last_tag, c->svc_bithist, c->rb_bins, c->rb_host_members, c->rb_host_chunks, c->rb_host_gchunks, c->hl_cl_members, c->hl_cl_chunks, c->hl_cl_gchunks, c->hl_buf, c->lvl_first, c->qps_hist, c->act_hist, c->cand_pool, c->own_arena ? c->arena : nullptr};
+			c->topn_metric, c->dev_pcts, c->zipf_cdf, c->lvl_snap, c->lvl_last, c->lvl_last_tag, c->svc_bithist, c->rb_bins, c->rb_host_members, c->rb_host_chunks, c->rb_host_gchunks, c->hl_cl_members, c->hl_cl_chunks, c->hl_cl_gchunks, c->hl_buf, c->hl_lvl, c->hl_view, c->lvl_first, c->qps_hist, c->act_hist, c->cand_pool, c->own_arena ? c->arena : nullptr};
 	for (void *p : ptrs)
 		if (p) hipFree(p);
 	if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
@@ -3267,6 +3313,7 @@ try {
 		set_err("window already prepared");
 		return GYS_ERR_STATE;
 	}
+	c->hl_close_t = (int64_t)(tusec / 1000000ull); // (the per-service registers are rolled where they are cleared: gys_window_finish)
 	if (c->cfg.enable_levels) {
 		const int rcl = level_roll(c, tusec); // before the eager fold below: it needs the cumulative records WITHOUT the closing window
 		if (rcl) return rcl;
@@ -3291,7 +3338,8 @@ static hipError_t enqueue_finish(gys_ctx *c, hipStream_t st)
 	if (c->nsvc) {
 		// CONN_BITMAP cleared every window (secs_to_reset_ = 5); lazily (per key, on its next touch) when the per-key pass runs
 		if (!c->cfg.enable_tdigest && (e = hipMemsetAsync(c->bitmap, 0, (uint64_t)c->nsvc * GYS_BM_WORDS * 4, st)) != hipSuccess) return e;
-		if (c->svc_hll && (e = hipMemsetAsync(c->svc_hll, 0, (uint64_t)c->nsvc << c->cfg.svc_hll_p, st)) != hipSuccess) return e;
+		// (with svc_hll_levels the roll that runs in front of this sequence has cleared them: hll_level_roll)
+		if (c->svc_hll && !c->hl_lvl && (e = hipMemsetAsync(c->svc_hll, 0, (uint64_t)c->nsvc << c->cfg.svc_hll_p, st)) != hipSuccess) return e;
 	}
 	const uint64_t hb = (uint64_t)c->hosts.size() * 16 * 4;
 	if (((uintptr_t)c->arena & 15u) == 0) { // (a caller's reduce_arena is torch / hipMalloc memory: always; the plain sequence below otherwise)
@@ -3328,6 +3376,12 @@ try {
 	if (!c->prepared) {
 		set_err("gys_window_finish without gys_window_prepare");
 		return GYS_ERR_STATE;
+	}
+	if (c->hl_lvl) {
+		// once per window, whatever was retried before: the roll happens here, where the open registers used to be cleared, with the close
+		// time of the prepare step.  In front of the captured sequence, not inside it (the bucket indices change from window to window).
+		const int rcl = hll_level_roll(c);
+		if (rcl) return rcl;
 	}
 	ProfScope ps(c, "window_finish");
 	// keep the (reduced) registers of this window for queries, start the next window from zero.  The sequence is the same every
@@ -3369,7 +3423,9 @@ try {
 // are due (connection accumulators, Count-Min rows of the response path), k_window_prepare, the eager-mode sweep, the copy / clear
 // sequence and the window-number increment -- captured once per (registry shape, which folds are due) and replayed with one launch.
 // Not capturable, and therefore run as gys_window_prepare + gys_window_finish: multi-level windows (the snapshot masks depend on the
-// close time) and more than one rank (the exchange sits between the two halves; gys_window_close_rccl).
+// close time) and more than one rank (the exchange sits between the two halves; gys_window_close_rccl).  With svc_hll_levels the graph
+// is kept: the roll of the per-service registers (hll_level_roll, its bucket indices depend on the close time) is launched in front of
+// it, and the graph then holds no clear of those registers.
 int gys_window_close(gys_ctx *c, uint64_t tusec)
 try {
 	GYS_ENTER(c);
@@ -3407,6 +3463,11 @@ try {
 		c->resp_dirty = rd;
 	}
 	if (cg.state == 1) {
+		if (c->hl_lvl) {
+			c->hl_close_t = (int64_t)(tusec / 1000000ull);
+			const int rcl = hll_level_roll(c); // (nothing in the graph reads the per-service registers)
+			if (rcl) return rcl;
+		}
 		ProfScope ps(c, "window_close_graph");
 		HIPCHK(hipGraphLaunch(cg.x, c->stream));
 		c->conn_dirty = false;
@@ -4495,14 +4556,9 @@ try {
 
 uint32_t gys_hll_file_bytes(gys_ctx *c) { return c && c->cfg.svc_hll_p ? 1u << c->cfg.svc_hll_p : 0u; }
 
-int gys_hll_rollup_dev(gys_ctx *c, int scope, uint8_t *d_regs, double *d_est)
-try {
-	GYS_ENTER(c);
-	if (!c || (!d_regs && !d_est) || scope < GYS_ROLLUP_HOST || scope > GYS_ROLLUP_GLOBAL || !HLL_ALIGNED(d_regs)) {
-		set_err("gys_hll_rollup_dev: null outputs, an output that is not 16-byte aligned or an unknown scope");
-		return GYS_ERR_INVAL;
-	}
-	HLL_CHECK();
+// host / cluster / rank files and estimates of the services' files at src ([nsvc] files: the open registers, or a level's files)
+static int hll_rollup_src(gys_ctx *c, const uint8_t *src, int scope, uint8_t *d_regs, double *d_est)
+{
 	const uint32_t p = c->cfg.svc_hll_p, nh = (uint32_t)c->hosts.size(), ncl = (uint32_t)c->cluster_names.size();
 	const size_t m = (size_t)1 << p;
 	const uint32_t ngroups = scope == GYS_ROLLUP_HOST ? nh : (scope == GYS_ROLLUP_CLUSTER ? ncl : 1u);
@@ -4518,7 +4574,7 @@ try {
 	uint8_t *out = scope == GYS_ROLLUP_HOST ? hostfiles : (d_regs ? d_regs : groupfiles);
 	{
 		ProfScope ps(c, "hll_rollup_hosts"); // the services' files -> one file per chunk -> one per host
-		hll_union_launch(c, HllUnionP{c->svc_hll, parts, c->rb_host_chunks, c->rb_host_members, c->rb_host_nchunks, 0u, 0u, p});
+		hll_union_launch(c, HllUnionP{src, parts, c->rb_host_chunks, c->rb_host_members, c->rb_host_nchunks, 0u, 0u, p});
 		hll_union_launch(c, HllUnionP{parts, hostfiles, c->rb_host_gchunks, nullptr, nh, 0u, 0u, p});
 	}
 	if (scope != GYS_ROLLUP_HOST) {
@@ -4537,6 +4593,17 @@ try {
 	}
 	HIPCHK(hipGetLastError());
 	return GYS_OK;
+}
+
+int gys_hll_rollup_dev(gys_ctx *c, int scope, uint8_t *d_regs, double *d_est)
+try {
+	GYS_ENTER(c);
+	if (!c || (!d_regs && !d_est) || scope < GYS_ROLLUP_HOST || scope > GYS_ROLLUP_GLOBAL || !HLL_ALIGNED(d_regs)) {
+		set_err("gys_hll_rollup_dev: null outputs, an output that is not 16-byte aligned or an unknown scope");
+		return GYS_ERR_INVAL;
+	}
+	HLL_CHECK();
+	return hll_rollup_src(c, c->svc_hll, scope, d_regs, d_est);
 } GYS_CATCH_ALL
 
 int gys_hll_merge_files_dev(gys_ctx *c, const uint8_t *d_in, uint32_t n, uint8_t *d_out, double *d_est)
@@ -4585,6 +4652,105 @@ try {
 	hipFree(d_all);
 	if (rc == GYS_OK) HIPCHK(es);
 	return rc;
+} GYS_CATCH_ALL
+
+// ---- the levels of the closed windows (gys_config.svc_hll_levels; definition in include/gysketch.h)
+#define HLL_LEVEL_CHECK(level)                                                                   \
+	if ((level) < 0 || (level) >= GYS_NLEVELS) {                                             \
+		set_err("level %d outside 0 .. %d", (int)(level), GYS_NLEVELS - 1);              \
+		return GYS_ERR_INVAL;                                                            \
+	}                                                                                        \
+	if (!c->hl_lvl) {                                                                        \
+		set_err("distinct-count levels are off (gys_config.svc_hll_levels = 0)");        \
+		return GYS_ERR_STATE;                                                            \
+	}
+
+// the level's files of slots [first, first + n) at time tusec into d_files and / or their estimates into d_est (k_hll_level_view)
+static int hll_level_view(gys_ctx *c, int level, uint64_t tusec, uint32_t first, uint32_t n, uint8_t *d_files, double *d_est)
+{
+	if (!n) return GYS_OK;
+	const int64_t tl = c->hl_t_last, tq = std::max((int64_t)(tusec / 1000000ull), tl);
+	const uint32_t p = c->cfg.svc_hll_p;
+	HllLevelViewP q{};
+	uint32_t farr = GYS_HLL_LVL_LAST;
+	if (level == 0) {
+		q.mask = tl >= 0 && tq - tl < LEVEL_SECS[0] ? 1u : 0u; // the window closed last, until a window's length has passed without another close
+	} else if (level == GYS_NLEVELS - 1) {
+		farr = GYS_HLL_LVL_ALL;
+		q.mask = 1u;
+	} else {
+		farr = GYS_HLL_LVL_RING + (uint32_t)(level - 1) * GYS_LEVEL_RING;
+		for (uint32_t j = 0; j < GYS_LEVEL_RING; ++j) // a bucket whose start has been crossed since the last close has expired (it is cleared at the next close)
+			if (tl >= 0 && !(level_bucket_start(tq, LEVEL_SECS[level], j) > tl)) q.mask |= 1u << j;
+	}
+	q.base = hll_level_array(c, farr);
+	q.stride = (uint64_t)c->cfg.max_services << p;
+	q.first = first;
+	q.n = n;
+	q.p = p;
+	q.files = d_files;
+	q.est = d_est;
+	const uint64_t pieces = (uint64_t)n << (p - 4u);
+	hipLaunchKernelGGL(k_hll_level_view, dim3((uint32_t)std::min<uint64_t>((pieces + GYS_HLL_NT - 1) / GYS_HLL_NT, (uint64_t)c->ncu * 16)), dim3(GYS_HLL_NT), 0, c->stream, q);
+	HIPCHK(hipGetLastError());
+	return GYS_OK;
+}
+
+int gys_scan_distinct_level_dev(gys_ctx *c, int level, uint64_t tusec, double *d_out)
+try {
+	GYS_ENTER(c);
+	if (!c || !d_out) return GYS_ERR_INVAL;
+	HLL_LEVEL_CHECK(level);
+	ProfScope ps(c, "hll_level_scan");
+	return hll_level_view(c, level, tusec, 0u, c->nsvc, nullptr, d_out);
+} GYS_CATCH_ALL
+
+int gys_query_distinct_level(gys_ctx *c, uint64_t glob_id, int level, uint64_t tusec, double *out)
+try {
+	GYS_ENTER(c);
+	if (!c || !out) return GYS_ERR_INVAL;
+	HLL_LEVEL_CHECK(level);
+	auto it = c->gid_map_h.find(glob_id);
+	if (it == c->gid_map_h.end()) {
+		set_err("unknown glob_id %016llx", (unsigned long long)glob_id);
+		return GYS_ERR_INVAL;
+	}
+	uint8_t *d_tmp = nullptr;
+	int rc = hll_scratch(c, 1, 0, 0, &d_tmp, nullptr, nullptr);
+	if (rc) return rc;
+	rc = hll_level_view(c, level, tusec, it->second, 1u, nullptr, (double *)d_tmp); // the scan's kernel on this one slot
+	if (rc) return rc;
+	HIPCHK(hipMemcpyAsync(out, d_tmp, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	return GYS_OK;
+} GYS_CATCH_ALL
+
+int gys_hll_rollup_level_dev(gys_ctx *c, int scope, int level, uint64_t tusec, uint8_t *d_regs, double *d_est)
+try {
+	GYS_ENTER(c);
+	if (!c || (!d_regs && !d_est) || scope < GYS_ROLLUP_HOST || scope > GYS_ROLLUP_GLOBAL || !HLL_ALIGNED(d_regs)) {
+		set_err("gys_hll_rollup_level_dev: null outputs, an output that is not 16-byte aligned or an unknown scope");
+		return GYS_ERR_INVAL;
+	}
+	HLL_LEVEL_CHECK(level);
+	// the level's files of every service once into scratch (nsvc files; grows, never shrinks), then the roll-up of the open window on them
+	const size_t need = std::max<size_t>((size_t)c->nsvc << c->cfg.svc_hll_p, 16);
+	if (c->hl_view_bytes < need) {
+		if (c->hl_view) {
+			HIPCHK(hipStreamSynchronize(c->stream));
+			HIPCHK(hipFree(c->hl_view));
+			c->hl_view = nullptr;
+			c->hl_view_bytes = 0;
+		}
+		HIPCHK(hipMalloc((void **)&c->hl_view, need));
+		c->hl_view_bytes = need;
+	}
+	{
+		ProfScope ps(c, "hll_level_files");
+		const int rc = hll_level_view(c, level, tusec, 0u, c->nsvc, c->hl_view, nullptr);
+		if (rc) return rc;
+	}
+	return hll_rollup_src(c, c->hl_view, scope, d_regs, d_est);
 } GYS_CATCH_ALL
 
 uint32_t gys_num_services(gys_ctx *c) { return c ? c->nsvc : 0; }
@@ -4738,6 +4904,25 @@ try {
 	if (!c->svc_hll) return GYS_ERR_STATE;
 	HIPCHK(hipMemcpyAsync(out, c->svc_hll + ((size_t)first_slot << c->cfg.svc_hll_p), (size_t)nslots << c->cfg.svc_hll_p, hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(hipStreamSynchronize(c->stream));
+	return GYS_OK;
+} GYS_CATCH_ALL
+
+int gys_export_svc_hll_level(gys_ctx *c, int level, uint64_t tusec, uint32_t first_slot, uint32_t nslots, uint8_t *out)
+try {
+	GYS_ENTER(c);
+	RANGE_CHECK(first_slot, nslots);
+	HLL_LEVEL_CHECK(level);
+	if (!nslots) return GYS_OK;
+	uint8_t *tmp = nullptr;
+	HIPCHK(hipMalloc((void **)&tmp, (size_t)nslots << c->cfg.svc_hll_p));
+	const int rc = hll_level_view(c, level, tusec, first_slot, nslots, tmp, nullptr);
+	hipError_t e = hipSuccess;
+	if (rc == GYS_OK) e = hipMemcpyAsync(out, tmp, (size_t)nslots << c->cfg.svc_hll_p, hipMemcpyDeviceToHost, c->stream);
+	const hipError_t es = hipStreamSynchronize(c->stream);
+	hipFree(tmp);
+	if (rc) return rc;
+	HIPCHK(e);
+	HIPCHK(es);
 	return GYS_OK;
 } GYS_CATCH_ALL
 

@@ -170,4 +170,90 @@ __global__ __launch_bounds__(GYS_HLL_NT) void k_hll_union(HllUnionP q)
 	}
 }
 
+// ------------------------------------------------------------------------------------------------ levels (gys_config.svc_hll_levels)
+// The registers of CLOSED windows for the four horizons of the histogram levels (5 s / 300 s / 5 days / all; the definition is in
+// include/gysketch.h).  A byte-wise maximum cannot be subtracted, so the 300-s and the 5-day level keep real ring buckets.  State:
+// GYS_HLL_LVL_FILES arrays of [max_services] files, bucket-major (a bucket of all services is one contiguous array):
+//   array 0 = the window closed last, 1 .. 10 = the 300-s ring, 11 .. 20 = the 5-day ring, 21 = every closed window.
+// Two more streaming kernels, 16 bytes per lane, no atomics, no LDS:
+//   k_hll_level_roll  the window close.  Per 16-byte piece of every open file: the two current ring buckets and `all` take the maximum with
+//                     it, `last` becomes it, the open file is cleared.  A piece that is all zero changes none of the three maxima and is
+//                     already clear: only `last` is written for it (1 piece read, 1 written).  Otherwise 4 pieces read + 5 written
+//                     (144 B per service at p = 4).  A current bucket whose ring slot has just expired (fresh) is written without being
+//                     read.  The host clears the OTHER expired buckets with memsets before the launch.
+//   k_hll_level_view  a level's files at query time: the byte-wise maximum of the buckets in `mask` (all their loads requested before the
+//                     first is used; mask 0: all zero), stored as files and / or turned into estimates by the arithmetic of k_hll_estimate
+//                     (hll_acc_word -> hll_group_sum -> hll_finish: the same bits for the same bytes).  Reads popcount(mask) m per service.
+#define GYS_HLL_LVL_LAST 0u
+#define GYS_HLL_LVL_RING 1u                                   // + (level - 1) * GYS_LEVEL_RING + bucket
+#define GYS_HLL_LVL_ALL (1u + 2u * GYS_LEVEL_RING)
+#define GYS_HLL_LVL_FILES (2u + 2u * GYS_LEVEL_RING)
+
+struct HllLevelRollP {
+	uint4 *open;                      // the open window's files, [npieces] pieces of 16 bytes (cleared)
+	uint4 *last, *ring1, *ring2, *all; // the same pieces of `last`, of the two CURRENT ring buckets and of `all`
+	uint64_t npieces;                 // nsvc << (p - 4)
+	uint32_t fresh1, fresh2;          // the current bucket of the 300-s / 5-day ring is in the clear mask: written, not read
+};
+
+__global__ __launch_bounds__(GYS_HLL_NT) void k_hll_level_roll(HllLevelRollP q)
+{
+	const uint64_t stride = (uint64_t)gridDim.x * GYS_HLL_NT;
+	const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+	for (uint64_t i = (uint64_t)blockIdx.x * GYS_HLL_NT + threadIdx.x; i < q.npieces; i += stride) {
+		const uint4 o = q.open[i];
+		const bool any = (o.x | o.y | o.z | o.w) != 0u;
+		uint4 a = zero, b = zero, g = zero;
+		if (any) { // (three loads in flight)
+			if (!q.fresh1) a = q.ring1[i];
+			if (!q.fresh2) b = q.ring2[i];
+			g = q.all[i];
+		}
+		q.last[i] = o;
+		if (any || q.fresh1) q.ring1[i] = hll_max16(a, o);
+		if (any || q.fresh2) q.ring2[i] = hll_max16(b, o);
+		if (any) {
+			q.all[i] = hll_max16(g, o);
+			q.open[i] = zero;
+		}
+	}
+}
+
+struct HllLevelViewP {
+	const uint8_t *base; // bucket j of the level = the array at base + j * stride; the file of slot s sits at + (s << p) inside it
+	uint64_t stride;     // bytes between two buckets (max_services << p)
+	uint32_t mask;       // the live buckets (bit j, j < GYS_LEVEL_RING); levels 0 and 3: the one array, or nothing
+	uint32_t first, n, p; // slots [first, first + n)
+	uint8_t *files;      // [n] files (16-byte aligned), or nullptr
+	double *est;         // [n] estimates, or nullptr
+};
+
+__global__ __launch_bounds__(GYS_HLL_NT) void k_hll_level_view(HllLevelViewP q)
+{
+	const uint32_t lg = q.p - 4u, lane = threadIdx.x & 63u;
+	const uint64_t npieces = (uint64_t)q.n << lg, stride = (uint64_t)gridDim.x * GYS_HLL_NT, stride16 = q.stride / 16u;
+	const uint4 *src = (const uint4 *)q.base + ((uint64_t)q.first << lg);
+	// (the loop of k_hll_estimate: every lane of a wave makes the same number of turns, a file never straddles two waves)
+	for (uint64_t base = (uint64_t)blockIdx.x * GYS_HLL_NT + (threadIdx.x & ~63u); base < npieces; base += stride) {
+		const uint64_t i = base + lane;
+		uint64_t lo = 0, hi = 0;
+		if (i < npieces) {
+			uint4 v[GYS_LEVEL_RING];
+#pragma unroll
+			for (uint32_t j = 0; j < GYS_LEVEL_RING; ++j) v[j] = (q.mask >> j) & 1u ? src[(uint64_t)j * stride16 + i] : make_uint4(0u, 0u, 0u, 0u);
+			uint4 acc = v[0];
+#pragma unroll
+			for (uint32_t j = 1; j < GYS_LEVEL_RING; ++j) acc = hll_max16(acc, v[j]);
+			if (q.files) ((uint4 *)q.files)[i] = acc;
+			hll_acc_word(acc.x, lo, hi);
+			hll_acc_word(acc.y, lo, hi);
+			hll_acc_word(acc.z, lo, hi);
+			hll_acc_word(acc.w, lo, hi);
+		}
+		if (!q.est) continue; // (the same in every lane)
+		hll_group_sum(lo, hi, lg);
+		if (i < npieces && (i & ((1u << lg) - 1u)) == (1u << lg) - 1u) q.est[i >> lg] = hll_finish(lo, hi, q.p);
+	}
+}
+
 } // namespace gys

@@ -36,7 +36,8 @@ def mid_buf(machine_id):
 
 class SketchEngine:
     def __init__(self, max_hosts, max_services, max_clusters=16, enable_tdigest=True, svc_hll_p=0, max_batch_events=1 << 20,
-                 rank=0, nranks=1, device=None, torch_arena=True, resp_path=0, enable_levels=False, td_buf_values=0, conn_pair_cms=False, td_pend_cap=0):
+                 rank=0, nranks=1, device=None, torch_arena=True, resp_path=0, enable_levels=False, td_buf_values=0, conn_pair_cms=False, td_pend_cap=0,
+                 svc_hll_levels=0):
         import torch
         self.L = capi.load()
         if not torch.cuda.is_available():
@@ -52,6 +53,7 @@ class SketchEngine:
         cfg.max_hosts, cfg.max_services, cfg.max_clusters = max_hosts, max_services, max_clusters
         cfg.enable_tdigest = 1 if enable_tdigest else 0
         cfg.svc_hll_p = svc_hll_p
+        cfg.svc_hll_levels = int(svc_hll_levels)  # the registers of the closed windows for the four levels (needs svc_hll_p)
         cfg.resp_path = resp_path
         cfg.enable_levels = int(enable_levels)  # False / True / 2 (without the 5-s level)
         cfg.td_buf_values = td_buf_values
@@ -394,6 +396,39 @@ class SketchEngine:
         capi.check(self.L.gys_hll_global_rccl(self.h, self.comm, C.c_void_p(out.data_ptr()), C.c_void_p(est.data_ptr())))
         self.sync()
         return out[:m].cpu().numpy(), float(est.cpu().numpy()[0])
+
+    # ---------------------------------------------------------------- ... of the CLOSED windows, per level (svc_hll_levels; 0 = window closed last, 1 = 300 s, 2 = 5 days, 3 = all)
+    def scan_distinct_level(self, level, tusec=0):
+        """the level's distinct-flow estimate of EVERY service at time tusec: [nsvc] float64 (gys_scan_distinct_level_dev)"""
+        n = self.num_services()
+        out = self.torch.zeros(max(n, 1), dtype=self.torch.float64, device=self.device)
+        self.order()
+        capi.check(self.L.gys_scan_distinct_level_dev(self.h, level, tusec, C.c_void_p(out.data_ptr())))
+        self.sync()
+        return out[:n].cpu().numpy()
+
+    def query_distinct_level(self, glob_id, level, tusec=0):
+        """one service (gys_query_distinct_level): the same bits as scan_distinct_level(level, tusec)[slot]"""
+        out = C.c_double()
+        capi.check(self.L.gys_query_distinct_level(self.h, int(glob_id), level, tusec, C.byref(out)))
+        return out.value
+
+    def hll_rollup_level(self, scope, level, tusec=0, want_regs=True):
+        """hll_rollup() of a level's files (gys_hll_rollup_level_dev): (files (ngroups, m) uint8 or None, estimates (ngroups,) float64)"""
+        n, m = self._hll_groups(scope), self.L.gys_hll_file_bytes(self.h)
+        regs = self.torch.zeros(max(n * m, 16), dtype=self.torch.uint8, device=self.device) if want_regs else None
+        est = self.torch.zeros(max(n, 1), dtype=self.torch.float64, device=self.device)
+        self.order()
+        capi.check(self.L.gys_hll_rollup_level_dev(self.h, scope, level, tusec, C.c_void_p(regs.data_ptr()) if want_regs else None, C.c_void_p(est.data_ptr())))
+        self.sync()
+        return (regs[:n * m].cpu().numpy().reshape(n, m) if want_regs else None), est[:n].cpu().numpy()
+
+    def export_svc_hll_level(self, level, tusec=0, first=0, n=None):
+        """the level's register files of slots [first, first + n) at time tusec: (n, m) uint8 (gys_export_svc_hll_level)"""
+        n = self.num_services() - first if n is None else n
+        out = np.zeros((n, 1 << self.cfg.svc_hll_p), dtype=np.uint8)
+        capi.check(self.L.gys_export_svc_hll_level(self.h, level, tusec, first, n, C.c_void_p(out.ctypes.data)))
+        return out
 
     def slab_quantiles(self, dev_slab, qs, index=0):
         qa = (C.c_double * len(qs))(*qs)

@@ -101,6 +101,10 @@ typedef struct {
 	                              larger buffer means proportionally fewer merges per window: 3968 at 54 values per service and window = a merge
 	                              every ~70 windows instead of every ~17, for 4 x 3968 bytes more HBM per service.  The digest state is a function
 	                              of the per-call value multisets AND of this number (the CPU oracle takes the same parameter). */
+	uint32_t svc_hll_levels;   /* 1 = keep the per-service HyperLogLog registers of the CLOSED windows for the four levels (window closed last /
+	                              300 s / 5 days / all; "distinct-flow counts of the closed windows" below); needs svc_hll_p.  22 register files per
+	                              service: 352 B at svc_hll_p = 4 (3.5 GB at 10^7 services), 22.5 KB at 10.  0 = off: nothing is allocated and a
+	                              window close enqueues what it always did */
 } gys_config;
 
 /* -------------------------------------------------------------------------------------------------------------------
@@ -398,7 +402,8 @@ uint32_t gys_num_clusters(gys_ctx *ctx);
  *   is <= 2.5 m and a register is zero.  The all-zero file gives exactly 0.  It is a function of the file's bytes alone: the per-service
  *   scan, the one-service query and the roll-ups return bit-identical doubles for identical files.
  * THE OPEN WINDOW: every call reads the per-service registers as gys_export_svc_hll returns them at the same moment -- the window being
- * filled; closing a window clears them (ask before the close, as for gys_scan_listener_state_dev) -- and modifies no engine state.
+ * filled; closing a window clears them (ask before the close, as for gys_scan_listener_state_dev; the closed windows are kept by
+ * gys_config.svc_hll_levels, see below) -- and modifies no engine state.
  * DEVICE pointers to files must be 16-byte aligned (any device allocation is).  Asynchronous on the context stream like the other
  * *_dev calls (gys_sync to wait), except gys_query_distinct and gys_hll_global_rccl, which return when the result is there. */
 /* the estimate of EVERY registered service in one pass: d_out (DEVICE) [gys_num_services] doubles */
@@ -415,6 +420,38 @@ int gys_hll_rollup_dev(gys_ctx *ctx, int scope, uint8_t *d_regs, double *d_est);
 /* the union of the n files d_in (DEVICE, contiguous, not overlapping the outputs) into d_out[0] and / or its estimate into d_est[0]
  * (either may be NULL, not both): the cross-rank step after an all-gather, or any caller-defined group */
 int gys_hll_merge_files_dev(gys_ctx *ctx, const uint8_t *d_in, uint32_t n, uint8_t *d_out, double *d_est);
+
+/* -------------------------------------------------------------------------------------------------------------------
+ * Distinct-flow counts of the CLOSED windows for the four levels of the histograms (gys_config.svc_hll_levels = 1; GYS_ERR_STATE when it is
+ * 0; level 0 .. 3 as for gys_query_hist_level_stats, GYS_ERR_INVAL otherwise).  Builder-defined like the open-window calls above; the ring
+ * arithmetic is that of the histogram levels, so both kinds of level expire at the same second.  Definition, with ring = GYS_LEVEL_RING = 10,
+ * dur[1] = 300 s, dur[2] = 432000 s, idx(t, dur) = (t % dur) * ring / dur the bucket that holds second t, and start(t, dur, j) the most
+ * recent start <= t of bucket j:
+ *   STATE per service, next to the open window's file: `last` (the window closed last), ringfile[l][j] for l = 1, 2 and j = 0 .. 9 (the union
+ *   of the windows whose close time fell into bucket j of level l while that bucket was live), `all` (every closed window); and one close time
+ *   t_last per context (seconds, -1 = no close yet).
+ *   CLOSE at tusec (gys_window_finish, gys_window_close, gys_window_close_rccl; the time is the one given to the prepare step), tnow =
+ *   max(tusec / 10^6, t_last): for each l, every bucket j with t_last >= 0 and start(tnow, dur[l], j) > t_last is cleared, then
+ *   ringfile[l][idx(tnow, dur[l])] = max(itself, open); all = max(all, open); last = open; open = 0; t_last = tnow.  Once per window.
+ *   LEVEL FILE of a service at query time tusec, tq = max(tusec / 10^6, t_last):
+ *     level 0      `last` if t_last >= 0 and tq - t_last < 5, else all zero;
+ *     level 1, 2   the byte-wise maximum of the buckets j for which NOT start(tq, dur[l], j) > t_last
+ *                  (equivalently, with w = dur / 10: the window closed at t_k belongs to the level iff t_k / w > tq / w - 10);
+ *     level 3      `all`.
+ *   Never the open window, and no query modifies state.  A GROUP's level file is the byte-wise maximum of its members' level files; the
+ *   ESTIMATE of a file is the one defined above (the same bits for the same bytes).  Because the maximum is idempotent and commutative, a
+ *   level file equals the file all flow keys of its member windows would leave in one empty file: the ring loses nothing.
+ * A service registered after some closes has all-zero files for the windows before its registration.
+ * No collective of its own: the cross-rank count of a level is gys_hll_rollup_level_dev(GYS_ROLLUP_GLOBAL) -> the caller's all-gather of
+ * one file per rank -> gys_hll_merge_files_dev. */
+/* the level's estimate of EVERY registered service: d_out (DEVICE) [gys_num_services] doubles; asynchronous */
+int gys_scan_distinct_level_dev(gys_ctx *ctx, int level, uint64_t tusec, double *d_out);
+/* one service, result in HOST memory: the same device code on one slot, bit-identical to that slot of gys_scan_distinct_level_dev.
+ * GYS_ERR_INVAL for an unknown glob_id */
+int gys_query_distinct_level(gys_ctx *ctx, uint64_t glob_id, int level, uint64_t tusec, double *out);
+/* host / cluster / rank files and / or estimates of a level: scopes, outputs and NULL rules of gys_hll_rollup_dev.  The level's files of
+ * all services are written once into a scratch array (gys_num_services files, kept by the context), then rolled up by the same launches */
+int gys_hll_rollup_level_dev(gys_ctx *ctx, int scope, int level, uint64_t tusec, uint8_t *d_regs, double *d_est);
 
 /* -------------------------------------------------------------------------------------------------------------------
  * The window exchange inside the library (RCCL over xGMI; no torch, no caller-written collective).  Replaces
@@ -698,6 +735,8 @@ int gys_export_pair_cms(gys_ctx *ctx, int which, void *out /* which 0 / 2 / 4: u
 int gys_export_active_conn_counters(gys_ctx *ctx, uint32_t first_slot, uint32_t nslots, uint64_t *out /* [nslots*4]: rows, bytes_sent, bytes_received, active conns */);
 int gys_export_global_hist(gys_ctx *ctx, gys_hist_rec *out); /* all-service response histogram of the last finished window (all ranks) */
 int gys_export_svc_hll(gys_ctx *ctx, uint32_t first_slot, uint32_t nslots, uint8_t *out /* [nslots << svc_hll_p] */);
+/* the same rows for a level of the closed windows at time tusec (gys_config.svc_hll_levels; "distinct-flow counts of the closed windows") */
+int gys_export_svc_hll_level(gys_ctx *ctx, int level, uint64_t tusec, uint32_t first_slot, uint32_t nslots, uint8_t *out /* [nslots << svc_hll_p] */);
 
 typedef struct {
 	uint64_t resp_events, resp_dropped_range, resp_dropped_nolistener;
