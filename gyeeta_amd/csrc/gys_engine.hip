@@ -314,74 +314,53 @@ struct gys_ctx {
 	std::mutex stage_mu, enq_mu;
 	std::condition_variable stage_cv;
 	std::atomic<uint64_t> stage_waits{0}; // times a host-pointer call found its ring slot still in flight and waited for the GPU
-	// Submission queue of gys_ingest_resp_events ("group commit", SURVEY 8b second option): the calls of all L2 threads are concatenated
-	// into ONE pinned batch -- a segment per call -- and handed to run_resp_batch together, so that the ~12 launches of a response batch
-	// are paid once per submission instead of once per 65536-event call.  A caller reserves its place under rq.mu, copies outside any
-	// lock, and whoever finds no submission in flight submits what has accumulated (a lone caller submits its own call at once: no added
-	// latency; while GYS_RQ_INFLIGHT submissions are still executing on the GPU, further calls accumulate and go out together as soon as
-	// one of them has finished -- the GPU always has the next submission queued behind the running one, and the fixed launches are
-	// amortised exactly when the GPU is the bottleneck).  A host appears at most once per batch (its keys
-	// see their per-call value multisets in call order: the digests stay bit-identical to per-call ingestion); batches are submitted in
-	// the order they were sealed.
-	struct RespBatch {
-		uint8_t *h = nullptr, *d = nullptr;
-		uint64_t cap_events = 0, fill = 0;
-		hipEvent_t done = nullptr;
-		hipEvent_t copied = nullptr; // the batch's H2D copy on the copy stream (the engine stream waits for it before the batch's kernels)
-		std::vector<gys_resp_seg> segs;
-		uint32_t writers = 0;
-		bool sealed = false;
-	};
-	struct RespQ {
-		static constexpr int NB = 6;
+	// Submission queues of the host-pointer calls ("group commit", SURVEY 8b second option): one for gys_ingest_resp_events, one for
+	// gys_ingest_tcp_conn (TCP_CONN_NOTIFY), one for gys_ingest_listener_state (LISTENER_STATE_NOTIFY).  The calls of all L2 threads are
+	// appended to ONE pinned batch and a batch is copied and launched once, so that the fixed cost of a submission is paid per batch
+	// instead of per call: the ~12 launches of a response batch per 65536-event call; for the records, through the 16-slot staging ring,
+	// an H2D copy, two event records, a stream wait and a launch -- five runtime calls of ~5 us each under enq_mu for a 2048-record
+	// (0.57 MB) or 512-record (45 KB) message: 69 M connection records/s and 24 M listener records/s from 16 threads, a third and a
+	// twentieth of what the link carries, with the ring wrapping all the time (gys_counters.stage_waits).
+	// The protocol (subq_* below): a caller reserves its place in the open batch under mu, copies outside any lock (`writers` counts the
+	// copies in progress), and whoever finds no submission being made submits what has accumulated.  A lone caller submits its own call at
+	// once: no added latency.  While GYS_RQ_INFLIGHT submissions are still executing on the GPU, further calls accumulate and go out
+	// together as soon as one of them has finished -- the GPU always has the next submission queued behind the running one, and the fixed
+	// cost is amortised exactly when the GPU is the bottleneck.  Batches are submitted in the order they were sealed.  The tail of a
+	// burst: calls that found GYS_RQ_INFLIGHT submissions on the GPU left their data in the open batch, and after the burst nobody calls
+	// again -- a flusher thread (started with the first queued call) submits that batch once a submission has retired.
+	// Responses: a segment per call, and a host appears at most once per batch (its keys see their per-call value multisets in call
+	// order: the digests stay bit-identical to per-call ingestion).  Records: the records, then an offset (and, for listener states, the
+	// sender's host slot) per record; they keep the order in which the calls reserved their place, so "the last record of a listener
+	// wins" holds across the messages of a batch as it does across calls.
+	struct SubQ {
+		enum Kind { RESP, CONN, LSTATE } kind = RESP; // (also its index in gys_ctx::sq)
+		struct Batch {
+			uint8_t *h = nullptr, *d = nullptr; // RESP: events; else [records: cap][offset per record: u32 x cap_recs][host slot per record: u32 x cap_recs]
+			uint64_t fill = 0;                  // RESP: events; else record bytes (8-byte aligned per call)
+			uint32_t nrec = 0;                  // records (not RESP)
+			std::vector<gys_resp_seg> segs;     // RESP: a segment per call
+			hipEvent_t done = nullptr;          // behind the batch's kernels: its buffers are not reused before
+			hipEvent_t copied = nullptr;        // the batch's H2D copies on the copy stream (the engine stream waits for it before the batch's kernels)
+			uint32_t writers = 0;
+		} b[6];
+		int nb = 0;                     // batches in use: 6 (RESP) / 4
+		uint64_t cap = 0, buf_bytes = 0; // per batch: `fill` it holds, size of h / d
+		uint32_t cap_recs = 0;
 		std::mutex mu;
 		std::condition_variable cv;
-		RespBatch b[NB];
 		std::deque<int> free, sealed, inflight; // sealed: awaiting submission, oldest first; inflight: submitted, GPU not done yet
 		int open = -1;
 		bool submitting = false;
-		int async_rc = 0;             // first error of a submission made on behalf of other callers; surfaces at the next call
+		int async_rc = 0; // first error of a submission made on behalf of other callers; surfaces at the next call
 		std::string async_err;
-		uint64_t calls = 0, submissions = 0;
-		std::vector<uint32_t> host_stamp; // host -> stamp of the open batch it is in
+		uint64_t calls = 0, submissions = 0, tail_flushes = 0;
+		std::vector<uint32_t> host_stamp; // RESP: host -> stamp of the open batch it is in
 		uint32_t stamp = 0;
-		// the tail of a burst: calls that found GYS_RQ_INFLIGHT submissions on the GPU left their events in the open batch, and after the
-		// burst nobody calls again -- a flusher thread (started with the first queued call) submits that batch once a submission has retired
 		std::condition_variable fcv;
 		std::thread flusher;
 		bool flusher_on = false, stop = false;
-		uint64_t tail_flushes = 0;
-	} rq;
-	// Submission queues of the host-pointer TCP_CONN_NOTIFY and LISTENER_STATE_NOTIFY calls (round 4; the same group commit as RespQ).
-	// Through the 16-slot staging ring every partha message cost its own H2D copy, two event records, a stream wait and a launch -- five
-	// runtime calls of ~5 us each under enq_mu for a 2048-record (0.57 MB) or 512-record (45 KB) message: 69 M connection records/s and
-	// 24 M listener records/s from 16 threads, a third and a twentieth of what the link carries, with the ring wrapping all the time
-	// (gys_counters.stage_waits).  Now the messages of all threads are appended to ONE pinned batch -- records, then an offset (and, for
-	// listener states, the sender's host slot) per record -- and a batch is copied and launched once.  A lone caller's message still goes
-	// out at once; messages accumulate only while GYS_RQ_INFLIGHT submissions are on the GPU.  Records keep the order in which the calls
-	// reserved their place, so "the last record of a listener wins" holds across the messages of a batch as it does across calls.
-	struct RecBatch {
-		uint8_t *h = nullptr, *d = nullptr; // [records: cap_bytes][offset per record: u32 x cap_recs][host slot per record: u32 x cap_recs]
-		uint64_t cap_bytes = 0, fill = 0;
-		uint32_t cap_recs = 0, nrec = 0;
-		hipEvent_t done = nullptr, copied = nullptr;
-		uint32_t writers = 0;
-	};
-	struct RecQ {
-		static constexpr int NB = 4;
-		bool conn = false; // TCP_CONN_NOTIFY (else LISTENER_STATE_NOTIFY)
-		std::mutex mu;
-		std::condition_variable cv, fcv;
-		RecBatch b[NB];
-		std::deque<int> free, sealed, inflight;
-		int open = -1;
-		bool submitting = false;
-		int async_rc = 0;
-		std::string async_err;
-		uint64_t calls = 0, submissions = 0, tail_flushes = 0;
-		std::thread flusher;
-		bool flusher_on = false, stop = false;
-	} cq[2]; // [0] connections, [1] listener states
+		const char *word() const { return kind == RESP ? "response" : "record"; } // (error texts)
+	} sq[3];
 	uint8_t *dev_staging = nullptr;
 	uint64_t dev_staging_bytes = 0;
 	uint32_t *dev_offsets = nullptr;
@@ -1899,41 +1878,62 @@ int ingest_staged_records(gys_ctx *c, uint32_t host, const void *batch, uint64_t
 }
 
 
-// ---- submission queue of the host-pointer response path (gys_ctx::RespQ)
+// ---- submission queues of the host-pointer response / connection / listener-state calls (gys_ctx::SubQ: the protocol is described there)
+using SubQ = gys_ctx::SubQ;
 constexpr uint64_t GYS_RQ_EVENTS = 1u << 21; // events per combined batch (48 MiB pinned + 48 MiB device each)
+constexpr uint64_t GYS_CQ_CONN_BYTES = 16u << 20, GYS_CQ_LSTATE_BYTES = 4u << 20; // record bytes per combined batch
+constexpr size_t GYS_RQ_INFLIGHT = 2; // submissions executing / queued on the GPU before new calls start to accumulate
 
-// submits batch bi (sealed, no writers); rq.mu NOT held
-int rq_submit_one(gys_ctx *c, int bi)
+void subq_init(gys_ctx *c, SubQ::Kind kind)
 {
-	gys_ctx::RespBatch &b = c->rq.b[bi];
+	SubQ &q = c->sq[kind];
+	q.kind = kind;
+	if (kind == SubQ::RESP) {
+		q.nb = 6;
+		q.cap = std::min<uint64_t>(GYS_RQ_EVENTS, std::max<uint64_t>(c->cfg.max_batch_events, 1));
+		q.buf_bytes = q.cap * 24;
+	} else {
+		q.nb = 4;
+		q.cap = kind == SubQ::CONN ? GYS_CQ_CONN_BYTES : GYS_CQ_LSTATE_BYTES;
+		q.cap_recs = (uint32_t)(q.cap / (kind == SubQ::CONN ? 280u : 88u));
+		q.buf_bytes = q.cap + (uint64_t)q.cap_recs * 8;
+	}
+	for (int i = 0; i < q.nb; ++i) q.free.push_back(i);
+}
+
+// submits batch b of q (sealed, no writers); q.mu NOT held
+int subq_submit_one(gys_ctx *c, SubQ &q, SubQ::Batch &b)
+{
+	const bool resp = q.kind == SubQ::RESP;
 	int rc = GYS_OK;
-	{
-		std::lock_guard<std::mutex> g(c->enq_mu);
-		// copy on its own stream, kernels on the engine stream behind an event: with everything on one stream the 48-MiB copy of a
-		// submission (0.85 ms at 57 GB/s) and its kernels alternate; the batch's buffers are not reused before `done` has fired
-		hipError_t e = hipMemcpyAsync(b.d, b.h, b.fill * 24, hipMemcpyHostToDevice, c->copy_stream ? c->copy_stream : c->stream);
-		if (e == hipSuccess && c->copy_stream) {
-			e = hipEventRecord(b.copied, c->copy_stream);
-			if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, b.copied, 0);
-		}
-		if (e == hipSuccess) {
-			rc = run_resp_batch(c, b.segs.data(), (uint32_t)b.segs.size(), b.d, b.fill);
-			e = hipEventRecord(b.done, c->stream);
-		}
-		if (e != hipSuccess) {
-			set_err("response submission: %s", hipGetErrorString(e));
-			rc = GYS_ERR_HIP;
-		}
+	std::lock_guard<std::mutex> g(c->enq_mu);
+	// copy on its own stream, kernels on the engine stream behind an event: with everything on one stream the 48-MiB copy of a response
+	// submission (0.85 ms at 57 GB/s) and its kernels alternate; the batch's buffers are not reused before `done` has fired
+	hipStream_t cs = c->copy_stream ? c->copy_stream : c->stream;
+	const uint64_t off_at = q.cap, host_at = q.cap + (uint64_t)q.cap_recs * 4;
+	hipError_t e = hipMemcpyAsync(b.d, b.h, resp ? b.fill * 24 : b.fill, hipMemcpyHostToDevice, cs);
+	if (e == hipSuccess && !resp) e = hipMemcpyAsync(b.d + off_at, b.h + off_at, (uint64_t)b.nrec * 4, hipMemcpyHostToDevice, cs);
+	if (e == hipSuccess && q.kind == SubQ::LSTATE) e = hipMemcpyAsync(b.d + host_at, b.h + host_at, (uint64_t)b.nrec * 4, hipMemcpyHostToDevice, cs);
+	if (e == hipSuccess && c->copy_stream) {
+		e = hipEventRecord(b.copied, c->copy_stream);
+		if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, b.copied, 0);
+	}
+	if (e == hipSuccess) {
+		if (resp) rc = run_resp_batch(c, b.segs.data(), (uint32_t)b.segs.size(), b.d, b.fill);
+		else if (q.kind == SubQ::CONN) rc = run_conn(c, b.d, (const uint32_t *)(b.d + off_at), b.nrec);
+		else rc = run_lstate(c, b.d, (const uint32_t *)(b.d + off_at), (const uint32_t *)(b.d + host_at), 0, b.nrec);
+		e = hipEventRecord(b.done, c->stream);
+	}
+	if (e != hipSuccess) {
+		set_err("%s submission: %s", q.word(), hipGetErrorString(e));
+		rc = GYS_ERR_HIP;
 	}
 	return rc;
 }
 
-constexpr size_t GYS_RQ_INFLIGHT = 2; // submissions executing / queued on the GPU before new calls start to accumulate
-
-// rq.mu held: batches whose kernels have finished go back to the free list
-void rq_reap(gys_ctx *c)
+// q.mu held: batches whose kernels have finished go back to the free list
+void subq_reap(SubQ &q)
 {
-	gys_ctx::RespQ &q = c->rq;
 	// anything but "not ready" ends a submission's stay on the in-flight list: an event in an error state never turns into hipSuccess, and
 	// a head that is never reaped would leave every later caller waiting once the free list has drained
 	while (!q.inflight.empty()) {
@@ -1941,7 +1941,7 @@ void rq_reap(gys_ctx *c)
 		if (e == hipErrorNotReady) break;
 		if (e != hipSuccess && !q.async_rc) {
 			q.async_rc = GYS_ERR_HIP;
-			q.async_err = std::string("response submission: ") + hipGetErrorString(e);
+			q.async_err = std::string(q.word()) + " submission: " + hipGetErrorString(e);
 		}
 		q.free.push_back(q.inflight.front());
 		q.inflight.pop_front();
@@ -1949,12 +1949,11 @@ void rq_reap(gys_ctx *c)
 	(void)hipGetLastError(); // (hipErrorNotReady is not an error)
 }
 
-// With rq.mu held (lk): submit, oldest first, every sealed batch whose writers are done -- and the open batch too when `all`, or when it
+// With q.mu held (lk): submit, oldest first, every sealed batch whose writers are done -- and the open batch too when `all`, or when it
 // has data, no writer, and fewer than GYS_RQ_INFLIGHT submissions are still on the GPU.  Returns the first error of a batch that
-// carried the caller's own data (`mine`), other errors are parked in rq.async_rc.
-int rq_drain(gys_ctx *c, std::unique_lock<std::mutex> &lk, int mine, bool all)
+// carried the caller's own data (`mine`), other errors are parked in q.async_rc.
+int subq_drain(gys_ctx *c, SubQ &q, std::unique_lock<std::mutex> &lk, int mine, bool all)
 {
-	gys_ctx::RespQ &q = c->rq;
 	int my_rc = GYS_OK;
 	if (q.submitting) {
 		if (!all) return GYS_OK; // the thread inside the submission picks up what accumulates
@@ -1962,29 +1961,29 @@ int rq_drain(gys_ctx *c, std::unique_lock<std::mutex> &lk, int mine, bool all)
 	}
 	for (;;) {
 		if (q.sealed.empty() && q.open >= 0 && q.b[q.open].fill && q.b[q.open].writers == 0) {
-			rq_reap(c);
+			subq_reap(q);
 			if (all || q.inflight.size() < GYS_RQ_INFLIGHT) {
-				q.b[q.open].sealed = true;
 				q.sealed.push_back(q.open);
 				q.open = -1;
 			}
 		}
 		if (q.sealed.empty()) break;
 		const int bi = q.sealed.front();
-		if (q.b[bi].writers) {
+		SubQ::Batch &b = q.b[bi];
+		if (b.writers) {
 			if (!all) break; // its last writer drains
-			q.cv.wait(lk, [&] { return q.b[bi].writers == 0; });
+			q.cv.wait(lk, [&] { return b.writers == 0; });
 		}
 		q.sealed.pop_front();
 		q.submitting = true;
 		lk.unlock();
-		const int rc = rq_submit_one(c, bi);
+		const int rc = subq_submit_one(c, q, b);
 		lk.lock();
 		q.submitting = false;
 		q.submissions++;
-		q.b[bi].sealed = false;
-		q.b[bi].fill = 0;
-		q.b[bi].segs.clear();
+		b.fill = 0;
+		b.nrec = 0;
+		b.segs.clear();
 		q.inflight.push_back(bi);
 		q.cv.notify_all();
 		if (rc) {
@@ -1998,26 +1997,30 @@ int rq_drain(gys_ctx *c, std::unique_lock<std::mutex> &lk, int mine, bool all)
 	return my_rc;
 }
 
-// everything the queue holds is on the stream when this returns (entry points other than the concurrent ingest calls start with it)
-int rq_flush(gys_ctx *c)
+// q.mu held: the error of a submission made for other callers (or by the flusher) is reported once, by the first call that comes by
+int subq_parked_error(SubQ &q)
 {
-	gys_ctx::RespQ &q = c->rq;
-	std::unique_lock<std::mutex> lk(q.mu);
-	int rc = GYS_OK;
-	if (q.open >= 0 || !q.sealed.empty() || q.submitting) rc = rq_drain(c, lk, -1, true);
-	if (!rc && q.async_rc) {
-		rc = q.async_rc;
+	const int rc = q.async_rc;
+	if (rc) {
 		set_err("%s", q.async_err.c_str());
 		q.async_rc = 0;
 	}
 	return rc;
 }
 
-// flusher thread of the submission queue: sleeps until a call leaves events behind in the open batch, then tries every 200 us to submit
-// it (rq_drain submits only while fewer than GYS_RQ_INFLIGHT submissions are on the GPU); an error lands in rq.async_rc for the next caller
-void rq_flusher(gys_ctx *c)
+// everything the queue holds is on the stream when this returns (entry points other than the concurrent ingest calls start with it)
+int subq_flush(gys_ctx *c, SubQ &q)
 {
-	gys_ctx::RespQ &q = c->rq;
+	std::unique_lock<std::mutex> lk(q.mu);
+	if (q.open >= 0 || !q.sealed.empty() || q.submitting) (void)subq_drain(c, q, lk, -1, true); // (no batch of this caller's: errors are parked)
+	return subq_parked_error(q);
+}
+
+// flusher thread of a submission queue: sleeps until a call leaves data behind in the open batch, then tries every 200 us to submit
+// it (subq_drain submits only while fewer than GYS_RQ_INFLIGHT submissions are on the GPU); an error lands in q.async_rc for the next caller
+void subq_flusher(gys_ctx *c, SubQ *qp)
+{
+	SubQ &q = *qp;
 	(void)hipSetDevice(c->device);
 	std::unique_lock<std::mutex> lk(q.mu);
 	for (;;) {
@@ -2033,28 +2036,31 @@ void rq_flusher(gys_ctx *c)
 		if (q.stop) break;
 		if (q.open >= 0 && q.b[q.open].fill && q.b[q.open].writers == 0 && !q.submitting) {
 			const uint64_t before = q.submissions;
-			(void)rq_drain(c, lk, -1, false);
+			(void)subq_drain(c, q, lk, -1, false);
 			if (q.submissions != before) q.tail_flushes++;
 		}
 	}
 }
 
-int rq_ingest(gys_ctx *c, uint32_t host, const void *ev24, uint32_t n)
+// one call of the sender in slot `host`.  Responses: n events of 24 bytes at `data` (offs unused).  Records: one message, `bytes` of
+// records at `data`, offs[i] = offset of record i of n in it.
+int subq_ingest(gys_ctx *c, SubQ &q, uint32_t host, const void *data, uint64_t bytes, uint32_t n, const uint32_t *offs)
 {
-	gys_ctx::RespQ &q = c->rq;
+	const bool resp = q.kind == SubQ::RESP;
+	const uint64_t need = resp ? n : align_up(bytes, 8); // of a batch's `fill`
 	std::unique_lock<std::mutex> lk(q.mu);
 	if (!q.flusher_on) {
 		q.flusher_on = true;
-		q.flusher = std::thread(rq_flusher, c);
+		q.flusher = std::thread(subq_flusher, c, &q);
 	}
 	// (an earlier submission made for other callers may have failed: that error is reported once, by the first call that comes by -- AFTER
-	// the caller's own events have been queued below, never instead of them)
+	// the caller's own data has been queued below, never instead of it)
 	q.calls++;
-	if (q.host_stamp.size() < c->hosts.size()) q.host_stamp.resize(c->hosts.size(), 0);
+	if (resp && q.host_stamp.size() < c->hosts.size()) q.host_stamp.resize(c->hosts.size(), 0);
 	int bi;
 	for (;;) {
 		if (q.open < 0) {
-			rq_reap(c);
+			subq_reap(q);
 			if (q.free.empty()) {
 				if (!q.inflight.empty()) { // every batch is on the GPU: wait for the oldest (outside the lock), then look again
 					hipEvent_t ev = q.b[q.inflight.front()].done;
@@ -2068,13 +2074,12 @@ int rq_ingest(gys_ctx *c, uint32_t host, const void *ev24, uint32_t n)
 			}
 			bi = q.free.front();
 			q.free.pop_front();
-			gys_ctx::RespBatch &nb = q.b[bi];
+			SubQ::Batch &nb = q.b[bi];
 			lk.unlock(); // (first-use allocation: outside the lock; the batch is not visible yet)
 			hipError_t e = hipSuccess;
 			if (!nb.h || !nb.d || !nb.done || !nb.copied) {
-				nb.cap_events = std::min<uint64_t>(GYS_RQ_EVENTS, std::max<uint64_t>(c->cfg.max_batch_events, 1));
-				if (!nb.h) e = hipHostMalloc((void **)&nb.h, nb.cap_events * 24, hipHostMallocDefault);
-				if (e == hipSuccess && !nb.d) e = hipMalloc((void **)&nb.d, nb.cap_events * 24);
+				if (!nb.h) e = hipHostMalloc((void **)&nb.h, q.buf_bytes, hipHostMallocDefault);
+				if (e == hipSuccess && !nb.d) e = hipMalloc((void **)&nb.d, q.buf_bytes);
 				if (e == hipSuccess && !nb.done) e = hipEventCreateWithFlags(&nb.done, hipEventDisableTiming);
 				if (e == hipSuccess && !nb.copied) e = hipEventCreateWithFlags(&nb.copied, hipEventDisableTiming);
 				if (e != hipSuccess) { // all four or none: a half-built batch must not look usable to the next caller
@@ -2082,8 +2087,7 @@ int rq_ingest(gys_ctx *c, uint32_t host, const void *ev24, uint32_t n)
 					if (nb.d) (void)hipFree(nb.d);
 					if (nb.done) (void)hipEventDestroy(nb.done);
 					if (nb.copied) (void)hipEventDestroy(nb.copied);
-					nb.h = nullptr;
-					nb.d = nullptr;
+					nb.h = nb.d = nullptr;
 					nb.done = nb.copied = nullptr;
 				}
 			}
@@ -2091,7 +2095,7 @@ int rq_ingest(gys_ctx *c, uint32_t host, const void *ev24, uint32_t n)
 			if (e != hipSuccess) {
 				q.free.push_back(bi);
 				q.cv.notify_all();
-				set_err("response batch buffers: %s", hipGetErrorString(e));
+				set_err("%s batch buffers: %s", q.word(), hipGetErrorString(e));
 				return GYS_ERR_HIP;
 			}
 			if (q.open >= 0) { // another caller opened one meanwhile
@@ -2103,260 +2107,79 @@ int rq_ingest(gys_ctx *c, uint32_t host, const void *ev24, uint32_t n)
 			++q.stamp;
 		}
 		bi = q.open;
-		gys_ctx::RespBatch &b = q.b[bi];
-		if (b.fill + n <= b.cap_events && q.host_stamp[host] != q.stamp) break;
+		const SubQ::Batch &ob = q.b[bi];
+		if (ob.fill + need <= q.cap && (resp ? q.host_stamp[host] != q.stamp : ob.nrec + n <= q.cap_recs)) break;
 		// no room, or the host already has a segment in this batch: seal it (submitted before anything opened later)
-		b.sealed = true;
 		q.sealed.push_back(bi);
 		q.open = -1;
-		const int rc = rq_drain(c, lk, -1, false);
-		if (rc) return rc;
+		(void)subq_drain(c, q, lk, -1, false); // (no batch of this caller's yet: errors are parked, the result is always GYS_OK)
 	}
-	gys_ctx::RespBatch &b = q.b[bi];
-	const uint64_t off = b.fill;
-	b.fill += n;
-	b.segs.push_back(gys_resp_seg{host, 0, off});
-	b.writers++;
-	q.host_stamp[host] = q.stamp;
-	lk.unlock();
-	memcpy(b.h + off * 24, ev24, (uint64_t)n * 24); // the caller's buffer is free from here on
-	lk.lock();
-	b.writers--;
-	if (b.writers == 0) q.cv.notify_all();
-	int rc = rq_drain(c, lk, bi, false);
-	if (q.open >= 0 && q.b[q.open].fill) q.fcv.notify_one(); // events stay behind in the open batch: the flusher sees to them if no call follows
-	if (!rc && q.async_rc) { // an earlier submission made for other callers (or by the flusher) failed: reported once, this call's events are queued all the same
-		rc = q.async_rc;
-		set_err("%s", q.async_err.c_str());
-		q.async_rc = 0;
-	}
-	return rc;
-}
-
-// ---- submission queues of the host-pointer connection / listener-state calls (gys_ctx::RecQ; the logic of rq_* above)
-constexpr uint64_t GYS_CQ_CONN_BYTES = 16u << 20, GYS_CQ_LSTATE_BYTES = 4u << 20; // record bytes per combined batch
-
-int recq_submit_one(gys_ctx *c, gys_ctx::RecQ &q, int bi)
-{
-	gys_ctx::RecBatch &b = q.b[bi];
-	int rc = GYS_OK;
-	std::lock_guard<std::mutex> g(c->enq_mu);
-	hipStream_t cs = c->copy_stream ? c->copy_stream : c->stream;
-	const uint64_t off_at = b.cap_bytes, host_at = b.cap_bytes + (uint64_t)b.cap_recs * 4;
-	hipError_t e = hipMemcpyAsync(b.d, b.h, b.fill, hipMemcpyHostToDevice, cs);
-	if (e == hipSuccess) e = hipMemcpyAsync(b.d + off_at, b.h + off_at, (uint64_t)b.nrec * 4, hipMemcpyHostToDevice, cs);
-	if (e == hipSuccess && !q.conn) e = hipMemcpyAsync(b.d + host_at, b.h + host_at, (uint64_t)b.nrec * 4, hipMemcpyHostToDevice, cs);
-	if (e == hipSuccess && c->copy_stream) {
-		e = hipEventRecord(b.copied, c->copy_stream);
-		if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, b.copied, 0);
-	}
-	if (e == hipSuccess) {
-		rc = q.conn ? run_conn(c, b.d, (const uint32_t *)(b.d + off_at), b.nrec)
-			    : run_lstate(c, b.d, (const uint32_t *)(b.d + off_at), (const uint32_t *)(b.d + host_at), 0, b.nrec);
-		e = hipEventRecord(b.done, c->stream);
-	}
-	if (e != hipSuccess) {
-		set_err("record submission: %s", hipGetErrorString(e));
-		rc = GYS_ERR_HIP;
-	}
-	return rc;
-}
-
-void recq_reap(gys_ctx::RecQ &q) // q.mu held
-{
-	while (!q.inflight.empty()) {
-		const hipError_t e = hipEventQuery(q.b[q.inflight.front()].done);
-		if (e == hipErrorNotReady) break;
-		if (e != hipSuccess && !q.async_rc) {
-			q.async_rc = GYS_ERR_HIP;
-			q.async_err = std::string("record submission: ") + hipGetErrorString(e);
-		}
-		q.free.push_back(q.inflight.front());
-		q.inflight.pop_front();
-	}
-	(void)hipGetLastError();
-}
-
-// q.mu held (lk): as rq_drain
-int recq_drain(gys_ctx *c, gys_ctx::RecQ &q, std::unique_lock<std::mutex> &lk, int mine, bool all)
-{
-	int my_rc = GYS_OK;
-	if (q.submitting) {
-		if (!all) return GYS_OK;
-		q.cv.wait(lk, [&] { return !q.submitting; });
-	}
-	for (;;) {
-		if (q.sealed.empty() && q.open >= 0 && q.b[q.open].nrec && q.b[q.open].writers == 0) {
-			recq_reap(q);
-			if (all || q.inflight.size() < GYS_RQ_INFLIGHT) {
-				q.sealed.push_back(q.open);
-				q.open = -1;
-			}
-		}
-		if (q.sealed.empty()) break;
-		const int bi = q.sealed.front();
-		if (q.b[bi].writers) {
-			if (!all) break; // its last writer drains
-			q.cv.wait(lk, [&] { return q.b[bi].writers == 0; });
-		}
-		q.sealed.pop_front();
-		q.submitting = true;
-		lk.unlock();
-		const int rc = recq_submit_one(c, q, bi);
-		lk.lock();
-		q.submitting = false;
-		q.submissions++;
-		q.b[bi].fill = 0;
-		q.b[bi].nrec = 0;
-		q.inflight.push_back(bi);
-		q.cv.notify_all();
-		if (rc) {
-			if (bi == mine) my_rc = rc;
-			else if (!q.async_rc) {
-				q.async_rc = rc;
-				q.async_err = g_err;
-			}
-		}
-	}
-	return my_rc;
-}
-
-int recq_flush(gys_ctx *c, gys_ctx::RecQ &q)
-{
-	std::unique_lock<std::mutex> lk(q.mu);
-	int rc = GYS_OK;
-	if (q.open >= 0 || !q.sealed.empty() || q.submitting) rc = recq_drain(c, q, lk, -1, true);
-	if (!rc && q.async_rc) {
-		rc = q.async_rc;
-		set_err("%s", q.async_err.c_str());
-		q.async_rc = 0;
-	}
-	return rc;
-}
-
-void recq_flusher(gys_ctx *c, gys_ctx::RecQ *qp) // the tail of a burst: as rq_flusher
-{
-	gys_ctx::RecQ &q = *qp;
-	(void)hipSetDevice(c->device);
-	std::unique_lock<std::mutex> lk(q.mu);
-	for (;;) {
-		q.fcv.wait(lk, [&] { return q.stop || (q.open >= 0 && q.b[q.open].nrec != 0); });
-		if (q.stop) break;
-		hipEvent_t busy = q.inflight.size() >= GYS_RQ_INFLIGHT ? q.b[q.inflight.front()].done : nullptr; // (as rq_flusher)
-		lk.unlock();
-		if (busy) (void)hipEventSynchronize(busy);
-		else std::this_thread::sleep_for(std::chrono::microseconds(200));
-		lk.lock();
-		if (q.stop) break;
-		if (q.open >= 0 && q.b[q.open].nrec && q.b[q.open].writers == 0 && !q.submitting) {
-			const uint64_t before = q.submissions;
-			(void)recq_drain(c, q, lk, -1, false);
-			if (q.submissions != before) q.tail_flushes++;
-		}
-	}
-}
-
-// one message: `bytes` of records at `batch`, offs[i] = offset of record i in it; host = the sender's slot
-int recq_ingest(gys_ctx *c, gys_ctx::RecQ &q, uint32_t host, const void *batch, uint64_t bytes, const std::vector<uint32_t> &offs)
-{
-	const uint64_t cap_bytes = q.conn ? GYS_CQ_CONN_BYTES : GYS_CQ_LSTATE_BYTES, need = align_up(bytes, 8);
-	const uint32_t cap_recs = (uint32_t)(cap_bytes / (q.conn ? 280u : 88u)), n = (uint32_t)offs.size();
-	if (need > cap_bytes / 2 || n > cap_recs / 2) {
-		// a call of many messages' size (a replayed backlog): on its own through the staging ring -- behind what the queue holds
-		const int rc = recq_flush(c, q);
-		return rc ? rc : ingest_staged_records(c, host, batch, bytes, offs, q.conn);
-	}
-	std::unique_lock<std::mutex> lk(q.mu);
-	if (!q.flusher_on) {
-		q.flusher_on = true;
-		q.flusher = std::thread(recq_flusher, c, &q);
-	}
-	// (a parked error of an earlier submission is reported after this message has been queued, see rq_ingest)
-	q.calls++;
-	int bi;
-	for (;;) {
-		if (q.open < 0) {
-			recq_reap(q);
-			if (q.free.empty()) {
-				if (!q.inflight.empty()) {
-					hipEvent_t ev = q.b[q.inflight.front()].done;
-					lk.unlock();
-					(void)hipEventSynchronize(ev);
-					lk.lock();
-				} else {
-					q.cv.wait(lk, [&] { return !q.free.empty() || !q.inflight.empty(); });
-				}
-				continue;
-			}
-			bi = q.free.front();
-			q.free.pop_front();
-			gys_ctx::RecBatch &nb = q.b[bi];
-			lk.unlock(); // (first-use allocation outside the lock; the batch is not visible yet)
-			hipError_t e = hipSuccess;
-			if (!nb.h || !nb.d || !nb.done || !nb.copied) {
-				const uint64_t total = cap_bytes + (uint64_t)cap_recs * 8;
-				if (!nb.h) e = hipHostMalloc((void **)&nb.h, total, hipHostMallocDefault);
-				if (e == hipSuccess && !nb.d) e = hipMalloc((void **)&nb.d, total);
-				if (e == hipSuccess && !nb.done) e = hipEventCreateWithFlags(&nb.done, hipEventDisableTiming);
-				if (e == hipSuccess && !nb.copied) e = hipEventCreateWithFlags(&nb.copied, hipEventDisableTiming);
-				if (e != hipSuccess) { // all four or none
-					if (nb.h) (void)hipHostFree(nb.h);
-					if (nb.d) (void)hipFree(nb.d);
-					if (nb.done) (void)hipEventDestroy(nb.done);
-					if (nb.copied) (void)hipEventDestroy(nb.copied);
-					nb.h = nb.d = nullptr;
-					nb.done = nb.copied = nullptr;
-				} else {
-					nb.cap_bytes = cap_bytes;
-					nb.cap_recs = cap_recs;
-				}
-			}
-			lk.lock();
-			if (e != hipSuccess) {
-				q.free.push_back(bi);
-				q.cv.notify_all();
-				set_err("record batch buffers: %s", hipGetErrorString(e));
-				return GYS_ERR_HIP;
-			}
-			if (q.open >= 0) { // another caller opened one meanwhile
-				q.free.push_front(bi);
-				q.cv.notify_all();
-				continue;
-			}
-			q.open = bi;
-		}
-		bi = q.open;
-		gys_ctx::RecBatch &b = q.b[bi];
-		if (b.fill + need <= b.cap_bytes && b.nrec + n <= b.cap_recs) break;
-		q.sealed.push_back(bi); // no room: submitted before anything opened later
-		q.open = -1;
-		const int rc = recq_drain(c, q, lk, -1, false);
-		if (rc) return rc;
-	}
-	gys_ctx::RecBatch &b = q.b[bi];
+	SubQ::Batch &b = q.b[bi];
 	const uint64_t at = b.fill;
 	const uint32_t r0 = b.nrec;
 	b.fill += need;
-	b.nrec += n;
+	if (resp) {
+		b.segs.push_back(gys_resp_seg{host, 0, at});
+		q.host_stamp[host] = q.stamp;
+	} else {
+		b.nrec += n;
+	}
 	b.writers++;
 	lk.unlock();
-	memcpy(b.h + at, batch, bytes); // the caller's buffer is free from here on
-	uint32_t *o = (uint32_t *)(b.h + b.cap_bytes) + r0;
-	for (uint32_t i = 0; i < n; ++i) o[i] = offs[i] + (uint32_t)at;
-	if (!q.conn) {
-		uint32_t *hs = (uint32_t *)(b.h + b.cap_bytes) + b.cap_recs + r0;
-		for (uint32_t i = 0; i < n; ++i) hs[i] = host;
-	}
+	if (resp) {
+		memcpy(b.h + at * 24, data, (uint64_t)n * 24);
+	} else {
+		memcpy(b.h + at, data, bytes);
+		uint32_t *o = (uint32_t *)(b.h + q.cap) + r0;
+		for (uint32_t i = 0; i < n; ++i) o[i] = offs[i] + (uint32_t)at;
+		if (q.kind == SubQ::LSTATE) std::fill_n(o + q.cap_recs, n, host);
+	} // the caller's buffer is free from here on
 	lk.lock();
 	b.writers--;
 	if (b.writers == 0) q.cv.notify_all();
-	int rc = recq_drain(c, q, lk, bi, false);
-	if (q.open >= 0 && q.b[q.open].nrec) q.fcv.notify_one();
-	if (!rc && q.async_rc) { // (as rq_ingest: another submission's error, reported once; this message is queued)
-		rc = q.async_rc;
-		set_err("%s", q.async_err.c_str());
-		q.async_rc = 0;
+	int rc = subq_drain(c, q, lk, bi, false);
+	if (q.open >= 0 && q.b[q.open].fill) q.fcv.notify_one(); // data stays behind in the open batch: the flusher sees to it if no call follows
+	if (!rc) rc = subq_parked_error(q);
+	return rc;
+}
+
+// a record message: combined with the other callers' pending messages, unless it has many messages' size (a replayed backlog) -- then on
+// its own through the staging ring, behind what the queue holds
+int ingest_records(gys_ctx *c, SubQ &q, uint32_t host, const void *batch, const void *pend, const std::vector<uint32_t> &offs)
+{
+	const uint64_t bytes = (uint64_t)((const uint8_t *)pend - (const uint8_t *)batch);
+	const uint32_t n = (uint32_t)offs.size();
+	if (align_up(bytes, 8) <= q.cap / 2 && n <= q.cap_recs / 2) return subq_ingest(c, q, host, batch, bytes, n, offs.data());
+	const int rc = subq_flush(c, q);
+	return rc ? rc : ingest_staged_records(c, host, batch, bytes, offs, q.kind == SubQ::CONN);
+}
+
+// a response call as its own submission through the staging ring, behind whatever the response queue holds (same-host calls keep their
+// order: a service's per-call value multisets keep the order of the calls); `fn`: the entry point, for the error text
+int ingest_staged_resp(gys_ctx *c, uint32_t host, const void *ev, uint32_t nevents, uint32_t evsize, bool v6, const char *fn)
+{
+	int rc = subq_flush(c, c->sq[SubQ::RESP]);
+	if (rc) return rc;
+	const uint64_t bytes = (uint64_t)nevents * evsize;
+	int si;
+	rc = stage_acquire(c, bytes, &si);
+	if (rc) return rc;
+	gys_ctx::Stage &st = c->stage[si];
+	memcpy(st.h, ev, bytes); // the caller's buffer is free from here on
+	{
+		std::lock_guard<std::mutex> g(c->enq_mu);
+		hipError_t e = hipMemcpyAsync(st.d, st.h, bytes, hipMemcpyHostToDevice, c->stream);
+		if (e == hipSuccess) {
+			gys_resp_seg seg{host, 0, 0};
+			rc = run_resp_batch(c, &seg, 1, st.d, nevents, v6);
+			e = hipEventRecord(st.done, c->stream);
+		}
+		if (e != hipSuccess) {
+			set_err("%s: %s", fn, hipGetErrorString(e));
+			rc = GYS_ERR_HIP;
+		}
 	}
+	stage_release(c, si);
 	return rc;
 }
 
@@ -2372,17 +2195,16 @@ int recq_ingest(gys_ctx *c, gys_ctx::RecQ &q, uint32_t host, const void *batch, 
 			return GYS_ERR_HIP;                                    \
 		}                                                              \
 	} while (0)
-// ... and, except for the host-pointer ingest calls that may run concurrently, puts whatever the response submission queue still holds
-// on the stream first (stream order = call order for everything that reads or closes state)
+// ... and, except for the host-pointer ingest calls that may run concurrently, puts whatever the submission queues still hold on the
+// stream first (stream order = call order for everything that reads or closes state)
 #define GYS_ENTER(c)                                                           \
 	do {                                                                   \
 		GYS_ENTER_NOFLUSH(c);                                          \
-		if (c) {                                                       \
-			int rcq_ = rq_flush(c);                                \
-			if (!rcq_) rcq_ = recq_flush(c, (c)->cq[0]);           \
-			if (!rcq_) rcq_ = recq_flush(c, (c)->cq[1]);           \
-			if (rcq_) return rcq_;                                 \
-		}                                                              \
+		if (c)                                                         \
+			for (auto &q_ : (c)->sq) {                             \
+				const int rcq_ = subq_flush(c, q_);            \
+				if (rcq_) return rcq_;                         \
+			}                                                      \
 	} while (0)
 
 // "Nothing throws across the boundary" (include/gysketch.h): the host side uses std::vector / std::string / std::thread, whose failures
@@ -2436,11 +2258,8 @@ try {
 	}
 	gys_ctx *c = new gys_ctx();
 	for (int i = 0; i < gys_ctx::NSTAGE; ++i) c->stage_free.push_back(i);
-	for (int i = 0; i < gys_ctx::RespQ::NB; ++i) c->rq.free.push_back(i);
-	c->cq[0].conn = true;
-	for (auto &q : c->cq)
-		for (int i = 0; i < gys_ctx::RecQ::NB; ++i) q.free.push_back(i);
 	c->cfg = *cfg;
+	for (SubQ::Kind k : {SubQ::RESP, SubQ::CONN, SubQ::LSTATE}) subq_init(c, k);
 	if (cfg->device >= 0) {
 		c->device = cfg->device;
 		HIPCHK(hipSetDevice(c->device));
@@ -2673,16 +2492,7 @@ void gys_destroy(gys_ctx *c)
 {
 	if (c) (void)hipSetDevice(c->device);
 	if (!c) return;
-	if (c->rq.flusher_on) {
-		{
-			std::lock_guard<std::mutex> g(c->rq.mu);
-			c->rq.stop = true;
-		}
-		c->rq.fcv.notify_all();
-		if (c->rq.flusher.joinable()) c->rq.flusher.join();
-		c->rq.flusher_on = false;
-	}
-	for (auto &q : c->cq) {
+	for (auto &q : c->sq) {
 		if (!q.flusher_on) continue;
 		{
 			std::lock_guard<std::mutex> g(q.mu);
@@ -2706,13 +2516,7 @@ void gys_destroy(gys_ctx *c)
 		if (sl.xdev) hipFree(sl.xdev);
 		if (sl.done) hipEventDestroy(sl.done);
 	}
-	for (auto &b : c->rq.b) {
-		if (b.h) hipHostFree(b.h);
-		if (b.d) hipFree(b.d);
-		if (b.done) hipEventDestroy(b.done);
-		if (b.copied) hipEventDestroy(b.copied);
-	}
-	for (auto &q : c->cq)
+	for (auto &q : c->sq)
 		for (auto &b : q.b) {
 			if (b.h) hipHostFree(b.h);
 			if (b.d) hipFree(b.d);
@@ -2895,31 +2699,8 @@ try {
 	if (!nevents) return GYS_OK;
 	static const bool no_queue = getenv("GYS_NO_RESP_QUEUE") != nullptr; // A/B: one submission per call through the staging ring
 	if (!no_queue && (uint64_t)nevents <= std::min<uint64_t>(GYS_RQ_EVENTS, c->cfg.max_batch_events))
-		return rq_ingest(c, host, ev24, nevents); // combined with the other callers' pending calls (gys_ctx::RespQ)
-	// larger than a combined batch: its own submission (after whatever the queue holds: same-host calls keep their order)
-	rc = rq_flush(c);
-	if (rc) return rc;
-	const uint64_t bytes = (uint64_t)nevents * 24;
-	int si;
-	rc = stage_acquire(c, bytes, &si);
-	if (rc) return rc;
-	gys_ctx::Stage &st = c->stage[si];
-	memcpy(st.h, ev24, bytes); // the caller's buffer is free from here on
-	{
-		std::lock_guard<std::mutex> g(c->enq_mu);
-		hipError_t e = hipMemcpyAsync(st.d, st.h, bytes, hipMemcpyHostToDevice, c->stream);
-		if (e == hipSuccess) {
-			gys_resp_seg seg{host, 0, 0};
-			rc = run_resp_batch(c, &seg, 1, st.d, nevents);
-			e = hipEventRecord(st.done, c->stream);
-		}
-		if (e != hipSuccess) {
-			set_err("gys_ingest_resp_events: %s", hipGetErrorString(e));
-			rc = GYS_ERR_HIP;
-		}
-	}
-	stage_release(c, si);
-	return rc;
+		return subq_ingest(c, c->sq[SubQ::RESP], host, ev24, 0, nevents, nullptr); // combined with the other callers' pending calls
+	return ingest_staged_resp(c, host, ev24, nevents, 24, false, "gys_ingest_resp_events"); // larger than a combined batch
 } GYS_CATCH_ALL
 
 int gys_ingest_resp_events_v6_dev(gys_ctx *c, const gys_resp_seg *segs, uint32_t nsegs, const void *d_ev48, uint64_t nevents)
@@ -2937,30 +2718,8 @@ try {
 	int rc = lookup_host(c, machine_id, &host);
 	if (rc) return rc;
 	if (!nevents) return GYS_OK;
-	// its own submission, behind whatever the IPv4 queue holds (a service's per-call value multisets keep the order of the calls)
-	rc = rq_flush(c);
-	if (rc) return rc;
-	const uint64_t bytes = (uint64_t)nevents * 48;
-	int si;
-	rc = stage_acquire(c, bytes, &si);
-	if (rc) return rc;
-	gys_ctx::Stage &st = c->stage[si];
-	memcpy(st.h, ev48, bytes); // the caller's buffer is free from here on
-	{
-		std::lock_guard<std::mutex> g(c->enq_mu);
-		hipError_t e = hipMemcpyAsync(st.d, st.h, bytes, hipMemcpyHostToDevice, c->stream);
-		if (e == hipSuccess) {
-			gys_resp_seg seg{host, 0, 0};
-			rc = run_resp_batch(c, &seg, 1, st.d, nevents, true);
-			e = hipEventRecord(st.done, c->stream);
-		}
-		if (e != hipSuccess) {
-			set_err("gys_ingest_resp_events_v6: %s", hipGetErrorString(e));
-			rc = GYS_ERR_HIP;
-		}
-	}
-	stage_release(c, si);
-	return rc;
+	// its own submission, behind whatever the IPv4 queue holds
+	return ingest_staged_resp(c, host, ev48, nevents, 48, true, "gys_ingest_resp_events_v6");
 } GYS_CATCH_ALL
 
 int gys_ingest_tcp_conn_dev(gys_ctx *c, const void *d_batch, const uint32_t *d_offsets, uint32_t nconns)
@@ -2987,7 +2746,7 @@ try {
 	}, offs);
 	if (rc) return rc;
 	if (offs.empty()) return GYS_OK;
-	return recq_ingest(c, c->cq[0], host, batch, (uint64_t)((const uint8_t *)pend - (const uint8_t *)batch), offs);
+	return ingest_records(c, c->sq[SubQ::CONN], host, batch, pend, offs);
 } GYS_CATCH_ALL
 
 int gys_ingest_listener_state_dev(gys_ctx *c, const void *d_batch, const uint32_t *d_offsets, const uint32_t *d_host_slot, uint32_t nrecs)
@@ -3050,7 +2809,7 @@ try {
 	rc = walk_batch((const uint8_t *)batch, nrecs, (const uint8_t *)pend, 88, [](const uint8_t *p) { return (uint32_t)(88u + p[85] + p[86]); }, offs);
 	if (rc) return rc;
 	if (offs.empty()) return GYS_OK;
-	return recq_ingest(c, c->cq[1], host, batch, (uint64_t)((const uint8_t *)pend - (const uint8_t *)batch), offs);
+	return ingest_records(c, c->sq[SubQ::LSTATE], host, batch, pend, offs);
 } GYS_CATCH_ALL
 
 // ------------------------------------------------------------------------------------------------ wire front-end
@@ -4973,31 +4732,22 @@ try {
 	out->actconn_remote_listen = v[CTR_ACTCONN_REMOTE_LISTEN];
 	out->actconn_unknown_listener = v[CTR_ACTCONN_UNKNOWN];
 	out->stage_waits = c->stage_waits.load();
-	{
-		std::lock_guard<std::mutex> g(c->rq.mu);
-		out->resp_calls_queued = c->rq.calls;
-		out->resp_submissions = c->rq.submissions;
-		out->resp_tail_flushes = c->rq.tail_flushes;
-	}
-	{
-		std::lock_guard<std::mutex> g(c->cq[0].mu);
-		out->conn_calls_queued = c->cq[0].calls;
-		out->conn_submissions = c->cq[0].submissions;
-		out->rec_tail_flushes = c->cq[0].tail_flushes;
-	}
-	{
-		std::lock_guard<std::mutex> g(c->cq[1].mu);
-		out->lstate_calls_queued = c->cq[1].calls;
-		out->lstate_submissions = c->cq[1].submissions;
-		out->rec_tail_flushes += c->cq[1].tail_flushes;
-	}
+	auto snap = [](SubQ &q, uint64_t *calls, uint64_t *submissions) {
+		std::lock_guard<std::mutex> g(q.mu);
+		*calls = q.calls;
+		*submissions = q.submissions;
+		return q.tail_flushes;
+	};
+	out->resp_tail_flushes = snap(c->sq[SubQ::RESP], &out->resp_calls_queued, &out->resp_submissions);
+	out->rec_tail_flushes = snap(c->sq[SubQ::CONN], &out->conn_calls_queued, &out->conn_submissions);
+	out->rec_tail_flushes += snap(c->sq[SubQ::LSTATE], &out->lstate_calls_queued, &out->lstate_submissions);
 	return GYS_OK;
 } GYS_CATCH_ALL
 
 int gys_resp_queue_pending(gys_ctx *c, uint64_t *events)
 try {
 	if (!c || !events) return GYS_ERR_INVAL;
-	gys_ctx::RespQ &q = c->rq;
+	SubQ &q = c->sq[SubQ::RESP];
 	std::lock_guard<std::mutex> g(q.mu);
 	uint64_t n = 0;
 	if (q.open >= 0) n += q.b[q.open].fill;
