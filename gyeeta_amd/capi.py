@@ -117,6 +117,14 @@ class SvcAggrRow(C.Structure):  # gys_svc_aggr_row
     _fields_ = [("group", C.c_uint32), ("ncols", C.c_uint32), ("count", C.c_uint64), ("sum", C.c_int64 * 8), ("min", C.c_int64 * 8), ("max", C.c_int64 * 8)]
 
 
+class RollupRow(C.Structure):   # gys_rollup_row
+    _fields_ = [("group", C.c_uint32), ("nmembers", C.c_uint32)]
+
+
+NO_GROUP = 0xFFFFFFFF
+GROUP_NONE, GROUP_HOST, GROUP_CLUSTER, GROUP_LABEL = 0, 1, 2, 3
+RF_ANY_STATE = 1
+
 SVC_COLS = ["qps5s", "nqry5s", "resp5s", "p95resp5s", "p95resp5m", "nconns", "nactive", "nprocs", "kbin15s", "kbout15s", "sererr", "clierr", "delayus",
             "cpudelus", "iodelus", "vmdelus", "usercpu", "syscpu", "rssmb", "nissue", "state", "issue", "ishttp"]  # GYS_SVC_COL_* in order
 SUMM_COLS = ["nidle", "ngood", "nok", "nbad", "nsevere", "ndown", "totqps", "totaconn", "totkbin", "totkbout", "totsererr", "nsvc", "nactive"]  # GYS_SUMM_COL_*
@@ -135,7 +143,7 @@ class Counters(C.Structure):
 
 
 assert C.sizeof(HistRec) == 256 and C.sizeof(TopnEntry) == 104 and C.sizeof(RespSeg) == 16 and C.sizeof(ListenerDayStats) == 48
-assert C.sizeof(SvcTerm) == 24 and C.sizeof(SvcRow) == 96 and C.sizeof(SvcAggrRow) == 208
+assert C.sizeof(SvcTerm) == 24 and C.sizeof(SvcRow) == 96 and C.sizeof(SvcAggrRow) == 208 and C.sizeof(RollupRow) == 8
 
 vp, u8p, u32p, u64p, i64p, i32p, f32p, f64p = (C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                                                C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_double))
@@ -220,6 +228,8 @@ SIGNATURES = {
     "gys_json_svcstate_multihost": (C.c_int, [vp, C.POINTER(SvcFilter), C.c_int, C.c_int, C.c_uint32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t,
                                               C.POINTER(C.c_size_t)]),
     "gys_query_svcstate_aggr": (C.c_int, [vp, C.POINTER(SvcFilter), C.c_int, u8p, C.c_uint32, C.POINTER(SvcAggrRow), C.c_uint32, u32p]),
+    "gys_set_service_groups": (C.c_int, [vp, u64p, u32p, C.c_uint32]),
+    "gys_rollup_filtered_dev": (C.c_int, [vp, C.POINTER(SvcFilter), C.c_uint32, C.c_int, C.c_int, C.c_uint64, C.POINTER(RollupRow), C.c_uint32, u32p, vp, vp, vp]),
     "gys_svc_aggr_value": (C.c_int, [C.POINTER(SvcAggrRow), C.c_uint32, C.c_int, f64p]),
     "gys_query_svcstate_percentiles": (C.c_int, [vp, C.POINTER(SvcFilter), C.c_int, f64p, C.c_uint32, i64p, u64p]),
     "gys_svc_ids_by_name": (C.c_int, [vp, C.c_int, C.POINTER(C.c_char_p), C.c_uint32, u64p, C.c_uint32, u32p]),

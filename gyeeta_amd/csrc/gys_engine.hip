@@ -31,6 +31,7 @@
 #include "gys_hllroll.hpp"
 #include "gys_huge.hpp"
 #include "gys_svcquery.hpp"
+#include "gys_rollsel.hpp"
 
 using namespace gys;
 
@@ -415,6 +416,16 @@ struct gys_ctx {
 	uint8_t *hl_lvl = nullptr;        // [GYS_HLL_LVL_FILES][max_services] files: last, the two rings, all
 	uint8_t *hl_view = nullptr;       // a level's files of every service, materialised for gys_hll_rollup_level_dev (nsvc files; grows)
 	size_t hl_view_bytes = 0;
+	// filtered roll-ups (gys_rollsel.hpp): the services' labels (gys_set_service_groups; allocated on first use, GYS_NO_GROUP everywhere)
+	// and the scratch of a selection (grows): the items' groups, the groups' counters / cursors, the members, the chunk lists,
+	// the rows with their offsets, the scan's tile sums and the totals
+	uint32_t *svc_label = nullptr;
+	uint32_t label_domain = 0; // every label set so far is below this
+	uint32_t *rs_item_group = nullptr, *rs_counts = nullptr, *rs_members = nullptr, *rs_tiles = nullptr, *rs_tot = nullptr;
+	RollupChunk *rs_chunks = nullptr, *rs_gchunks = nullptr;
+	gys_rollup_row *rs_rows = nullptr;
+	uint2 *rs_rowoff = nullptr;
+	uint64_t rs_item_cap = 0, rs_counts_cap = 0, rs_members_cap = 0, rs_tiles_cap = 0, rs_tot_cap = 0, rs_chunks_cap = 0, rs_gchunks_cap = 0, rs_rows_cap = 0, rs_rowoff_cap = 0;
 	int64_t hl_t_last = -1;           // close time (s) of the last window rolled into hl_lvl, -1: none yet
 	uint32_t hl_roll_epoch = 0xFFFFFFFEu; // the window rolled last (a finish step that is retried after a failure further down must not roll twice)
 	int64_t hl_close_t = 0;           // close time (s) the prepared window was given (gys_window_prepare; the roll runs in gys_window_finish)
@@ -2536,7 +2547,7 @@ void gys_destroy(gys_ctx *c)
 			c->batch_cnt, c->batch_off, c->scan_block_sums, c->ev_kv, c->staged, c->huge_scratch, c->huge_acc, c->huge_tail, c->huge_tb_list, c->huge_bm, c->huge_chunk_off, c->huge_fb_list, c->hll32, c->svc_ctr, c->svc_win, c->svc_state, c->svc_claim, c->svc_hll, c->host_summ_win, c->host_summ_last, c->host_state,
 			c->host_state_epoch, c->host_cluster, c->counters, c->misc, c->htbl, c->hlst, c->hdesc, c->wire_jump[0], c->wire_jump[1], c->wire_cnt,
 			c->wire_rank, c->wire_bsums, c->wire_status, c->wire_mark, c->wire_flags, c->wire_msgs, c->last, c->last_act32, c->last_act64, c->ring_act32, c->ring_act64, c->act_live, c->q_cand_key, c->q_out_keys, c->q_cand_slot, c->q_misc, c->q_host_mask, c->q_slot_list, c->q_set, c->q_out_rows, c->q_acc, c->q_cnt, c->dev_staging, c->dev_offsets, c->csr_off, c->csr_mem, c->svc_act, c->d_epoch, c->topn_slot,
-			c->topn_metric, c->dev_pcts, c->zipf_cdf, c->lvl_snap, c->lvl_last, c->lvl_last_tag, c->svc_bithist, c->rb_bins, c->rb_host_members, c->rb_host_chunks, c->rb_host_gchunks, c->hl_cl_members, c->hl_cl_chunks, c->hl_cl_gchunks, c->hl_buf, c->hl_lvl, c->hl_view, c->lvl_first, c->qps_hist, c->act_hist, c->cand_pool, c->own_arena ? c->arena : nullptr};
+			c->topn_metric, c->dev_pcts, c->zipf_cdf, c->lvl_snap, c->lvl_last, c->lvl_last_tag, c->svc_bithist, c->rb_bins, c->rb_host_members, c->rb_host_chunks, c->rb_host_gchunks, c->hl_cl_members, c->hl_cl_chunks, c->hl_cl_gchunks, c->hl_buf, c->hl_lvl, c->hl_view, c->svc_label, c->rs_item_group, c->rs_counts, c->rs_members, c->rs_tiles, c->rs_tot, c->rs_chunks, c->rs_gchunks, c->rs_rows, c->rs_rowoff, c->lvl_first, c->qps_hist, c->act_hist, c->cand_pool, c->own_arena ? c->arena : nullptr};
 	for (void *p : ptrs)
 		if (p) hipFree(p);
 	if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
@@ -4484,15 +4495,9 @@ try {
 	return GYS_OK;
 } GYS_CATCH_ALL
 
-int gys_hll_rollup_level_dev(gys_ctx *c, int scope, int level, uint64_t tusec, uint8_t *d_regs, double *d_est)
-try {
-	GYS_ENTER(c);
-	if (!c || (!d_regs && !d_est) || scope < GYS_ROLLUP_HOST || scope > GYS_ROLLUP_GLOBAL || !HLL_ALIGNED(d_regs)) {
-		set_err("gys_hll_rollup_level_dev: null outputs, an output that is not 16-byte aligned or an unknown scope");
-		return GYS_ERR_INVAL;
-	}
-	HLL_LEVEL_CHECK(level);
-	// the level's files of every service once into scratch (nsvc files; grows, never shrinks), then the roll-up of the open window on them
+// the level's files of every service once into c->hl_view (nsvc files; grows, never shrinks): the roll-ups of the open window then run on them
+static int hll_level_files(gys_ctx *c, int level, uint64_t tusec)
+{
 	const size_t need = std::max<size_t>((size_t)c->nsvc << c->cfg.svc_hll_p, 16);
 	if (c->hl_view_bytes < need) {
 		if (c->hl_view) {
@@ -4504,11 +4509,20 @@ try {
 		HIPCHK(hipMalloc((void **)&c->hl_view, need));
 		c->hl_view_bytes = need;
 	}
-	{
-		ProfScope ps(c, "hll_level_files");
-		const int rc = hll_level_view(c, level, tusec, 0u, c->nsvc, c->hl_view, nullptr);
-		if (rc) return rc;
+	ProfScope ps(c, "hll_level_files");
+	return hll_level_view(c, level, tusec, 0u, c->nsvc, c->hl_view, nullptr);
+}
+
+int gys_hll_rollup_level_dev(gys_ctx *c, int scope, int level, uint64_t tusec, uint8_t *d_regs, double *d_est)
+try {
+	GYS_ENTER(c);
+	if (!c || (!d_regs && !d_est) || scope < GYS_ROLLUP_HOST || scope > GYS_ROLLUP_GLOBAL || !HLL_ALIGNED(d_regs)) {
+		set_err("gys_hll_rollup_level_dev: null outputs, an output that is not 16-byte aligned or an unknown scope");
+		return GYS_ERR_INVAL;
 	}
+	HLL_LEVEL_CHECK(level);
+	const int rc = hll_level_files(c, level, tusec);
+	if (rc) return rc;
 	return hll_rollup_src(c, c->hl_view, scope, d_regs, d_est);
 } GYS_CATCH_ALL
 
@@ -5128,3 +5142,4 @@ try {
 #include "gys_json.hpp"
 #include "gys_regex.hpp"
 #include "gys_svcquery_host.hpp"
+#include "gys_rollsel_host.hpp"

@@ -279,6 +279,14 @@ public:
 		std::unique_lock<std::shared_mutex> g(mu_); // (a query: not concurrent with ingest calls)
 		return gys_query_svcstate_aggr(ctx_, filter, group_by, cols, ncols, out, maxrows, nrows) == GYS_OK;
 	}
+	// the aggregated response-time digest / distinct-flow count of the listeners a filter selects, per group (the WHERE + GROUP BY of
+	// public.tdigest_percentile over listeners' rows, common/gy_query_common.cc:1818-1855): rows on the host, slabs / files / estimates on the device
+	bool aggr_listener_sketches(const gys_svc_filter *filter, uint32_t flags, int group_by, int hll_level, time_t tnow, gys_rollup_row *rows, uint32_t maxrows,
+				    uint32_t *nrows, gys_tdigest_slab *d_slabs, uint8_t *d_regs, double *d_est) noexcept
+	{
+		std::unique_lock<std::shared_mutex> g(mu_); // (a query: not concurrent with ingest calls)
+		return gys_rollup_filtered_dev(ctx_, filter, flags, group_by, hll_level, (uint64_t)tnow * 1000000ull, rows, maxrows, nrows, d_slabs, d_regs, d_est) == GYS_OK;
+	}
 	// MCONN_HANDLER::web_curr_top_listeners (server/gy_mnodehandle.cc:2706-3190): machine_id = one partha's four top-10 queues,
 	// nullptr = every host's queues merged into MAX_MULTI_TOPN = 50 slots per kind; flags: GYS_TOP_* (which arrays to send)
 	bool web_curr_top_listeners(const uint8_t *machine_id, uint32_t flags, const char *madid, const char *timestr, std::string &out) noexcept

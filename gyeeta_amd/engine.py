@@ -602,6 +602,49 @@ class SketchEngine:
             res.append((r.group, r.count, {c: (r.sum[a], r.min[a], r.max[a]) for a, c in enumerate(cols)}))
         return res
 
+    # ---------------------------------------------------------------- roll-up digests / distinct counts of the services a filter selects, per group
+    def set_service_groups(self, glob_ids, groups):
+        """gys_set_service_groups: the caller's dense group index (or capi.NO_GROUP) per service; all-or-nothing on an unknown id"""
+        ids = np.ascontiguousarray(glob_ids, dtype=np.uint64)
+        grp = np.ascontiguousarray(groups, dtype=np.uint32)
+        assert ids.shape == grp.shape and ids.ndim == 1
+        capi.check(self.L.gys_set_service_groups(self.h, ids.ctypes.data_as(capi.u64p), grp.ctypes.data_as(capi.u32p), len(ids)))
+        real = grp[grp != capi.NO_GROUP]
+        if len(real):  # the label domain: what rollup_filtered sizes its outputs by (the library keeps 64 KB of scratch per computed row)
+            self._label_domain = max(getattr(self, "_label_domain", 0), int(real.max()) + 1)
+
+    def rollup_filtered(self, group_by=0, terms=None, group_oper=(), top_oper="and", machine_ids=None, svcids=None, clusters=None, any_state=False,
+                        hll_level=-1, tusec=0, want=("slabs", "regs", "est"), maxrows=None):
+        """gys_rollup_filtered_dev -> (rows [(group, nmembers)] of the groups written, nrows there are, {"slabs": SLAB_DT records,
+        "regs": (rows, m) uint8, "est": (rows,) float64} for the outputs named in `want`)"""
+        f, keep = self._svc_filter(terms, group_oper, top_oper, machine_ids, svcids, clusters)
+        if maxrows is None:
+            maxrows = {capi.GROUP_NONE: 1, capi.GROUP_HOST: self.L.gys_num_hosts(self.h), capi.GROUP_CLUSTER: self.L.gys_num_clusters(self.h)}.get(
+                group_by, min(getattr(self, "_label_domain", 0), self.num_services()))
+        cap = max(maxrows, 1)
+        m = self.L.gys_hll_file_bytes(self.h)
+        u8 = self.torch.uint8
+        slabs = self.torch.zeros(cap * C.sizeof(capi.TDigestSlab), dtype=u8, device=self.device) if "slabs" in want else None
+        regs = self.torch.zeros(max(cap * m, 16), dtype=u8, device=self.device) if "regs" in want else None
+        est = self.torch.zeros(cap, dtype=self.torch.float64, device=self.device) if "est" in want else None
+        rows = (capi.RollupRow * cap)()
+        n = C.c_uint32()
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self.order()
+        capi.check(self.L.gys_rollup_filtered_dev(self.h, C.byref(f), capi.RF_ANY_STATE if any_state else 0, group_by, hll_level, tusec, rows, maxrows,
+                                                  C.byref(n), ptr(slabs), ptr(regs), ptr(est)))
+        self.sync()
+        nr = min(n.value, maxrows)
+        out = {}
+        if slabs is not None:
+            out["slabs"] = np.frombuffer(slabs.cpu().numpy().tobytes(), dtype=self.SLAB_DT)[:nr]
+            out["slabs_dev"] = slabs
+        if regs is not None:
+            out["regs"] = regs[:nr * m].cpu().numpy().reshape(nr, m)
+        if est is not None:
+            out["est"] = est[:nr].cpu().numpy()
+        return [(rows[i].group, rows[i].nmembers) for i in range(nr)], n.value, out
+
     def json_clusterstate(self, shyamaid="0" * 16, timestr=""):
         return self._json(self.L.gys_json_clusterstate, shyamaid.encode(), timestr.encode())
 

@@ -653,6 +653,53 @@ enum { GYS_SUMM_COL_NIDLE = 0, GYS_SUMM_COL_NGOOD, GYS_SUMM_COL_NOK, GYS_SUMM_CO
 int gys_json_svcsumm_multihost(gys_ctx *ctx, const gys_svc_filter *filter, int sort_col, int sort_desc, uint32_t maxrecs, const char *madhava_id16,
 			       const char *timestr, char *buf, size_t buflen, size_t *needed);
 
+/* -------------------------------------------------------------------------------------------------------------------
+ * Roll-up digests and distinct counts of the services a FILTER selects, per GROUP: the WHERE and the GROUP BY of the aggregated percentile
+ * the reference computes in Postgres, public.tdigest_percentile(col, 100, p) over a set of listeners' rows
+ * (common/gy_query_common.cc:1818-1855) -- "p99 of the services whose state is bad, per cluster", "distinct flows to these 40 svcids",
+ * "p95 of the same service across all its hosts" (the aggregation MAGGR_LISTENER / aggr_glob_id_ stands for).  One call: the filter pass,
+ * the members of every group gathered on the device, then the roll-up kernels of gys_tdigest_rollup_dev / gys_hll_rollup_dev on them.
+ *
+ * Labels: a caller-assigned dense group index per service (its own map of aggr_glob_id_ / a service name to 0 .. G-1).  Every service
+ * starts at GYS_NO_GROUP.  groups[i] < gys_config.max_services or GYS_NO_GROUP; every id is checked before anything is applied: an unknown
+ * id or a group out of range is GYS_ERR_INVAL and changes nothing.  An id named twice keeps the later group. */
+#define GYS_NO_GROUP 0xFFFFFFFFu
+int gys_set_service_groups(gys_ctx *ctx, const uint64_t *glob_ids, const uint32_t *groups, uint32_t n);
+
+typedef struct {
+	uint32_t group, nmembers; /* host slot / cluster index / label / 0; services in it */
+} gys_rollup_row;
+enum { GYS_GROUP_NONE = 0, GYS_GROUP_HOST = 1, GYS_GROUP_CLUSTER = 2, GYS_GROUP_LABEL = 3 }; /* 0 .. 2 as gys_query_svcstate_aggr */
+#define GYS_RF_ANY_STATE 1u
+/* MEMBERS.  flags 0: exactly the services gys_query_svcstate_scan lists for `filter` with an unlimited maxrecs -- state record current, the
+ * terms pass, machine_ids / svcids / clusters select them.  GYS_RF_ANY_STATE: every registered service is a candidate whatever the age of
+ * its state record; the terms are evaluated on the kept record (all zero if the service never reported) and the selections still apply -- the
+ * form for a deployment that ingests response events only.
+ * GROUP of a member: GYS_GROUP_NONE: 0; _HOST: its host slot; _CLUSTER: its host's cluster index; _LABEL: its label (a service labelled
+ * GYS_NO_GROUP is in no group).
+ * ROWS (HOST): one per group that has a member, in ascending group order (the rule of gys_query_svcstate_aggr).  *nrows = such groups; it may
+ * exceed maxrows, then the first maxrows groups are computed and written.  Row r owns d_slabs[r], file r of d_regs
+ * (gys_hll_file_bytes each, 16-byte aligned) and d_est[r] (DEVICE, maxrows entries each).  Any of the three may be NULL, not all:
+ * d_slabs needs enable_tdigest, d_regs / d_est need svc_hll_p (GYS_ERR_STATE otherwise).  rows and *nrows are valid on return (one small
+ * read of the counts inside the call); the device outputs follow in stream order (gys_sync).
+ * SCRATCH: the digests need 64 KB of value bins per COMPUTED row (min(*nrows, maxrows) rows; kept by the context, grown on demand) besides the
+ * caller's maxrows slabs / files / estimates: size maxrows by the groups there can be (1, gys_num_hosts, gys_num_clusters, the highest label
+ * set + 1), not by the number of services -- 10^4 label groups are 640 MB of bins, 10^7 would be 640 GB.
+ * hll_level -1: the open window's registers (as gys_hll_rollup_dev); 0 .. 3: the level's files at tusec (as gys_hll_rollup_level_dev; needs
+ * svc_hll_levels, GYS_ERR_STATE otherwise); anything else GYS_ERR_INVAL, as are an unknown group_by, unknown flags and NULL filter / rows /
+ * nrows.  (A filter without terms and selections -- all zero -- selects everything.)
+ * DEFINITIONS.  A group's digest is the DIRECT union by value bin of its member services (every member's clusters and buffered values
+ * into the group's bins, then the cut into clusters) -- not a roll-up of host slabs: a filtered GYS_GROUP_CLUSTER group holding all
+ * services of a cluster is the same distribution as, but NOT bit-equal to, the GYS_ROLLUP_CLUSTER slab, which goes through the host
+ * slabs; GYS_GROUP_HOST groups holding all services of their hosts ARE bit-equal to GYS_ROLLUP_HOST.  A group's register file is the
+ * byte-wise maximum of its members' files (bit-equal to the fixed roll-ups of the same members at every scope), its estimate the one
+ * estimator on those bytes.  Both are independent of the order of the members: results are bit-reproducible.
+ * No engine state is modified; concurrency as the other query calls.  ACROSS RANKS there is no collective of its own: every rank runs the
+ * call with the same filter and labels, the caller all-gathers its rows' slabs / files and joins the rows of one group with
+ * gys_tdigest_merge_slabs_dev / gys_hll_merge_files_dev. */
+int gys_rollup_filtered_dev(gys_ctx *ctx, const gys_svc_filter *filter, uint32_t flags, int group_by, int hll_level, uint64_t tusec,
+			    gys_rollup_row *rows, uint32_t maxrows, uint32_t *nrows, gys_tdigest_slab *d_slabs, uint8_t *d_regs, double *d_est);
+
 /* The per-listener 5-second scan from the engine's OWN state (needs gys_config.enable_levels): replaces the loop of
  * TCP_SOCK_HANDLER::listener_stats_update (common/gy_socket_stat.cc:4044-4365) that turns every listener's counters and histograms into
  * one comm::LISTENER_STATE_NOTIFY (common/gy_comm_proto.h:2183-2254), and the data-parallel part of TCP_LISTENER::get_curr_state
