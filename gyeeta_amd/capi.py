@@ -230,6 +230,8 @@ SIGNATURES = {
     "gys_query_svcstate_aggr": (C.c_int, [vp, C.POINTER(SvcFilter), C.c_int, u8p, C.c_uint32, C.POINTER(SvcAggrRow), C.c_uint32, u32p]),
     "gys_set_service_groups": (C.c_int, [vp, u64p, u32p, C.c_uint32]),
     "gys_rollup_filtered_dev": (C.c_int, [vp, C.POINTER(SvcFilter), C.c_uint32, C.c_int, C.c_int, C.c_uint64, C.POINTER(RollupRow), C.c_uint32, u32p, vp, vp, vp]),
+    "gys_hist_rollup_level_dev": (C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, vp]),
+    "gys_hist_rollup_filtered_dev": (C.c_int, [vp, C.POINTER(SvcFilter), C.c_uint32, C.c_int, C.c_int, C.c_uint64, C.POINTER(RollupRow), C.c_uint32, u32p, vp]),
     "gys_svc_aggr_value": (C.c_int, [C.POINTER(SvcAggrRow), C.c_uint32, C.c_int, f64p]),
     "gys_query_svcstate_percentiles": (C.c_int, [vp, C.POINTER(SvcFilter), C.c_int, f64p, C.c_uint32, i64p, u64p]),
     "gys_svc_ids_by_name": (C.c_int, [vp, C.c_int, C.POINTER(C.c_char_p), C.c_uint32, u64p, C.c_uint32, u32p]),

@@ -29,6 +29,7 @@
 #include "gys_kernels.hpp"
 #include "gys_rollup.hpp"
 #include "gys_hllroll.hpp"
+#include "gys_histroll.hpp"
 #include "gys_huge.hpp"
 #include "gys_svcquery.hpp"
 #include "gys_rollsel.hpp"
@@ -412,6 +413,9 @@ struct gys_ctx {
 	std::vector<uint32_t> hl_cl_snap; // host_cluster_h the lists were built from
 	uint8_t *hl_buf = nullptr;
 	size_t hl_buf_bytes = 0;
+	// group histograms of the levels (gys_histroll.hpp): one scratch buffer (grows: a record per chunk and per host)
+	gys_hist_rec *hr_buf = nullptr;
+	size_t hr_buf_recs = 0;
 	// distinct counts of the closed windows (cfg.svc_hll_levels; "levels" in gys_hllroll.hpp)
 	uint8_t *hl_lvl = nullptr;        // [GYS_HLL_LVL_FILES][max_services] files: last, the two rings, all
 	uint8_t *hl_view = nullptr;       // a level's files of every service, materialised for gys_hll_rollup_level_dev (nsvc files; grows)
@@ -2547,7 +2551,7 @@ void gys_destroy(gys_ctx *c)
 			c->batch_cnt, c->batch_off, c->scan_block_sums, c->ev_kv, c->staged, c->huge_scratch, c->huge_acc, c->huge_tail, c->huge_tb_list, c->huge_bm, c->huge_chunk_off, c->huge_fb_list, c->hll32, c->svc_ctr, c->svc_win, c->svc_state, c->svc_claim, c->svc_hll, c->host_summ_win, c->host_summ_last, c->host_state,
 			c->host_state_epoch, c->host_cluster, c->counters, c->misc, c->htbl, c->hlst, c->hdesc, c->wire_jump[0], c->wire_jump[1], c->wire_cnt,
 			c->wire_rank, c->wire_bsums, c->wire_status, c->wire_mark, c->wire_flags, c->wire_msgs, c->last, c->last_act32, c->last_act64, c->ring_act32, c->ring_act64, c->act_live, c->q_cand_key, c->q_out_keys, c->q_cand_slot, c->q_misc, c->q_host_mask, c->q_slot_list, c->q_set, c->q_out_rows, c->q_acc, c->q_cnt, c->dev_staging, c->dev_offsets, c->csr_off, c->csr_mem, c->svc_act, c->d_epoch, c->topn_slot,
-			c->topn_metric, c->dev_pcts, c->zipf_cdf, c->lvl_snap, c->lvl_last, c->lvl_last_tag, c->svc_bithist, c->rb_bins, c->rb_host_members, c->rb_host_chunks, c->rb_host_gchunks, c->hl_cl_members, c->hl_cl_chunks, c->hl_cl_gchunks, c->hl_buf, c->hl_lvl, c->hl_view, c->svc_label, c->rs_item_group, c->rs_counts, c->rs_members, c->rs_tiles, c->rs_tot, c->rs_chunks, c->rs_gchunks, c->rs_rows, c->rs_rowoff, c->lvl_first, c->qps_hist, c->act_hist, c->cand_pool, c->own_arena ? c->arena : nullptr};
+			c->topn_metric, c->dev_pcts, c->zipf_cdf, c->lvl_snap, c->lvl_last, c->lvl_last_tag, c->svc_bithist, c->rb_bins, c->rb_host_members, c->rb_host_chunks, c->rb_host_gchunks, c->hl_cl_members, c->hl_cl_chunks, c->hl_cl_gchunks, c->hl_buf, c->hr_buf, c->hl_lvl, c->hl_view, c->svc_label, c->rs_item_group, c->rs_counts, c->rs_members, c->rs_tiles, c->rs_tot, c->rs_chunks, c->rs_gchunks, c->rs_rows, c->rs_rowoff, c->lvl_first, c->qps_hist, c->act_hist, c->cand_pool, c->own_arena ? c->arena : nullptr};
 	for (void *p : ptrs)
 		if (p) hipFree(p);
 	if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
@@ -4803,6 +4807,129 @@ try {
 	}
 	hipFree(tmp);
 	return rc;
+} GYS_CATCH_ALL
+
+// ------------------------------------------------------------------------------------------------ group histograms of the levels (gys_histroll.hpp)
+// the scratch buffer: [partial records: one per chunk][host records].  Grows, never shrinks (chunks <= services / 1024 + groups).
+static int hist_union_scratch(gys_ctx *c, size_t nparts, size_t nhostrecs, gys_hist_rec **parts, gys_hist_rec **hostrecs)
+{
+	const size_t a = std::max<size_t>(nparts, 1);
+	if (c->hr_buf_recs < a + nhostrecs) {
+		if (c->hr_buf) {
+			HIPCHK(hipStreamSynchronize(c->stream));
+			HIPCHK(hipFree(c->hr_buf));
+			c->hr_buf = nullptr;
+			c->hr_buf_recs = 0;
+		}
+		HIPCHK(hipMalloc((void **)&c->hr_buf, (a + nhostrecs) * sizeof(gys_hist_rec)));
+		c->hr_buf_recs = a + nhostrecs;
+	}
+	*parts = c->hr_buf;
+	if (hostrecs) *hostrecs = c->hr_buf + a;
+	return GYS_OK;
+}
+
+static void hist_union_launch(gys_ctx *c, const HistUnionP &q)
+{
+	if (q.nchunks) hipLaunchKernelGGL(k_hist_level_union, dim3(std::min<uint32_t>(q.nchunks, (uint32_t)c->ncu * 8)), dim3(GYS_HR_NT), 0, c->stream, q);
+}
+
+// the sources of `level` at tusec for every service, exactly as level_view() reads them: the fold of the buffered values first, then
+// tq = max(tusec / 10^6, the last close) -- never the open window
+static int hist_union_level(gys_ctx *c, int level, uint64_t tusec, HistUnionP &q)
+{
+	int64_t tq = (int64_t)(tusec / 1000000ull);
+	if (tq < c->lvl_t_last) tq = c->lvl_t_last;
+	{
+		const int rcf = fold_range(c, 0, c->nsvc);
+		if (rcf) return rcf;
+	}
+	q = HistUnionP{};
+	q.v.win = c->hist_win;
+	q.v.all = c->hist_all;
+	q.v.meta = c->cfg.enable_tdigest ? c->td_meta : nullptr;
+	q.v.epoch_open = c->epoch + (c->prepared ? 1u : 0u);
+	level_source(c, level, tq, &q.v.mode, &q.v.sub);
+	q.v.last_tag = c->cfg.enable_tdigest ? c->lvl_last_tag : nullptr;
+	q.v.last_epoch = c->lvl_last_epoch;
+	return GYS_OK;
+}
+
+// the members' level records -> one record per chunk (parts) -> one per row (d_rows)
+static int hist_union_rows(gys_ctx *c, int level, uint64_t tusec, const RollupChunk *d_chunks, uint32_t nchunks, const uint32_t *d_members, const RollupChunk *d_gchunks,
+			   uint32_t nrows, gys_hist_rec *parts, gys_hist_rec *d_rows)
+{
+	HistUnionP q;
+	const int rc = hist_union_level(c, level, tusec, q);
+	if (rc) return rc;
+	ProfScope ps(c, "hist_rollup_union");
+	q.dst = parts;
+	q.chunks = d_chunks;
+	q.members = d_members;
+	q.nchunks = nchunks;
+	hist_union_launch(c, q);
+	HistUnionP g{};
+	g.plain = 1;
+	g.src = parts;
+	g.dst = d_rows;
+	g.chunks = d_gchunks;
+	g.nchunks = nrows;
+	hist_union_launch(c, g);
+	HIPCHK(hipGetLastError());
+	return GYS_OK;
+}
+
+int gys_hist_rollup_level_dev(gys_ctx *c, int scope, int level, uint64_t tusec, gys_hist_rec *d_out)
+try {
+	GYS_ENTER(c);
+	if (!c || !d_out || scope < GYS_ROLLUP_HOST || scope > GYS_ROLLUP_GLOBAL || level < 0 || level >= GYS_NLEVELS) {
+		set_err("gys_hist_rollup_level_dev: null output, an unknown scope or a level outside 0 .. %d", GYS_NLEVELS - 1);
+		return GYS_ERR_INVAL;
+	}
+	LEVELS_CHECK();
+	LEVEL0_CHECK(level);
+	const uint32_t nh = (uint32_t)c->hosts.size(), ncl = (uint32_t)c->cluster_names.size();
+	const uint32_t ngroups = scope == GYS_ROLLUP_HOST ? nh : (scope == GYS_ROLLUP_CLUSTER ? ncl : 1u);
+	if (!ngroups) return GYS_OK;
+	int rc = rollup_host_lists(c);
+	if (rc == GYS_OK && scope == GYS_ROLLUP_CLUSTER) rc = hll_cluster_lists(c);
+	if (rc) return rc;
+	const uint32_t nparts = std::max(std::max(c->rb_host_nchunks, scope == GYS_ROLLUP_CLUSTER ? c->hl_cl_nchunks : 0u), (nh + GYS_RB_CHUNK_SERVICES - 1) / GYS_RB_CHUNK_SERVICES);
+	gys_hist_rec *parts = nullptr, *hostrecs = nullptr;
+	if ((rc = hist_union_scratch(c, nparts, scope == GYS_ROLLUP_HOST ? 0 : nh, &parts, &hostrecs)) != GYS_OK) return rc;
+	if (scope == GYS_ROLLUP_HOST) hostrecs = d_out;
+	if ((rc = hist_union_rows(c, level, tusec, c->rb_host_chunks, c->rb_host_nchunks, c->rb_host_members, c->rb_host_gchunks, nh, parts, hostrecs)) != GYS_OK) return rc;
+	if (scope == GYS_ROLLUP_HOST) return GYS_OK;
+	ProfScope ps(c, "hist_rollup_groups"); // host records -> cluster records / the rank's record (plain)
+	HistUnionP g{};
+	g.plain = 1;
+	g.src = hostrecs;
+	g.dst = parts;
+	if (scope == GYS_ROLLUP_CLUSTER) {
+		g.chunks = c->hl_cl_chunks;
+		g.members = c->hl_cl_members;
+		g.nchunks = c->hl_cl_nchunks;
+	} else { // equal chunks of the contiguous host records (no host: one empty chunk)
+		g.n = nh;
+		g.per = GYS_RB_CHUNK_SERVICES;
+		g.nchunks = std::max(1u, (nh + GYS_RB_CHUNK_SERVICES - 1) / GYS_RB_CHUNK_SERVICES);
+	}
+	hist_union_launch(c, g);
+	HistUnionP f{};
+	f.plain = 1;
+	f.src = parts;
+	f.dst = d_out;
+	if (scope == GYS_ROLLUP_CLUSTER) {
+		f.chunks = c->hl_cl_gchunks;
+		f.nchunks = ncl;
+	} else {
+		f.n = g.nchunks;
+		f.per = std::max(g.nchunks, 1u);
+		f.nchunks = 1u;
+	}
+	hist_union_launch(c, f);
+	HIPCHK(hipGetLastError());
+	return GYS_OK;
 } GYS_CATCH_ALL
 
 int gys_query_hist_level_stats(gys_ctx *c, uint64_t glob_id, int level, uint64_t tusec, gys_time_hist_val *pstats, uint32_t nstats, int64_t *tcount,

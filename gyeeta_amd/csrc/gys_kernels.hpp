@@ -4119,38 +4119,72 @@ struct LevelViewP {
 	gys_hist_rec *out;       // [n]; max_val_seen is the all-time maximum for every level (the reference keeps no per-level maximum)
 };
 
-__global__ __launch_bounds__(256) void k_level_view(LevelViewP p)
+// THE level-view rule for pair k of service `slot`, in two halves so that a caller can have the loads of several services in flight before the first
+// is used (k_hist_level_union, gys_histroll.hpp): level_pair_load issues every load the pair needs, level_pair_value is pure arithmetic.
+//   cumulative record - the folded part of the OPEN window (lazily folded records whose hw_epoch is the open epoch) - the snapshot (mode 0);
+//   mode 1: empty; mode 2: the last-window record behind its last_tag test; pair 15's .y is the all-time maximum at every level.
+// SPARSE = false loads what k_level_view always loaded.  SPARSE = true leaves out the loads whose value the rule then does not look at (the window
+// record of a service whose open window holds nothing folded, the cumulative pairs 0..14 of modes 1 and 2): the same result from fewer bytes.
+struct LevelPair {
+	ulonglong2 cum, w, s;
+	uint32_t hw, tag;
+};
+
+template <bool SPARSE>
+__device__ __forceinline__ LevelPair level_pair_load(const LevelViewP &p, uint32_t slot, uint32_t k)
 {
-	const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (t >= (uint64_t)p.n * 16ull) return;
-	const uint32_t slot = p.first + (uint32_t)(t >> 4), k = (uint32_t)(t & 15u);
 	const uint64_t g = (uint64_t)slot * 16ull + k;
-	ulonglong2 cum = ((const ulonglong2 *)p.all)[g];
-	const ulonglong2 w = ((const ulonglong2 *)p.win)[g];
+	LevelPair in;
+	in.cum = in.w = in.s = ulonglong2{0ull, 0ull};
+	in.hw = p.epoch_open + 1u; // (not the open epoch)
+	in.tag = p.last_epoch;
+	if (!SPARSE || p.mode == 0 || k == 15u) in.cum = ((const ulonglong2 *)p.all)[g];
+	if (p.meta && (!SPARSE || p.mode == 0)) in.hw = p.meta[slot].hw_epoch;
+	if (!SPARSE || (p.meta ? in.hw == p.epoch_open : k == 15u)) in.w = ((const ulonglong2 *)p.win)[g];
+	if (p.mode == 0) {
+		if (p.sub) in.s = ((const ulonglong2 *)p.sub)[g];
+	} else if (p.mode == 2) {
+		if (p.last_tag) in.tag = p.last_tag[slot];
+		if (in.tag == p.last_epoch) in.s = ((const ulonglong2 *)p.sub)[g];
+	}
+	return in;
+}
+
+__device__ __forceinline__ ulonglong2 level_pair_value(const LevelViewP &p, const LevelPair &in, uint32_t k)
+{
+	ulonglong2 cum = in.cum;
 	if (p.meta) {
-		if (p.meta[slot].hw_epoch == p.epoch_open) { // the folded part of the OPEN window is not in any level yet
-			cum.x -= w.x;
-			if (k < 15u) cum.y -= w.y;
+		if (in.hw == p.epoch_open) { // the folded part of the OPEN window is not in any level yet
+			cum.x -= in.w.x;
+			if (k < 15u) cum.y -= in.w.y;
 		}
-	} else if (k == 15u && (long long)cum.y < (long long)w.y) {
-		cum.y = w.y; // the maximum is reported over everything seen
+	} else if (k == 15u && (long long)cum.y < (long long)in.w.y) {
+		cum.y = in.w.y; // the maximum is reported over everything seen
 	}
 	ulonglong2 r;
 	if (p.mode == 0) {
 		r = cum;
 		if (p.sub) {
-			const ulonglong2 s = ((const ulonglong2 *)p.sub)[g];
-			r.x -= s.x;
-			if (k < 15u) r.y -= s.y;
+			r.x -= in.s.x;
+			if (k < 15u) r.y -= in.s.y;
 		}
-	} else if (p.mode == 2 && (!p.last_tag || p.last_tag[slot] == p.last_epoch)) {
-		r = ((const ulonglong2 *)p.sub)[g];
+	} else if (p.mode == 2 && in.tag == p.last_epoch) {
+		r = in.s;
 		if (k == 15u) r.y = cum.y;
 	} else {
 		r.x = 0;
 		r.y = k < 15u ? 0ull : cum.y;
 	}
-	((ulonglong2 *)p.out)[t] = r;
+	return r;
+}
+
+__global__ __launch_bounds__(256) void k_level_view(LevelViewP p)
+{
+	const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (t >= (uint64_t)p.n * 16ull) return;
+	const uint32_t slot = p.first + (uint32_t)(t >> 4), k = (uint32_t)(t & 15u);
+	const LevelPair in = level_pair_load<false>(p, slot, k);
+	((ulonglong2 *)p.out)[t] = level_pair_value(p, in, k);
 }
 
 // TIME_HISTOGRAM::get_stats_for_period (common/gy_statistics.h:1378-1406): per histogram bucket count(start, end) / sum(start, end) of the

@@ -287,6 +287,20 @@ public:
 		std::unique_lock<std::shared_mutex> g(mu_); // (a query: not concurrent with ingest calls)
 		return gys_rollup_filtered_dev(ctx_, filter, flags, group_by, hll_level, (uint64_t)tnow * 1000000ull, rows, maxrows, nrows, d_slabs, d_regs, d_est) == GYS_OK;
 	}
+	// the response-time histogram of every host / cluster / this madhava at one of the 5 s / 5 min / 5 days / all levels (the sum of the
+	// listeners' level records: GY_HISTOGRAM::add_histogram, common/gy_statistics.h:625-660), and of the listeners a filter selects, per group;
+	// records on the device, percentiles through gys_hist_percentiles_dev
+	bool aggr_resp_hist_level(int scope, int level, time_t tnow, gys_hist_rec *d_out) noexcept
+	{
+		std::unique_lock<std::shared_mutex> g(mu_); // (a query: not concurrent with ingest calls)
+		return gys_hist_rollup_level_dev(ctx_, scope, level, (uint64_t)tnow * 1000000ull, d_out) == GYS_OK;
+	}
+	bool aggr_listener_resp_hist(const gys_svc_filter *filter, uint32_t flags, int group_by, int level, time_t tnow, gys_rollup_row *rows, uint32_t maxrows, uint32_t *nrows,
+				     gys_hist_rec *d_recs) noexcept
+	{
+		std::unique_lock<std::shared_mutex> g(mu_);
+		return gys_hist_rollup_filtered_dev(ctx_, filter, flags, group_by, level, (uint64_t)tnow * 1000000ull, rows, maxrows, nrows, d_recs) == GYS_OK;
+	}
 	// MCONN_HANDLER::web_curr_top_listeners (server/gy_mnodehandle.cc:2706-3190): machine_id = one partha's four top-10 queues,
 	// nullptr = every host's queues merged into MAX_MULTI_TOPN = 50 slots per kind; flags: GYS_TOP_* (which arrays to send)
 	bool web_curr_top_listeners(const uint8_t *machine_id, uint32_t flags, const char *madid, const char *timestr, std::string &out) noexcept

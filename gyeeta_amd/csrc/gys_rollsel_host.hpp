@@ -1,5 +1,6 @@
 // gys_rollsel_host.hpp -- host side of the filtered, grouped roll-ups (kernels: gys_rollsel.hpp).  Included once by gys_engine.hip behind
-// gys_svcquery_host.hpp: the filter goes through q_fill_filter, the members through rollup_run / hll_union_launch as those of the fixed roll-ups.
+// gys_svcquery_host.hpp: the filter goes through q_fill_filter, the members through rollup_run / hll_union_launch / hist_union_rows as those of the
+// fixed roll-ups.
 #pragma once
 
 #define GYS_RS_ROWS_EAGER 65536u // up to this many possible rows (512 KB) the rows travel with the totals, before it is known how many there are
@@ -69,25 +70,14 @@ try {
 	return GYS_OK;
 } GYS_CATCH_ALL
 
-int gys_rollup_filtered_dev(gys_ctx *c, const gys_svc_filter *f, uint32_t flags, int group_by, int hll_level, uint64_t tusec, gys_rollup_row *rows, uint32_t maxrows,
-			    uint32_t *nrows, gys_tdigest_slab *d_slabs, uint8_t *d_regs, double *d_est)
-try {
-	GYS_ENTER(c);
-	if (!c || !f || !rows || !nrows || (flags & ~GYS_RF_ANY_STATE) || group_by < GYS_GROUP_NONE || group_by > GYS_GROUP_LABEL || (!d_slabs && !d_regs && !d_est) ||
-	    hll_level < -1 || hll_level >= GYS_NLEVELS || !HLL_ALIGNED(d_regs)) {
-		set_err("gys_rollup_filtered_dev: null filter / rows / nrows / outputs, d_regs not 16-byte aligned, unknown flags, group_by or hll_level");
-		return GYS_ERR_INVAL;
-	}
-	*nrows = 0;
-	if (d_slabs) TDIGEST_CHECK();
-	const bool want_hll = d_regs || d_est;
-	if (want_hll) {
-		HLL_CHECK();
-		if (hll_level >= 0 && !c->hl_lvl) {
-			set_err("distinct-count levels are off (gys_config.svc_hll_levels = 0)");
-			return GYS_ERR_STATE;
-		}
-	}
+} // extern "C"
+
+// the selection half of the filtered roll-ups: the filter's services grouped into rows (rows / *nrows are the caller's), their members in
+// c->rs_members, the chunk lists in c->rs_chunks (*pnchunks chunks) and the rows' chunk ranges in c->rs_gchunks (*pnr rows, 0: nothing to do)
+static int rollsel_select(gys_ctx *c, const gys_svc_filter *f, uint32_t flags, int group_by, gys_rollup_row *rows, uint32_t maxrows, uint32_t *nrows, uint32_t *pnr,
+			  uint32_t *pnchunks)
+{
+	*pnr = *pnchunks = 0;
 	const uint32_t nh = (uint32_t)c->hosts.size(), ncl = (uint32_t)c->cluster_names.size();
 	const uint32_t ndomain = group_by == GYS_GROUP_NONE ? 1u : group_by == GYS_GROUP_HOST ? nh : group_by == GYS_GROUP_CLUSTER ? ncl : (c->svc_label ? c->label_domain : 0u);
 	int rc;
@@ -166,7 +156,35 @@ try {
 		hipLaunchKernelGGL(k_rollsel_chunks, dim3(std::min<uint32_t>((nr + 3u) / 4u, (uint32_t)c->ncu * 8)), dim3(GYS_RS_THREADS), 0, c->stream, cp);
 		HIPCHK(hipGetLastError());
 	}
-	const uint32_t nr = std::min(tot[RS_TOT_ROWS], maxrows), nchunks = tot[RS_TOT_CHUNKS];
+	*pnr = std::min(tot[RS_TOT_ROWS], maxrows);
+	*pnchunks = tot[RS_TOT_CHUNKS];
+	return GYS_OK;
+}
+
+extern "C" {
+
+int gys_rollup_filtered_dev(gys_ctx *c, const gys_svc_filter *f, uint32_t flags, int group_by, int hll_level, uint64_t tusec, gys_rollup_row *rows, uint32_t maxrows,
+			    uint32_t *nrows, gys_tdigest_slab *d_slabs, uint8_t *d_regs, double *d_est)
+try {
+	GYS_ENTER(c);
+	if (!c || !f || !rows || !nrows || (flags & ~GYS_RF_ANY_STATE) || group_by < GYS_GROUP_NONE || group_by > GYS_GROUP_LABEL || (!d_slabs && !d_regs && !d_est) ||
+	    hll_level < -1 || hll_level >= GYS_NLEVELS || !HLL_ALIGNED(d_regs)) {
+		set_err("gys_rollup_filtered_dev: null filter / rows / nrows / outputs, d_regs not 16-byte aligned, unknown flags, group_by or hll_level");
+		return GYS_ERR_INVAL;
+	}
+	*nrows = 0;
+	if (d_slabs) TDIGEST_CHECK();
+	const bool want_hll = d_regs || d_est;
+	if (want_hll) {
+		HLL_CHECK();
+		if (hll_level >= 0 && !c->hl_lvl) {
+			set_err("distinct-count levels are off (gys_config.svc_hll_levels = 0)");
+			return GYS_ERR_STATE;
+		}
+	}
+	uint32_t nr, nchunks;
+	int rc = rollsel_select(c, f, flags, group_by, rows, maxrows, nrows, &nr, &nchunks);
+	if (rc != GYS_OK || !nr) return rc;
 	if (d_slabs) {
 		ProfScope ps(c, "rollsel_digests");
 		if ((rc = rollup_run(c, 0, c->rs_chunks, nchunks, c->rs_members, nr, nullptr, d_slabs)) != GYS_OK) return rc;
@@ -188,6 +206,26 @@ try {
 		HIPCHK(hipGetLastError());
 	}
 	return GYS_OK;
+} GYS_CATCH_ALL
+
+int gys_hist_rollup_filtered_dev(gys_ctx *c, const gys_svc_filter *f, uint32_t flags, int group_by, int level, uint64_t tusec, gys_rollup_row *rows, uint32_t maxrows,
+				 uint32_t *nrows, gys_hist_rec *d_recs)
+try {
+	GYS_ENTER(c);
+	if (!c || !f || !rows || !nrows || !d_recs || (flags & ~GYS_RF_ANY_STATE) || group_by < GYS_GROUP_NONE || group_by > GYS_GROUP_LABEL || level < 0 || level >= GYS_NLEVELS) {
+		set_err("gys_hist_rollup_filtered_dev: null filter / rows / nrows / d_recs, unknown flags or group_by, or a level outside 0 .. %d", GYS_NLEVELS - 1);
+		return GYS_ERR_INVAL;
+	}
+	*nrows = 0;
+	LEVELS_CHECK();
+	LEVEL0_CHECK(level);
+	uint32_t nr, nchunks;
+	int rc = rollsel_select(c, f, flags, group_by, rows, maxrows, nrows, &nr, &nchunks);
+	if (rc != GYS_OK || !nr) return rc;
+	gys_hist_rec *parts = nullptr;
+	if ((rc = hist_union_scratch(c, nchunks, 0, &parts, nullptr)) != GYS_OK) return rc;
+	// the members' level records -> one record per chunk -> one per row
+	return hist_union_rows(c, level, tusec, c->rs_chunks, nchunks, c->rs_members, c->rs_gchunks, nr, parts, d_recs);
 } GYS_CATCH_ALL
 
 } // extern "C"

@@ -645,6 +645,46 @@ class SketchEngine:
             out["est"] = est[:nr].cpu().numpy()
         return [(rows[i].group, rows[i].nmembers) for i in range(nr)], n.value, out
 
+    # ---------------------------------------------------------------- group response-time histograms of the levels (0 = window closed last, 1 = 300 s, 2 = 5 days, 3 = all)
+    def _group_percentiles(self, dev_recs, n, pcts):
+        """gys_hist_percentiles_dev(GYS_RESP_TIME_HASH) on n device records: (n, len(pcts)) int64"""
+        out = self.torch.zeros(max(n * len(pcts), 1), dtype=self.torch.int64, device=self.device)
+        pa = (C.c_float * len(pcts))(*pcts)
+        capi.check(self.L.gys_hist_percentiles_dev(self.h, 0, C.c_void_p(dev_recs.data_ptr()), n, pa, len(pcts), C.c_void_p(out.data_ptr())))
+        self.sync()
+        return out[:n * len(pcts)].cpu().numpy().reshape(n, len(pcts))
+
+    def hist_rollup_level(self, scope, level, tusec=0, pcts=None):
+        """gys_hist_rollup_level_dev: the hosts' / clusters' / the rank's records of a level at tusec, [groups][16][2] int64 like
+        export_hist_level; with pcts=(...) -> (records, percentiles (groups, len(pcts)) int64 of gys_hist_percentiles_dev on the device records)"""
+        n = self._hll_groups(scope)
+        recs = self.torch.zeros((max(n, 1), 16, 2), dtype=self.torch.int64, device=self.device)
+        self.order()
+        capi.check(self.L.gys_hist_rollup_level_dev(self.h, scope, level, int(tusec), C.c_void_p(recs.data_ptr())))
+        self.sync()
+        out = recs[:n].cpu().numpy()
+        return out if pcts is None else (out, self._group_percentiles(recs, n, pcts))
+
+    def hist_rollup_filtered(self, group_by=0, level=3, tusec=0, terms=None, group_oper=(), top_oper="and", machine_ids=None, svcids=None, clusters=None,
+                             any_state=False, maxrows=None, pcts=None):
+        """gys_hist_rollup_filtered_dev -> (rows [(group, nmembers)] of the groups written, nrows there are, records [rows][16][2] int64); with
+        pcts=(...) a fourth element: the rows' percentiles (rows, len(pcts)) int64"""
+        f, keep = self._svc_filter(terms, group_oper, top_oper, machine_ids, svcids, clusters)
+        if maxrows is None:
+            maxrows = {capi.GROUP_NONE: 1, capi.GROUP_HOST: self.L.gys_num_hosts(self.h), capi.GROUP_CLUSTER: self.L.gys_num_clusters(self.h)}.get(
+                group_by, min(getattr(self, "_label_domain", 0), self.num_services()))
+        cap = max(maxrows, 1)
+        recs = self.torch.zeros((cap, 16, 2), dtype=self.torch.int64, device=self.device)
+        rows = (capi.RollupRow * cap)()
+        n = C.c_uint32()
+        self.order()
+        capi.check(self.L.gys_hist_rollup_filtered_dev(self.h, C.byref(f), capi.RF_ANY_STATE if any_state else 0, group_by, level, int(tusec), rows, maxrows,
+                                                       C.byref(n), C.c_void_p(recs.data_ptr())))
+        self.sync()
+        nr = min(n.value, maxrows)
+        res = ([(rows[i].group, rows[i].nmembers) for i in range(nr)], n.value, recs[:nr].cpu().numpy())
+        return res if pcts is None else res + (self._group_percentiles(recs, nr, pcts),)
+
     def json_clusterstate(self, shyamaid="0" * 16, timestr=""):
         return self._json(self.L.gys_json_clusterstate, shyamaid.encode(), timestr.encode())
 

@@ -700,6 +700,36 @@ enum { GYS_GROUP_NONE = 0, GYS_GROUP_HOST = 1, GYS_GROUP_CLUSTER = 2, GYS_GROUP_
 int gys_rollup_filtered_dev(gys_ctx *ctx, const gys_svc_filter *filter, uint32_t flags, int group_by, int hll_level, uint64_t tusec,
 			    gys_rollup_row *rows, uint32_t maxrows, uint32_t *nrows, gys_tdigest_slab *d_slabs, uint8_t *d_regs, double *d_est);
 
+/* -------------------------------------------------------------------------------------------------------------------
+ * Group response-time histograms of the CLOSED windows for the four levels (gys_config.enable_levels; GYS_ERR_STATE when it is 0, and for
+ * level 0 when it is 2; level 0 .. 3 as for gys_query_hist_level_stats, GYS_ERR_INVAL otherwise): "p95 / p99 of this host, this cluster,
+ * this set of services over the last 5 s / 5 min / 5 days / since the start".  The roll-up digests above are since-start only (a t-digest
+ * cannot be subtracted); the exact GY_HISTOGRAM records exist per service at every level, and this is their sum per group.
+ *   DEFINITION.  The record of a group at (level, tusec) = GY_HISTOGRAM::add_histogram (common/gy_statistics.h:625-660) of its members'
+ *   records exactly as gys_export_hist_level returns them for the same level and tusec: per bucket count += count and sum += sum,
+ *   total_count += total_count, max_val_seen = the larger (at every level the all-time maximum, as there).  A group without a member has the
+ *   record gys_hist_init_dev leaves: all zero, max_val_seen = INT64_MIN.  Time handling is that of the level records: tq = max(tusec / 10^6,
+ *   the last close), never the open window.
+ *   PERCENTILES of the group records: gys_hist_percentiles_dev(GYS_RESP_TIME_HASH, d_out, ngroups, ...) -- the reference's get_percentiles
+ *   (common/gy_statistics.h:707-791) on the summed record; no percentile code of its own.
+ *   BIT-EXACT and order-free: the adds are 64-bit integer adds (they commute and associate mod 2^64) and a maximum, so every path gives the
+ *   same bits -- any member order, services -> hosts -> cluster as well as services -> cluster directly, the fixed scopes as well as an
+ *   all-selecting filtered call grouped by host or cluster.
+ *   No per-service level records are materialised (the members' level views are worked out in registers); scratch kept by the context: one
+ *   record per chunk of 1024 members plus one per host.  No engine state a query can see is modified; concurrency as the other query calls;
+ *   asynchronous: the device outputs follow in stream order (gys_sync).
+ *   ACROSS RANKS there is no collective of its own: every rank runs the call, the caller all-gathers its records and adds the records of one
+ *   group with gys_hist_merge_dev. */
+/* one record per host slot (gys_num_hosts) / registered cluster (gys_num_clusters) / one, of `level` (0..3) at tusec, into d_out (DEVICE):
+ * the sum of the members' records as gys_export_hist_level returns them at the same tusec.  Scopes as gys_tdigest_rollup_dev; works with
+ * enable_tdigest = 0 and svc_hll_p = 0 too.  GYS_ERR_INVAL for an unknown scope or level or a NULL d_out */
+int gys_hist_rollup_level_dev(gys_ctx *ctx, int scope, int level, uint64_t tusec, gys_hist_rec *d_out);
+/* the same for the services a filter selects, per group: members, groups, rows, maxrows / *nrows rules exactly those of
+ * gys_rollup_filtered_dev; row r owns d_recs[r] (DEVICE, maxrows records).  Without services, or with a label domain of 0: GYS_OK and
+ * *nrows = 0.  GYS_ERR_INVAL for an unknown group_by / flags / level or NULL filter / rows / nrows / d_recs */
+int gys_hist_rollup_filtered_dev(gys_ctx *ctx, const gys_svc_filter *filter, uint32_t flags, int group_by, int level, uint64_t tusec,
+				 gys_rollup_row *rows, uint32_t maxrows, uint32_t *nrows, gys_hist_rec *d_recs);
+
 /* The per-listener 5-second scan from the engine's OWN state (needs gys_config.enable_levels): replaces the loop of
  * TCP_SOCK_HANDLER::listener_stats_update (common/gy_socket_stat.cc:4044-4365) that turns every listener's counters and histograms into
  * one comm::LISTENER_STATE_NOTIFY (common/gy_comm_proto.h:2183-2254), and the data-parallel part of TCP_LISTENER::get_curr_state
