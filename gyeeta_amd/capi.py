@@ -163,6 +163,11 @@ SIGNATURES = {
     "gys_register_cluster": (C.c_int, [vp, C.c_char_p, u32p]),
     "gys_register_host": (C.c_int, [vp, mid, C.c_char_p, u32p]),
     "gys_register_listeners": (C.c_int, [vp, mid, C.POINTER(ListenerInfo), C.c_uint32, u32p]),
+    "gys_delete_listeners": (C.c_int, [vp, u64p, C.c_uint32, u32p]),
+    "gys_register_listeners_slots": (C.c_int, [vp, mid, C.POINTER(ListenerInfo), C.c_uint32, u32p]),
+    "gys_num_free_slots": (C.c_uint32, [vp]),
+    "gys_svc_state_bytes": (C.c_uint64, [vp]),
+    "gys_list_stale_listeners": (C.c_int, [vp, C.c_uint32, C.c_uint32, u64p, C.c_uint32, u32p]),
     "gys_ingest_resp_events": (C.c_int, [vp, mid, vp, C.c_uint32]),
     "gys_ingest_resp_events_dev": (C.c_int, [vp, C.POINTER(RespSeg), C.c_uint32, vp, C.c_uint64]),
     "gys_ingest_resp_events_v6": (C.c_int, [vp, mid, C.c_char_p, C.c_uint32]),

@@ -15,6 +15,7 @@
 #include <cstring>
 #include <deque>
 #include <map>
+#include <set>
 #include <string>
 #include <thread>
 #include <condition_variable>
@@ -33,6 +34,7 @@
 #include "gys_huge.hpp"
 #include "gys_svcquery.hpp"
 #include "gys_rollsel.hpp"
+#include "gys_svcdel.hpp"
 
 using namespace gys;
 
@@ -182,7 +184,17 @@ struct gys_ctx {
 	std::unordered_map<std::string, uint32_t> cluster_map;
 	std::vector<std::string> cluster_names;
 	std::unordered_map<uint64_t, uint32_t> gid_map_h; // glob_id -> slot (host mirror for single-key queries)
-	uint32_t nsvc = 0;
+	uint32_t nsvc = 0; // high-water mark of the slots handed out: [0, nsvc) are registered or free
+	// deleted listeners (gys_svcdel.hpp): the slots gys_delete_listeners gave back, lowest first, and per slot the host (GYS_NOSLOT: free)
+	// and the (netns:32|port:16) key it was registered under
+	std::set<uint32_t> free_slots;
+	std::vector<uint32_t> svc_host_h;
+	std::vector<uint64_t> svc_key_h;
+	SvcClearSeg *clr_segs = nullptr;     // k_svc_clear's segment list (rebuilt per call: hist_win and lvl_last change places)
+	unsigned long long *stale_bits = nullptr; // gys_list_stale_listeners scratch (grows)
+	uint32_t *stale_tiles = nullptr;
+	uint64_t *stale_ids = nullptr;
+	uint64_t stale_tiles_cap = 0, stale_ids_cap = 0;
 	std::vector<HostListeners> host_lst;
 	std::vector<uint32_t> host_seen; // batch stamp per host (duplicate-host detection in a multi-segment batch)
 	uint32_t batch_stamp = 0;
@@ -842,9 +854,39 @@ void host_rebind_local(HostListeners &hl, uint64_t key48, uint32_t slot, uint32_
 		}
 }
 
-int host_lst_add(gys_ctx *c, uint32_t host, const gys_listener_info *arr, uint32_t n, uint32_t first_slot)
+// after the host's mirror changed: rebuilds what a changed chain invalidated (tables, candidate records, the global table's entries of the
+// keys with candidates) and uploads the sub-tables
+int host_lst_flush(gys_ctx *c, uint32_t host)
 {
 	HostListeners &hl = c->host_lst[host];
+	if (hl.dirty) {
+		host_rebuild(hl);
+		const int rc = host_cands_upload(c, hl);
+		if (rc) return rc;
+		// the global table (general pipeline): a key with candidates points at its chain's records
+		std::vector<uint64_t> kv;
+		for (const auto &cf : hl.cand_first) {
+			kv.push_back(listener_key(host, (uint32_t)(cf.first >> 16), (uint16_t)(cf.first & 0xFFFFu)));
+			kv.push_back((uint64_t)(GYS_SLOT_GROUP | (hl.cand_off + cf.second)));
+		}
+		if (!kv.empty()) {
+			const uint32_t nk = (uint32_t)(kv.size() / 2);
+			const int rs = ensure_staging(c, kv.size() * 8, 0);
+			if (rs) return rs;
+			HIPCHK(hipMemcpyAsync(c->dev_staging, kv.data(), kv.size() * 8, hipMemcpyHostToDevice, c->stream));
+			hipLaunchKernelGGL(k_table_set, dim3((nk + 255) / 256), dim3(256), 0, c->stream, c->lk_tbl, (const uint64_t *)c->dev_staging, nk);
+			HIPCHK(hipStreamSynchronize(c->stream));
+		}
+	}
+	return host_lst_upload(c, host);
+}
+
+// slotv: the slot of arr[i] (gys_register_listeners_slots), or nullptr: first_slot + i
+int host_lst_add(gys_ctx *c, uint32_t host, const gys_listener_info *arr, uint32_t n, uint32_t first_slot, const uint32_t *slotv = nullptr)
+{
+	HostListeners &hl = c->host_lst[host];
+	// (a flush that failed after gys_delete_listeners compacted keys / slots left the tables behind the locals: the lookups below need them)
+	if (hl.dirty) host_rebuild(hl);
 	auto new_local = [&](uint64_t key48, uint32_t slot) { // false: the host left the LDS path
 		if (hl.overflow) return false;
 		HostListeners *t = hl.sub.empty() ? &hl : &hl.sub[host_part_of(key48, (uint32_t)hl.sub.size())];
@@ -868,7 +910,7 @@ int host_lst_add(gys_ctx *c, uint32_t host, const gys_listener_info *arr, uint32
 	};
 	for (uint32_t i = 0; i < n; ++i) {
 		const uint64_t key48 = host_key48(arr[i].netns, arr[i].port);
-		const uint32_t slot = first_slot + i;
+		const uint32_t slot = slotv ? slotv[i] : first_slot + i;
 		const HostListeners::LAddr a = listener_addr(arr[i]);
 		auto ch = hl.chain.find(key48);
 		if (ch != hl.chain.end()) {
@@ -919,26 +961,7 @@ int host_lst_add(gys_ctx *c, uint32_t host, const gys_listener_info *arr, uint32
 			hl.dirty = true;
 		}
 	}
-	if (hl.dirty) {
-		host_rebuild(hl);
-		const int rc = host_cands_upload(c, hl);
-		if (rc) return rc;
-		// the global table (general pipeline): a key with candidates points at its chain's records
-		std::vector<uint64_t> kv;
-		for (const auto &cf : hl.cand_first) {
-			kv.push_back(listener_key(host, (uint32_t)(cf.first >> 16), (uint16_t)(cf.first & 0xFFFFu)));
-			kv.push_back((uint64_t)(GYS_SLOT_GROUP | (hl.cand_off + cf.second)));
-		}
-		if (!kv.empty()) {
-			const uint32_t nk = (uint32_t)(kv.size() / 2);
-			const int rs = ensure_staging(c, kv.size() * 8, 0);
-			if (rs) return rs;
-			HIPCHK(hipMemcpyAsync(c->dev_staging, kv.data(), kv.size() * 8, hipMemcpyHostToDevice, c->stream));
-			hipLaunchKernelGGL(k_table_set, dim3((nk + 255) / 256), dim3(256), 0, c->stream, c->lk_tbl, (const uint64_t *)c->dev_staging, nk);
-			HIPCHK(hipStreamSynchronize(c->stream));
-		}
-	}
-	return host_lst_upload(c, host);
+	return host_lst_flush(c, host);
 }
 
 inline DigestP digest_params(gys_ctx *c)
@@ -2551,7 +2574,7 @@ void gys_destroy(gys_ctx *c)
 			c->batch_cnt, c->batch_off, c->scan_block_sums, c->ev_kv, c->staged, c->huge_scratch, c->huge_acc, c->huge_tail, c->huge_tb_list, c->huge_bm, c->huge_chunk_off, c->huge_fb_list, c->hll32, c->svc_ctr, c->svc_win, c->svc_state, c->svc_claim, c->svc_hll, c->host_summ_win, c->host_summ_last, c->host_state,
 			c->host_state_epoch, c->host_cluster, c->counters, c->misc, c->htbl, c->hlst, c->hdesc, c->wire_jump[0], c->wire_jump[1], c->wire_cnt,
 			c->wire_rank, c->wire_bsums, c->wire_status, c->wire_mark, c->wire_flags, c->wire_msgs, c->last, c->last_act32, c->last_act64, c->ring_act32, c->ring_act64, c->act_live, c->q_cand_key, c->q_out_keys, c->q_cand_slot, c->q_misc, c->q_host_mask, c->q_slot_list, c->q_set, c->q_out_rows, c->q_acc, c->q_cnt, c->dev_staging, c->dev_offsets, c->csr_off, c->csr_mem, c->svc_act, c->d_epoch, c->topn_slot,
-			c->topn_metric, c->dev_pcts, c->zipf_cdf, c->lvl_snap, c->lvl_last, c->lvl_last_tag, c->svc_bithist, c->rb_bins, c->rb_host_members, c->rb_host_chunks, c->rb_host_gchunks, c->hl_cl_members, c->hl_cl_chunks, c->hl_cl_gchunks, c->hl_buf, c->hr_buf, c->hl_lvl, c->hl_view, c->svc_label, c->rs_item_group, c->rs_counts, c->rs_members, c->rs_tiles, c->rs_tot, c->rs_chunks, c->rs_gchunks, c->rs_rows, c->rs_rowoff, c->lvl_first, c->qps_hist, c->act_hist, c->cand_pool, c->own_arena ? c->arena : nullptr};
+			c->topn_metric, c->dev_pcts, c->zipf_cdf, c->lvl_snap, c->lvl_last, c->lvl_last_tag, c->svc_bithist, c->rb_bins, c->rb_host_members, c->rb_host_chunks, c->rb_host_gchunks, c->hl_cl_members, c->hl_cl_chunks, c->hl_cl_gchunks, c->hl_buf, c->hr_buf, c->hl_lvl, c->hl_view, c->svc_label, c->rs_item_group, c->rs_counts, c->rs_members, c->rs_tiles, c->rs_tot, c->rs_chunks, c->rs_gchunks, c->rs_rows, c->rs_rowoff, c->lvl_first, c->qps_hist, c->act_hist, c->cand_pool, c->clr_segs, c->stale_bits, c->stale_tiles, c->stale_ids, c->own_arena ? c->arena : nullptr};
 	for (void *p : ptrs)
 		if (p) hipFree(p);
 	if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
@@ -2691,8 +2714,364 @@ try {
 		c->svc_comm.push_back(cm);
 		c->svc_gid_h.push_back(arr[i].glob_id);
 		c->svc_port_h.push_back(arr[i].port);
+		c->svc_host_h.push_back(host);
+		c->svc_key_h.push_back(host_key48(arr[i].netns, arr[i].port));
 	}
 	c->nsvc += n;
+	return GYS_OK;
+} GYS_CATCH_ALL
+
+// ------------------------------------------------------------------------------------------------ deleting listeners (gys_svcdel.hpp)
+// every per-service array of the context as k_svc_clear segments, with the contents gys_create leaves
+static void svc_clear_segments(gys_ctx *c, std::vector<SvcClearSeg> &segs)
+{
+	const uint64_t S = c->cfg.max_services;
+	const uint4 zero = make_uint4(0u, 0u, 0u, 0u), ones = make_uint4(~0u, ~0u, ~0u, ~0u);
+	auto add = [&](void *base, uint64_t bytes, uint4 fill, uint4 last) {
+		if (base) segs.push_back(SvcClearSeg{(uint8_t *)base, bytes, fill, last});
+	};
+	auto hist = [&](gys_hist_rec *base, int64_t minval) { // zero, max_val_seen (the record's last 8 bytes) = minval
+		add(base, sizeof(gys_hist_rec), zero, make_uint4(0u, 0u, (uint32_t)(uint64_t)minval, (uint32_t)((uint64_t)minval >> 32)));
+	};
+	add(c->svc_gid, 8, zero, zero);
+	add(c->svc_host, 4, ones, ones);
+	hist(c->hist_win, INT64_MIN);
+	hist(c->hist_all, INT64_MIN);
+	add(c->bitmap, GYS_BM_WORDS * 4, zero, zero);
+	add(c->svc_ctr, 32, zero, zero);
+	add(c->svc_win, 24, zero, zero);
+	add(c->svc_state, 96, zero, zero);
+	add(c->svc_claim, 8, zero, zero);
+	add(c->svc_act, 32, zero, zero);
+	if (c->svc_hll) add(c->svc_hll, 1ull << c->cfg.svc_hll_p, zero, zero);
+	if (c->hl_lvl)
+		for (uint32_t f = 0; f < GYS_HLL_LVL_FILES; ++f) add(hll_level_array(c, f), 1ull << c->cfg.svc_hll_p, zero, zero);
+	if (c->cfg.enable_levels) {
+		for (uint32_t j = 0; j < 2 * GYS_LEVEL_RING; ++j) add(c->lvl_snap + (uint64_t)j * S, sizeof(gys_hist_rec), zero, zero);
+		if (c->cfg.enable_levels == 1) hist(c->lvl_last, INT64_MIN);
+		if (c->cfg.enable_levels == 1 && c->cfg.enable_tdigest) add(c->lvl_last_tag, 4, ones, ones);
+		add(c->lvl_first, 8, zero, zero);
+		hist(c->qps_hist, INT32_MIN);
+		hist(c->act_hist, INT32_MIN);
+	}
+	if (c->cfg.enable_tdigest) {
+		add(c->td_sum, GYS_TD_NB * 8ull, zero, zero);
+		add(c->td_cnt, GYS_TD_NB * 4ull, zero, zero);
+		add(c->td_meta, sizeof(TdMeta), zero, zero);
+		const uint4 mm = make_uint4((uint32_t)INT32_MAX, (uint32_t)INT32_MIN, (uint32_t)INT32_MAX, (uint32_t)INT32_MIN);
+		add(c->td_minmax, 8, mm, mm);
+		add(c->td_cur, 4, zero, zero); // (the words of td_pend behind a zero cursor are never read)
+		add(c->td_run, 4, zero, zero);
+		add(c->td_run0, 4, zero, zero);
+		add(c->td_run1, 4, zero, zero);
+		add(c->td_prevm, 4, zero, zero);
+		add(c->resp_win, 4, zero, zero);
+	}
+	add(c->svc_label, 4, ones, ones); // GYS_NO_GROUP
+	add(c->svc_bithist, 2, zero, zero);
+}
+
+// the segment list and the device memory a clear of listed slots needs (staging_bytes: what the caller puts into dev_staging)
+static int svc_clear_prepare(gys_ctx *c, std::vector<SvcClearSeg> &segs, uint64_t staging_bytes)
+{
+	svc_clear_segments(c, segs);
+	if (segs.size() > GYS_SVCCLEAR_MAXSEG) {
+		set_err("internal error: %zu clear segments", segs.size());
+		return GYS_ERR_INTERNAL;
+	}
+	if (!c->clr_segs) HIPCHK(hipMalloc((void **)&c->clr_segs, GYS_SVCCLEAR_MAXSEG * sizeof(SvcClearSeg)));
+	return ensure_staging(c, staging_bytes, 0);
+}
+// d_slots: nslots slot numbers on the device.  segs has to stay alive until the stream has been synchronised.
+static int svc_clear_launch(gys_ctx *c, const std::vector<SvcClearSeg> &segs, const uint32_t *d_slots, uint32_t nslots)
+{
+	HIPCHK(hipMemcpyAsync(c->clr_segs, segs.data(), segs.size() * sizeof(SvcClearSeg), hipMemcpyHostToDevice, c->stream));
+	ProfScope ps(c, "svc_clear");
+	hipLaunchKernelGGL(k_svc_clear, dim3(std::min<uint32_t>(nslots, (uint32_t)c->ncu * 8u)), dim3(GYS_SVCCLEAR_NT), 0, c->stream, c->clr_segs, (uint32_t)segs.size(), d_slots,
+			   nslots, c->cfg.max_services);
+	HIPCHK(hipGetLastError());
+	return GYS_OK;
+}
+
+int gys_delete_listeners(gys_ctx *c, const uint64_t *glob_ids, uint32_t n, uint32_t *ndeleted)
+try {
+	GYS_ENTER(c); // whatever was ingested before the call is applied to the services before they go
+	if (!c || (!glob_ids && n)) return GYS_ERR_INVAL;
+	if (ndeleted) *ndeleted = 0;
+	// every id is looked up before anything changes; unknown ids and repeats are not counted
+	std::vector<uint32_t> del;
+	{
+		std::unordered_set<uint32_t> seen;
+		for (uint32_t i = 0; i < n; ++i) {
+			auto it = c->gid_map_h.find(glob_ids[i]);
+			if (it != c->gid_map_h.end() && seen.insert(it->second).second) del.push_back(it->second);
+		}
+	}
+	if (del.empty()) return GYS_OK;
+	const uint32_t nd = (uint32_t)del.size();
+	// ---- whatever can fail for want of memory comes first (at most one lk_tbl key per deleted listener), before the mirror changes
+	std::vector<SvcClearSeg> segs;
+	int rc = svc_clear_prepare(c, segs, 2ull * nd * 8 + (uint64_t)nd * 4);
+	if (rc) return rc;
+	// ---- host mirror: the listeners leave their hosts' chains, sub-tables and all_slots; lk_gone = the global-table keys that lose their last listener
+	std::unordered_map<uint32_t, std::unordered_set<uint32_t>> by_host;
+	for (uint32_t s : del) by_host[c->svc_host_h[s]].insert(s);
+	// the touched hosts' mirrors as they were: an error before the device work is done puts them back, so that mirror and device never disagree
+	struct MirrorUndo {
+		gys_ctx *c;
+		std::vector<std::pair<uint32_t, HostListeners>> was;
+		bool armed = true;
+		~MirrorUndo()
+		{
+			if (armed)
+				for (auto &w : was) c->host_lst[w.first] = std::move(w.second);
+		}
+	} undo{c};
+	undo.was.reserve(by_host.size());
+	for (auto &hv : by_host) undo.was.emplace_back(hv.first, c->host_lst[hv.first]);
+	std::vector<uint64_t> keys; // [gid_tbl keys: nd][lk_tbl keys]
+	for (uint32_t s : del) keys.push_back(c->svc_gid_h[s]);
+	for (auto &hv : by_host) {
+		const uint32_t host = hv.first;
+		const std::unordered_set<uint32_t> &dead = hv.second;
+		HostListeners &hl = c->host_lst[host];
+		std::unordered_set<uint64_t> touched; // keys a deleted listener was registered under
+		for (uint32_t s : dead) {
+			const uint64_t key48 = c->svc_key_h[s];
+			touched.insert(key48);
+			auto ch = hl.chain.find(key48);
+			if (ch != hl.chain.end()) {
+				auto &v = ch->second;
+				v.erase(std::remove_if(v.begin(), v.end(), [&](const HostListeners::ChainEnt &e) { return e.slot == s; }), v.end());
+				if (v.empty()) hl.chain.erase(ch);
+			}
+			auto ok = hl.okey.find(key48);
+			if (ok != hl.okey.end() && ok->second == s) hl.okey.erase(ok);
+		}
+		hl.all_slots.erase(std::remove_if(hl.all_slots.begin(), hl.all_slots.end(), [&](uint32_t s) { return dead.count(s) != 0; }), hl.all_slots.end());
+		std::unordered_set<uint64_t> live; // touched keys that still have a listener bound
+		if (hl.overflow) {
+			for (uint64_t k : touched)
+				if (hl.chain.count(k) || hl.okey.count(k)) live.insert(k);
+		} else {
+			// the locals (key, slot) of the deleted listeners go; the survivors close up and the tables are rebuilt from them, hole-free
+			auto compact = [&](HostListeners &t) {
+				size_t w = 0;
+				for (size_t l = 0; l < t.slots.size(); ++l) {
+					if (dead.count(t.slots[l])) continue;
+					if (touched.count(t.keys[l])) live.insert(t.keys[l]);
+					t.slots[w] = t.slots[l];
+					t.keys[w] = t.keys[l];
+					++w;
+				}
+				t.slots.resize(w);
+				t.keys.resize(w);
+			};
+			if (hl.sub.empty()) compact(hl);
+			else for (HostListeners &t : hl.sub) compact(t);
+		}
+		for (uint64_t k : touched)
+			if (!live.count(k)) keys.push_back(listener_key(host, (uint32_t)(k >> 16), (uint16_t)(k & 0xFFFFu)));
+		hl.dirty = true;
+	}
+	// ---- device: the keys leave the tables, the hosts' sub-tables are rebuilt, the slots are cleared -- all behind the drained queues
+	const uint32_t nlk = (uint32_t)keys.size() - nd;
+	const uint64_t keys_bytes = keys.size() * 8;
+	HIPCHK(hipMemcpyAsync(c->dev_staging, keys.data(), keys_bytes, hipMemcpyHostToDevice, c->stream));
+	HIPCHK(hipMemcpyAsync(c->dev_staging + keys_bytes, del.data(), (size_t)nd * 4, hipMemcpyHostToDevice, c->stream));
+	{
+		ProfScope ps(c, "table_erase");
+		hipLaunchKernelGGL(k_table_erase, dim3(1), dim3(64), 0, c->stream, c->gid_tbl, (const uint64_t *)c->dev_staging, nd, (uint32_t *)nullptr);
+		if (nlk) hipLaunchKernelGGL(k_table_erase, dim3(1), dim3(64), 0, c->stream, c->lk_tbl, (const uint64_t *)c->dev_staging + nd, nlk, (uint32_t *)nullptr);
+	}
+	rc = svc_clear_launch(c, segs, (const uint32_t *)(c->dev_staging + keys_bytes), nd);
+	if (rc) return rc;
+	HIPCHK(hipStreamSynchronize(c->stream)); // (keys / del / segs are locals; the staging buffer is reused by host_lst_flush)
+	undo.armed = false; // the device has let the listeners go: the mirror follows
+	for (uint32_t s : del) {
+		c->gid_map_h.erase(c->svc_gid_h[s]);
+		c->svc_gid_h[s] = 0;
+		c->svc_comm[s] = std::array<char, 16>{};
+		c->svc_port_h[s] = 0;
+		c->svc_host_h[s] = GYS_NOSLOT;
+		c->svc_key_h[s] = 0;
+		c->free_slots.insert(s);
+	}
+	c->csr_stamp = ~0ull; // the hosts' member lists are rebuilt, as after a registration
+	c->rb_host_nsvc = ~0u;
+	if (ndeleted) *ndeleted = nd;
+	{
+		// (a host whose upload fails here stays marked dirty: host_lst_add and the next delete rebuild its tables from the mirror first)
+		ProfScope ps(c, "host_rebuild");
+		for (auto &hv : by_host) {
+			rc = host_lst_flush(c, hv.first);
+			if (rc) return rc;
+		}
+	}
+	return GYS_OK;
+} GYS_CATCH_ALL
+
+int gys_register_listeners_slots(gys_ctx *c, const uint8_t machine_id[16], const gys_listener_info *arr_in, uint32_t n_in, uint32_t *slots)
+try {
+	GYS_ENTER(c);
+	if (!c || !machine_id || (!arr_in && n_in)) return GYS_ERR_INVAL;
+	uint32_t host;
+	int rc = lookup_host(c, machine_id, &host);
+	if (rc) return rc;
+	// known ids keep their slot, repeats inside the call share the first one's
+	std::vector<gys_listener_info> fresh;
+	std::vector<uint32_t> fresh_of(n_in, GYS_NOSLOT); // arr_in index -> index in fresh (new ids)
+	{
+		std::unordered_map<uint64_t, uint32_t> seen;
+		for (uint32_t i = 0; i < n_in; ++i) {
+			if (arr_in[i].glob_id == GYS_EMPTY_KEY) {
+				set_err("glob_id ~0 is reserved");
+				return GYS_ERR_INVAL;
+			}
+			if (c->gid_map_h.count(arr_in[i].glob_id)) continue;
+			auto ins = seen.emplace(arr_in[i].glob_id, (uint32_t)fresh.size());
+			if (ins.second) fresh.push_back(arr_in[i]);
+			fresh_of[i] = ins.first->second;
+		}
+	}
+	const uint32_t n = (uint32_t)fresh.size();
+	const uint32_t nfree = (uint32_t)std::min<size_t>(n, c->free_slots.size()), ntail = n - nfree;
+	if ((uint64_t)c->nsvc + ntail > c->cfg.max_services) {
+		set_err("max_services exhausted (%zu free slots)", c->free_slots.size());
+		return GYS_ERR_NOMEM;
+	}
+	std::vector<uint32_t> sl(n);
+	{
+		auto it = c->free_slots.begin();
+		for (uint32_t i = 0; i < nfree; ++i, ++it) sl[i] = *it; // lowest slot number first
+		for (uint32_t i = 0; i < ntail; ++i) sl[nfree + i] = c->nsvc + i;
+	}
+	if (n) {
+		const gys_listener_info *arr = fresh.data();
+		std::vector<uint64_t> keys(2 * (size_t)n);
+		for (uint32_t i = 0; i < n; ++i) {
+			keys[i] = arr[i].glob_id;
+			keys[n + i] = listener_key(host, arr[i].netns, arr[i].port);
+		}
+		const uint64_t keys_bytes = keys.size() * 8;
+		std::vector<SvcClearSeg> segs;
+		rc = nfree ? svc_clear_prepare(c, segs, keys_bytes + (uint64_t)n * 4) : ensure_staging(c, keys_bytes + (uint64_t)n * 4, 0);
+		if (rc) return rc;
+		const uint64_t *d_keys = (const uint64_t *)c->dev_staging;
+		const uint32_t *d_sl = (const uint32_t *)(c->dev_staging + keys_bytes);
+		HIPCHK(hipMemcpyAsync(c->dev_staging, keys.data(), keys_bytes, hipMemcpyHostToDevice, c->stream));
+		HIPCHK(hipMemcpyAsync(c->dev_staging + keys_bytes, sl.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+		HIPCHK(hipMemsetAsync(c->misc, 0, 4, c->stream));
+		// A free slot is part of every pass over [0, nsvc): a window close that went by while it was free wrote for it what it writes for a
+		// registered service without data (the first-close time of the since-start period, the level-0 tag, snapshots).  The slot is handed
+		// out as gys_create left it -- a listener's series starts at ITS first close, like a tail slot's -- so it is cleared once more here.
+		if (nfree) {
+			rc = svc_clear_launch(c, segs, d_sl, nfree); // (sl[0 .. nfree) are the reused slots)
+			if (rc) return rc;
+		}
+		const dim3 grid((n + 255) / 256), block(256);
+		hipLaunchKernelGGL(k_scatter_u64, grid, block, 0, c->stream, c->svc_gid, d_sl, d_keys, n);
+		hipLaunchKernelGGL(k_table_insert_vals, grid, block, 0, c->stream, c->gid_tbl, d_keys, d_sl, n, c->misc);
+		hipLaunchKernelGGL(k_table_insert_vals, grid, block, 0, c->stream, c->lk_tbl, d_keys + n, d_sl, n, c->misc);
+		hipLaunchKernelGGL(k_scatter_const_u32, grid, block, 0, c->stream, c->svc_host, d_sl, host, n);
+		uint32_t nfail = 0;
+		HIPCHK(hipMemcpyAsync(&nfail, c->misc, 4, hipMemcpyDeviceToHost, c->stream));
+		HIPCHK(hipStreamSynchronize(c->stream));
+		if (nfail) {
+			set_err("key table full (%u inserts failed)", nfail);
+			return GYS_ERR_NOMEM;
+		}
+		rc = host_lst_add(c, host, arr, n, 0, sl.data());
+		if (rc) return rc;
+		const uint32_t top = c->nsvc + ntail;
+		c->svc_comm.resize(top);
+		c->svc_gid_h.resize(top);
+		c->svc_port_h.resize(top);
+		c->svc_host_h.resize(top);
+		c->svc_key_h.resize(top);
+		for (uint32_t i = 0; i < n; ++i) {
+			const uint32_t s = sl[i];
+			c->gid_map_h[arr[i].glob_id] = s;
+			c->host_lst[host].all_slots.push_back(s);
+			memcpy(c->svc_comm[s].data(), arr[i].comm, 16);
+			c->svc_gid_h[s] = arr[i].glob_id;
+			c->svc_port_h[s] = arr[i].port;
+			c->svc_host_h[s] = host;
+			c->svc_key_h[s] = host_key48(arr[i].netns, arr[i].port);
+			c->free_slots.erase(s);
+		}
+		c->nsvc = top;
+		c->csr_stamp = ~0ull; // (a reused slot changes the hosts' member lists without changing the service count they are stamped with)
+		c->rb_host_nsvc = ~0u;
+	}
+	if (slots)
+		for (uint32_t i = 0; i < n_in; ++i) slots[i] = fresh_of[i] != GYS_NOSLOT ? sl[fresh_of[i]] : c->gid_map_h[arr_in[i].glob_id];
+	return GYS_OK;
+} GYS_CATCH_ALL
+
+uint32_t gys_num_free_slots(gys_ctx *c) { return c ? (uint32_t)c->free_slots.size() : 0; }
+
+uint64_t gys_svc_state_bytes(gys_ctx *c)
+{
+	if (!c) return 0;
+	std::vector<SvcClearSeg> segs;
+	svc_clear_segments(c, segs);
+	uint64_t b = 0;
+	for (const SvcClearSeg &sg : segs) b += sg.bytes;
+	return b;
+}
+
+int gys_list_stale_listeners(gys_ctx *c, uint32_t flags, uint32_t max_age_windows, uint64_t *glob_ids, uint32_t cap, uint32_t *nfound)
+try {
+	GYS_ENTER(c);
+	if (!c || !nfound || (!glob_ids && cap) || (flags & ~(GYS_STALE_DELETED | GYS_STALE_AGED))) return GYS_ERR_INVAL;
+	*nfound = 0;
+	if (!c->nsvc || !flags) return GYS_OK;
+	SvcStaleP p{};
+	p.svc_state = c->svc_state;
+	p.nsvc = c->nsvc;
+	p.ntiles = (c->nsvc + GYS_STALE_TILE - 1u) / GYS_STALE_TILE;
+	p.epoch = c->epoch;
+	p.flags = flags;
+	p.max_age = max_age_windows;
+	cap = std::min(cap, c->nsvc); // (there are no more hits than services: a caller's "everything" does not size the id buffer)
+	p.cap = cap;
+	if (c->stale_tiles_cap < p.ntiles) {
+		HIPCHK(hipStreamSynchronize(c->stream));
+		if (c->stale_bits) HIPCHK(hipFree(c->stale_bits));
+		if (c->stale_tiles) HIPCHK(hipFree(c->stale_tiles));
+		c->stale_bits = nullptr;
+		c->stale_tiles = nullptr;
+		c->stale_tiles_cap = 0;
+		const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(2ull * p.ntiles, 64), ((uint64_t)c->cfg.max_services + GYS_STALE_TILE - 1u) / GYS_STALE_TILE);
+		HIPCHK(hipMalloc((void **)&c->stale_bits, want * 16 * 8));
+		HIPCHK(hipMalloc((void **)&c->stale_tiles, (want + 1) * 4));
+		c->stale_tiles_cap = want;
+	}
+	if (c->stale_ids_cap < cap) {
+		HIPCHK(hipStreamSynchronize(c->stream));
+		if (c->stale_ids) HIPCHK(hipFree(c->stale_ids));
+		c->stale_ids = nullptr;
+		c->stale_ids_cap = 0;
+		HIPCHK(hipMalloc((void **)&c->stale_ids, (uint64_t)cap * 8));
+		c->stale_ids_cap = cap;
+	}
+	p.bits = c->stale_bits;
+	p.tile_cnt = c->stale_tiles;
+	p.ids = c->stale_ids;
+	{
+		ProfScope ps(c, "svc_stale");
+		hipLaunchKernelGGL(k_svc_stale_mark, dim3(std::min<uint32_t>(p.ntiles, (uint32_t)c->ncu * 8u)), dim3(GYS_STALE_NT), 0, c->stream, p);
+		hipLaunchKernelGGL(k_svc_stale_scan, dim3(1), dim3(GYS_STALE_NT), 0, c->stream, p);
+		if (cap) hipLaunchKernelGGL(k_svc_stale_emit, dim3(grid_for((uint64_t)p.ntiles * 16, GYS_STALE_NT, (uint32_t)c->ncu * 8)), dim3(GYS_STALE_NT), 0, c->stream, p);
+	}
+	HIPCHK(hipGetLastError());
+	uint32_t total = 0;
+	HIPCHK(hipMemcpyAsync(&total, c->stale_tiles + p.ntiles, 4, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	const uint32_t nw = std::min(total, cap);
+	if (nw) HIPCHK(hipMemcpy(glob_ids, c->stale_ids, (size_t)nw * 8, hipMemcpyDeviceToHost));
+	*nfound = total;
 	return GYS_OK;
 } GYS_CATCH_ALL
 

@@ -30,6 +30,7 @@
 #include <shared_mutex>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "../../include/gysketch.h"
 
@@ -68,6 +69,47 @@ public:
 	{
 		std::unique_lock<std::shared_mutex> g(mu_);
 		return gys_register_listeners(ctx_, machine_id, arr, n, nullptr) == GYS_OK;
+	}
+
+	// NOTIFY_NEW_LISTENER for a long-running process: new listeners take the slots deleted ones gave back before the tail
+	bool partha_new_listeners_reuse(const uint8_t machine_id[16], const gys_listener_info *arr, uint32_t n, uint32_t *slots = nullptr) noexcept
+	{
+		std::unique_lock<std::shared_mutex> g(mu_);
+		return gys_register_listeners_slots(ctx_, machine_id, arr, n, slots) == GYS_OK;
+	}
+	// a LISTEN_FLAG_DELETE record's effect in the reference (gy_mconnhdlr.cc:11195-11248): the listeners leave the engine, their slots become free
+	bool delete_listeners(const uint64_t *glob_ids, uint32_t n, uint32_t *ndeleted = nullptr) noexcept
+	{
+		std::unique_lock<std::shared_mutex> g(mu_);
+		return gys_delete_listeners(ctx_, glob_ids, n, ndeleted) == GYS_OK;
+	}
+	// MCONN_HANDLER::cleanup_partha_unused_listeners (gy_mconnhdlr.cc:16284-16343) for every partha at once: the listeners whose state a
+	// delete record marked and those that have not reported for max_age_windows windows (360 x 5 s = the reference's 30 minutes) are listed
+	// by one device pass (at most 65536 per round) and deleted 512 at a time: gys_delete_listeners' table erase is one lane walking the
+	// batch, sized for the hundreds of ids of a delete message.  Returns the number deleted, or -1 on an error.
+	int64_t cleanup_unused_listeners(uint32_t max_age_windows = 360) noexcept
+	{
+		std::unique_lock<std::shared_mutex> g(mu_);
+		int64_t total = 0;
+		try {
+			std::vector<uint64_t> ids(65536);
+			for (;;) {
+				uint32_t nfound = 0, nd = 0;
+				if (gys_list_stale_listeners(ctx_, GYS_STALE_DELETED | GYS_STALE_AGED, max_age_windows, ids.data(), (uint32_t)ids.size(), &nfound) != GYS_OK) return -1;
+				const uint32_t nw = nfound < ids.size() ? nfound : (uint32_t)ids.size();
+				if (!nw) break;
+				for (uint32_t at = 0; at < nw; at += 512u) {
+					uint32_t part = 0;
+					if (gys_delete_listeners(ctx_, ids.data() + at, nw - at < 512u ? nw - at : 512u, &part) != GYS_OK) return -1;
+					nd += part;
+				}
+				total += nd;
+				if (nfound <= ids.size() || !nd) break;
+			}
+		} catch (...) {
+			return -1;
+		}
+		return total;
 	}
 
 	// MCONN_HANDLER::partha_tcp_conn_info: pone points into the L1 receive buffer, valid only during the call

@@ -63,7 +63,7 @@ struct RollSelP {
 };
 
 // the kept record of `slot` whatever its age (GYS_RF_ANY_STATE): all zero if the service never reported; its host is the one it was
-// registered under.  false: the host is not part of the query.
+// registered under.  false: the host is not part of the query, or the slot is free.
 template <typename P>
 __device__ __forceinline__ bool svc_load_any(const P &p, uint32_t slot, uint32_t *w, uint32_t *host_out)
 {
@@ -78,6 +78,7 @@ __device__ __forceinline__ bool svc_load_any(const P &p, uint32_t slot, uint32_t
 	}
 	const uint32_t host = p.svc_host[slot];
 	*host_out = host;
+	if (host == GYS_NOSLOT) return false; // a free slot (gys_delete_listeners): no host, no group
 	if (p.host_mask && !((p.host_mask[host >> 5] >> (host & 31u)) & 1u)) return false;
 	return true;
 }

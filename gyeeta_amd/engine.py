@@ -108,8 +108,9 @@ class SketchEngine:
     def owns(self, machine_id):
         return self.L.gys_shard_of(mid_buf(machine_id), self.nranks) == self.rank
 
-    def register_listeners(self, machine_id, glob_ids, netns, ports, comm=b"svc", addrs=None):
-        """addrs: per listener None (an any-address listener: NEW_LISTENER::is_any_ip_) or the 4 / 16 address bytes it is bound to"""
+    def _listener_infos(self, glob_ids, netns, ports, comm=b"svc", addrs=None):
+        """the gys_listener_info array of a registration call; addrs: per listener None (an any-address listener: NEW_LISTENER::is_any_ip_) or the
+        4 / 16 address bytes it is bound to"""
         n = len(glob_ids)
         arr = (capi.ListenerInfo * n)()
         for i in range(n):
@@ -123,9 +124,46 @@ class SketchEngine:
                 a = bytes(a)
                 arr[i].addr_is_v6 = 1 if len(a) == 16 else 0
                 arr[i].addr = (C.c_uint8 * 16)(*(a + bytes(16))[:16])
+        return arr
+
+    def register_listeners(self, machine_id, glob_ids, netns, ports, comm=b"svc", addrs=None):
+        """addrs: per listener None (an any-address listener: NEW_LISTENER::is_any_ip_) or the 4 / 16 address bytes it is bound to"""
+        arr = self._listener_infos(glob_ids, netns, ports, comm, addrs)
         first = C.c_uint32()
-        capi.check(self.L.gys_register_listeners(self.h, mid_buf(machine_id), arr, n, C.byref(first)))
+        capi.check(self.L.gys_register_listeners(self.h, mid_buf(machine_id), arr, len(glob_ids), C.byref(first)))
         return first.value
+
+    def register_listeners_slots(self, machine_id, glob_ids, netns, ports, comm=b"svc", addrs=None):
+        """gys_register_listeners_slots: new ids take the free slots gys_delete_listeners left (lowest first), then the tail; returns the
+        slot of every listener (numpy u32), new or known"""
+        n = len(glob_ids)
+        arr = self._listener_infos(glob_ids, netns, ports, comm, addrs)
+        slots = np.zeros(max(n, 1), dtype=np.uint32)
+        capi.check(self.L.gys_register_listeners_slots(self.h, mid_buf(machine_id), arr, n, slots.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return slots[:n]
+
+    def delete_listeners(self, glob_ids):
+        """gys_delete_listeners: the services leave the engine and their slots become free; returns how many were known"""
+        ids = np.ascontiguousarray(glob_ids, dtype=np.uint64)
+        nd = C.c_uint32()
+        capi.check(self.L.gys_delete_listeners(self.h, ids.ctypes.data_as(C.POINTER(C.c_uint64)), len(ids), C.byref(nd)))
+        return nd.value
+
+    def num_free_slots(self):
+        return self.L.gys_num_free_slots(self.h)
+
+    def svc_state_bytes(self):
+        """gys_svc_state_bytes: bytes of per-service device state a delete resets per slot"""
+        return self.L.gys_svc_state_bytes(self.h)
+
+    STALE_DELETED, STALE_AGED = 1, 2
+
+    def list_stale_listeners(self, flags=3, max_age_windows=360, cap=1 << 16):
+        """gys_list_stale_listeners: (ids of the first `cap` hits in slot order, number of hits)"""
+        ids = np.zeros(max(cap, 1), dtype=np.uint64)
+        nf = C.c_uint32()
+        capi.check(self.L.gys_list_stale_listeners(self.h, flags, max_age_windows, ids.ctypes.data_as(C.POINTER(C.c_uint64)), cap, C.byref(nf)))
+        return ids[:min(cap, nf.value)].copy(), nf.value
 
     LISTENER_INFO_DT = np.dtype([("glob_id", "<u8"), ("netns", "<u4"), ("port", "<u2"), ("is_any_ip", "u1"), ("addr_is_v6", "u1"), ("comm", "S16"),
                                  ("addr", "u1", (16,))])

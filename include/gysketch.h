@@ -152,8 +152,65 @@ typedef struct {
 
 /* assigns consecutive service slots [*first_slot, *first_slot + n) to the listeners the engine does not know yet.  A glob_id that is
  * already registered (a partha resends its listeners after a reconnect) keeps its slot and all of its state, and repeats inside one call
- * are dropped: with such entries fewer than n slots are assigned (gys_lookup_service gives any listener's slot). */
+ * are dropped: with such entries fewer than n slots are assigned (gys_lookup_service gives any listener's slot).
+ * The slots come from the TAIL only -- [gys_num_services, max_services) -- and never from the free slots gys_delete_listeners left:
+ * GYS_ERR_NOMEM at the tail's end even while free slots exist.  gys_register_listeners_slots takes those. */
 int gys_register_listeners(gys_ctx *ctx, const uint8_t machine_id[16], const gys_listener_info *arr, uint32_t n, uint32_t *first_slot);
+
+/* -------------------------------------------------------------------------------------------------------------------
+ * deleting listeners.  The reference removes a listener from glob_listener_tbl_ and the partha's listen_tbl_ on a LISTENER_STATE_NOTIFY
+ * record flagged LISTEN_FLAG_DELETE (server/gy_mconnhdlr.cc:11195-11248; the agent sends it when the listener goes away,
+ * common/gy_socket_stat.cc:4021-4036) and synthesises such records every cleanup cycle for the listeners whose state is older than 30
+ * minutes (server/gy_mconnhdlr.cc:16296-16343).  The engine's ingest only MARKS the kept state on such a record (its window word becomes 0,
+ * gys_counters.lstate_deleted); the caller removes the service with the calls below -- gys_list_stale_listeners finds the marked and the
+ * aged ones.
+ *
+ * gys_delete_listeners: every id is looked up before anything changes.  An id the engine does not know is neither counted in *ndeleted
+ * (may be NULL) nor an error (the reference's nmissed); repeats inside the call count once.  GYS_ERR_INVAL for glob_ids == NULL with n != 0.
+ * The call first puts whatever the three submission queues hold on the stream (as every call outside the host-pointer ingest does): what
+ * was ingested before it is applied to the service before it goes.  On return -- device work follows in stream order --
+ *   - gys_lookup_service(id) gives GYS_ERR_NOTFOUND; state / connection / active-connection records that name the id count as missed / unknown;
+ *   - a response event for its (netns, port) is dropped (resp_dropped_nolistener) or goes to the next listener of that key by the
+ *     first-match rule above;
+ *   - the service's slot is a FREE SLOT: it belongs to no host (it has left the host's roll-ups, top-N and JSON lists), is in neither key
+ *     table, has no label (GYS_NO_GROUP) and its per-service state is reset to what gys_create leaves -- buffered values, digest, both
+ *     histogram records, bitmap rows, counters, kept state, level snapshots, distinct-count files, QPS / active-connection histograms.
+ *     Every export, scan and window close is still sized by gys_num_services and writes for a free slot what it writes for a registered
+ *     service that never got data (a close that goes by while the slot is free leaves it the first-close time of such a service);
+ *     gys_register_listeners_slots resets a free slot once more when it hands it out, so a reused slot starts like a tail slot;
+ *     gys_scan_listener_state_dev's records of a free slot carry glob_id 0; GYS_RF_ANY_STATE selections skip free slots;
+ *   - the service's part of the OPEN window is discarded with it (its window event count, i.e. its Count-Min share at the close: the
+ *     reference drops the object and its histograms the same way).  What already went into rank-wide registers stays: the global HLL,
+ *     the all-service histogram, host summaries, cluster rows, pair Count-Mins. */
+int gys_delete_listeners(gys_ctx *ctx, const uint64_t *glob_ids, uint32_t n, uint32_t *ndeleted);
+
+/* gys_register_listeners with a slot per listener: slots[i] (may be NULL) = the slot of arr[i], new or known.  The rules are those of
+ * gys_register_listeners (known ids keep their slot, repeats inside the call are dropped and report the first one's slot); new ids, in
+ * array order, take FREE SLOTS first, lowest slot number first, and consecutive tail slots after that.  GYS_ERR_NOMEM only when free
+ * slots and tail together do not suffice; nothing is registered then.  (A key-table insert that fails -- the tables are sized for
+ * max_services at a load of 1/2, so this means a broken table -- also gives GYS_ERR_NOMEM, as in gys_register_listeners; the device side
+ * of the call is then partly done and not undone, and the context should be destroyed.) */
+int gys_register_listeners_slots(gys_ctx *ctx, const uint8_t machine_id[16], const gys_listener_info *arr, uint32_t n, uint32_t *slots);
+
+/* free slots below gys_num_services (which stays the high-water mark every export and scan is sized by) */
+uint32_t gys_num_free_slots(gys_ctx *ctx);
+
+/* bytes of per-service device state in this context's configuration: what a delete resets per slot (the buffered values of the digest,
+ * which need no reset behind a zero cursor, are not counted) */
+uint64_t gys_svc_state_bytes(gys_ctx *ctx);
+
+/* The reference's inactivity walk (server/gy_mconnhdlr.cc:16296-16343) as one device pass over the kept state records, plus the pick-up
+ * of the delete records.  flags:
+ *   GYS_STALE_DELETED  services whose kept record was marked by a LISTEN_FLAG_DELETE record (window word 0 under a non-zero id).  A
+ *                      listener deleted before it ever reported state cannot be told from one that never reported and is NOT listed:
+ *                      the caller has that id from the message itself;
+ *   GYS_STALE_AGED     services whose kept record is older than max_age_windows closed windows: kept in window w with more than
+ *                      max_age_windows windows closed since w opened (360 = the reference's 30 minutes of 5-s windows).
+ * Services that never reported state and free slots are never listed.  *nfound = all hits and may exceed cap; the first `cap` ids in
+ * ascending slot order are written to glob_ids (cap may be any number: the engine's id buffer is sized by min(cap, gys_num_services)).  Nothing is modified: the caller hands the ids to gys_delete_listeners.  Synchronous. */
+#define GYS_STALE_DELETED 1u
+#define GYS_STALE_AGED 2u
+int gys_list_stale_listeners(gys_ctx *ctx, uint32_t flags, uint32_t max_age_windows, uint64_t *glob_ids, uint32_t cap, uint32_t *nfound);
 
 /* -------------------------------------------------------------------------------------------------------------------
  * ingest
