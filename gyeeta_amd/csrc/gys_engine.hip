@@ -29,6 +29,7 @@
 
 #include "gys_kernels.hpp"
 #include "gys_rollup.hpp"
+#include "gys_groups.hpp"
 #include "gys_hllroll.hpp"
 #include "gys_histroll.hpp"
 #include "gys_huge.hpp"
@@ -58,6 +59,56 @@ void set_err(const char *fmt, ...)
 			return GYS_ERR_HIP;                                                                \
 		}                                                                                          \
 	} while (0)
+
+// An owning, grow-only device buffer of `cap` elements.  grow() keeps a buffer that is large enough; otherwise it waits for the stream (a
+// kernel in flight may still read the old buffer), frees it and allocates anew: the contents are NOT kept.  The destructor frees.
+template <typename T>
+struct DevBuf {
+	T *p = nullptr;
+	size_t cap = 0;
+	DevBuf() = default;
+	DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+	DevBuf &operator=(DevBuf &&o) noexcept
+	{
+		std::swap(p, o.p);
+		std::swap(cap, o.cap);
+		return *this;
+	}
+	~DevBuf() { release(); }
+	void release()
+	{
+		if (p) hipFree(p);
+		p = nullptr;
+		cap = 0;
+	}
+	int grow(size_t n, hipStream_t stream)
+	{
+		if (p && cap >= n) return GYS_OK;
+		if (p) HIPCHK(hipStreamSynchronize(stream));
+		release();
+		n = std::max<size_t>(n, 1);
+		HIPCHK(hipMalloc((void **)&p, n * sizeof(T)));
+		cap = n;
+		return GYS_OK;
+	}
+	int upload(const std::vector<T> &v, hipStream_t stream) // (asynchronous: v must outlive the copy)
+	{
+		const int rc = grow(v.size(), stream);
+		if (rc) return rc;
+		if (!v.empty()) HIPCHK(hipMemcpyAsync(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, stream));
+		return GYS_OK;
+	}
+};
+
+// The member lists of one grouping (gys_groups.hpp) and their copy on the device, built at one generation of the registry
+// (gys_ctx::registry_gen); ensure_host_groups() / ensure_cluster_groups() rebuild them when the registry has moved on.
+struct DeviceGroups {
+	GroupLists h;
+	DevBuf<uint32_t> members, off; // (off: only where a kernel reads it -- the all-hosts top-N)
+	DevBuf<RollupChunk> chunks, gchunks;
+	uint32_t nchunks = 0;
+	uint64_t gen = ~0ull;
+};
 
 struct MachId {
 	uint64_t first, second;
@@ -379,20 +430,20 @@ struct gys_ctx {
 	uint64_t dev_staging_bytes = 0;
 	uint32_t *dev_offsets = nullptr;
 	uint32_t dev_offsets_cap = 0;
-	// host -> member services (slot order) on the device, rebuilt when the registry changed (roll-ups, all-hosts top-N)
-	uint32_t *csr_off = nullptr, *csr_mem = nullptr;
-	uint64_t csr_stamp = ~0ull;
+	// which service belongs to which host, which host to which cluster: counted up by every call that changes either (services added or
+	// deleted, a host registered or moved to another cluster, a cluster added).  The two cached groupings are rebuilt when it has moved:
+	// host -> services (ascending slot inside a host, the tie-break order of the top-N; roll-ups, all-hosts top-N) and cluster -> hosts
+	uint64_t registry_gen = 0;
+	DeviceGroups host_groups, cluster_groups;
 	std::vector<uint16_t> svc_port_h; // listener port per service slot (web_curr_top_listeners "port")
 	uint32_t *topn_slot = nullptr;
 	uint64_t *topn_metric = nullptr;
 	// filtered multi-host listener-state query (gys_svcquery.hpp): scratch, grow-only
-	unsigned long long *q_cand_key = nullptr, *q_out_keys = nullptr;
-	uint32_t *q_cand_slot = nullptr, *q_misc = nullptr, *q_host_mask = nullptr, *q_slot_list = nullptr;
-	int32_t *q_set = nullptr;
-	uint8_t *q_out_rows = nullptr;
-	long long *q_acc = nullptr;
-	unsigned long long *q_cnt = nullptr;
-	uint64_t q_cand_cap = 0, q_slot_cap = 0, q_out_cap = 0, q_okeys_cap = 0, q_mask_cap = 0, q_set_cap = 0, q_acc_cap = 0, q_cnt_cap = 0, q_slist_cap = 0;
+	DevBuf<unsigned long long> q_cand_key, q_out_keys, q_cnt;
+	DevBuf<uint32_t> q_cand_slot, q_misc, q_host_mask, q_slot_list;
+	DevBuf<int32_t> q_set;
+	DevBuf<uint8_t> q_out_rows;
+	DevBuf<long long> q_acc;
 	float *dev_pcts = nullptr;
 	float *zipf_cdf = nullptr;
 	uint32_t zipf_n = 0, zipf_milli = 0;
@@ -410,38 +461,25 @@ struct gys_ctx {
 	// lazily folded records (t-digest on): hist_win and lvl_last change places at every close instead of a copy; lvl_last[slot] then is the service's
 	// record of window lvl_last_tag[slot] (written by the close's fold pass) and counts only when that is lvl_last_epoch, the window closed last
 	uint32_t *lvl_last_tag = nullptr;
-	// roll-up digests (gys_rollup.hpp): the groups' value bins (grows), the hosts' member lists on the device (rebuilt when services were registered)
-	unsigned long long *rb_bins = nullptr;
-	size_t rb_bins_groups = 0;
-	uint32_t *rb_host_members = nullptr;
-	RollupChunk *rb_host_chunks = nullptr;
-	uint32_t rb_host_nsvc = ~0u, rb_host_nh = ~0u, rb_host_nchunks = 0;
-	RollupChunk *rb_host_gchunks = nullptr; // [hosts] {host, first chunk, end chunk} of rb_host_chunks: a host's chunks as the members of a second pass
-	// distinct counts (gys_hllroll.hpp): the clusters' host lists (rebuilt when a host's cluster changed) and one scratch buffer (grows:
-	// a file per chunk, per host and per group -- first call / after a registration only)
-	uint32_t *hl_cl_members = nullptr;
-	RollupChunk *hl_cl_chunks = nullptr, *hl_cl_gchunks = nullptr;
-	uint32_t hl_cl_nchunks = 0, hl_cl_ncl = ~0u;
-	std::vector<uint32_t> hl_cl_snap; // host_cluster_h the lists were built from
-	uint8_t *hl_buf = nullptr;
-	size_t hl_buf_bytes = 0;
+	// roll-up digests (gys_rollup.hpp): the groups' value bins (GYS_RB_STRIDE words per group; grows)
+	DevBuf<unsigned long long> rb_bins;
+	// distinct counts (gys_hllroll.hpp): one scratch buffer (grows: a file per chunk, per host and per group -- first call / after a
+	// registration only)
+	DevBuf<uint8_t> hl_buf;
 	// group histograms of the levels (gys_histroll.hpp): one scratch buffer (grows: a record per chunk and per host)
-	gys_hist_rec *hr_buf = nullptr;
-	size_t hr_buf_recs = 0;
+	DevBuf<gys_hist_rec> hr_buf;
 	// distinct counts of the closed windows (cfg.svc_hll_levels; "levels" in gys_hllroll.hpp)
 	uint8_t *hl_lvl = nullptr;        // [GYS_HLL_LVL_FILES][max_services] files: last, the two rings, all
-	uint8_t *hl_view = nullptr;       // a level's files of every service, materialised for gys_hll_rollup_level_dev (nsvc files; grows)
-	size_t hl_view_bytes = 0;
+	DevBuf<uint8_t> hl_view;          // a level's files of every service, materialised for gys_hll_rollup_level_dev (nsvc files; grows)
 	// filtered roll-ups (gys_rollsel.hpp): the services' labels (gys_set_service_groups; allocated on first use, GYS_NO_GROUP everywhere)
 	// and the scratch of a selection (grows): the items' groups, the groups' counters / cursors, the members, the chunk lists,
 	// the rows with their offsets, the scan's tile sums and the totals
 	uint32_t *svc_label = nullptr;
 	uint32_t label_domain = 0; // every label set so far is below this
-	uint32_t *rs_item_group = nullptr, *rs_counts = nullptr, *rs_members = nullptr, *rs_tiles = nullptr, *rs_tot = nullptr;
-	RollupChunk *rs_chunks = nullptr, *rs_gchunks = nullptr;
-	gys_rollup_row *rs_rows = nullptr;
-	uint2 *rs_rowoff = nullptr;
-	uint64_t rs_item_cap = 0, rs_counts_cap = 0, rs_members_cap = 0, rs_tiles_cap = 0, rs_tot_cap = 0, rs_chunks_cap = 0, rs_gchunks_cap = 0, rs_rows_cap = 0, rs_rowoff_cap = 0;
+	DevBuf<uint32_t> rs_item_group, rs_counts, rs_members, rs_tiles, rs_tot;
+	DevBuf<RollupChunk> rs_chunks, rs_gchunks;
+	DevBuf<gys_rollup_row> rs_rows;
+	DevBuf<uint2> rs_rowoff;
 	int64_t hl_t_last = -1;           // close time (s) of the last window rolled into hl_lvl, -1: none yet
 	uint32_t hl_roll_epoch = 0xFFFFFFFEu; // the window rolled last (a finish step that is retried after a failure further down must not roll twice)
 	int64_t hl_close_t = 0;           // close time (s) the prepared window was given (gys_window_prepare; the roll runs in gys_window_finish)
@@ -2573,8 +2611,8 @@ void gys_destroy(gys_ctx *c)
 			c->td_cnt, c->td_meta, c->td_minmax, c->td_pend, c->td_cur, c->td_run, c->td_run0, c->td_run1, c->td_prevm, c->pre_hot, c->host_batch, c->append_list, c->svc_host, c->host_spill, c->merge_list, c->merge_list_slow, c->merge_list1, c->merge_list2, c->resp_win, c->cms_partial, c->huge_list, c->query_list, c->merge_count, c->query_sum, c->query_cnt,
 			c->batch_cnt, c->batch_off, c->scan_block_sums, c->ev_kv, c->staged, c->huge_scratch, c->huge_acc, c->huge_tail, c->huge_tb_list, c->huge_bm, c->huge_chunk_off, c->huge_fb_list, c->hll32, c->svc_ctr, c->svc_win, c->svc_state, c->svc_claim, c->svc_hll, c->host_summ_win, c->host_summ_last, c->host_state,
 			c->host_state_epoch, c->host_cluster, c->counters, c->misc, c->htbl, c->hlst, c->hdesc, c->wire_jump[0], c->wire_jump[1], c->wire_cnt,
-			c->wire_rank, c->wire_bsums, c->wire_status, c->wire_mark, c->wire_flags, c->wire_msgs, c->last, c->last_act32, c->last_act64, c->ring_act32, c->ring_act64, c->act_live, c->q_cand_key, c->q_out_keys, c->q_cand_slot, c->q_misc, c->q_host_mask, c->q_slot_list, c->q_set, c->q_out_rows, c->q_acc, c->q_cnt, c->dev_staging, c->dev_offsets, c->csr_off, c->csr_mem, c->svc_act, c->d_epoch, c->topn_slot,
-			c->topn_metric, c->dev_pcts, c->zipf_cdf, c->lvl_snap, c->lvl_last, c->lvl_last_tag, c->svc_bithist, c->rb_bins, c->rb_host_members, c->rb_host_chunks, c->rb_host_gchunks, c->hl_cl_members, c->hl_cl_chunks, c->hl_cl_gchunks, c->hl_buf, c->hr_buf, c->hl_lvl, c->hl_view, c->svc_label, c->rs_item_group, c->rs_counts, c->rs_members, c->rs_tiles, c->rs_tot, c->rs_chunks, c->rs_gchunks, c->rs_rows, c->rs_rowoff, c->lvl_first, c->qps_hist, c->act_hist, c->cand_pool, c->clr_segs, c->stale_bits, c->stale_tiles, c->stale_ids, c->own_arena ? c->arena : nullptr};
+			c->wire_rank, c->wire_bsums, c->wire_status, c->wire_mark, c->wire_flags, c->wire_msgs, c->last, c->last_act32, c->last_act64, c->ring_act32, c->ring_act64, c->act_live, c->dev_staging, c->dev_offsets, c->svc_act, c->d_epoch, c->topn_slot,
+			c->topn_metric, c->dev_pcts, c->zipf_cdf, c->lvl_snap, c->lvl_last, c->lvl_last_tag, c->svc_bithist, c->hl_lvl, c->svc_label, c->lvl_first, c->qps_hist, c->act_hist, c->cand_pool, c->clr_segs, c->stale_bits, c->stale_tiles, c->stale_ids, c->own_arena ? c->arena : nullptr};
 	for (void *p : ptrs)
 		if (p) hipFree(p);
 	if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
@@ -2602,6 +2640,7 @@ try {
 		}
 		const uint32_t idx = (uint32_t)c->cluster_names.size();
 		c->cluster_names.emplace_back(cluster_name);
+		c->registry_gen++; // (one more group, still empty)
 		it = c->cluster_map.emplace(cluster_name, idx).first;
 	}
 	if (cluster_idx) *cluster_idx = it->second;
@@ -2635,9 +2674,11 @@ try {
 		c->host_names.emplace_back();
 		c->host_lst.back().tbl.assign(16, GYS_HOST_TBL_EMPTY);
 		c->host_seen.push_back(0);
+		c->registry_gen++;
 		rc = host_lst_upload(c, slot);
 		if (rc) return rc;
 	}
+	if (c->host_cluster_h[slot] != cidx) c->registry_gen++; // (a repeated registration that changes nothing leaves the cached groupings alone)
 	c->host_cluster_h[slot] = cidx;
 	HIPCHK(hipMemcpyAsync(c->host_cluster + slot, &cidx, 4, hipMemcpyHostToDevice, c->stream));
 	HIPCHK(hipStreamSynchronize(c->stream));
@@ -2718,6 +2759,7 @@ try {
 		c->svc_key_h.push_back(host_key48(arr[i].netns, arr[i].port));
 	}
 	c->nsvc += n;
+	c->registry_gen++;
 	return GYS_OK;
 } GYS_CATCH_ALL
 
@@ -2897,8 +2939,7 @@ try {
 		c->svc_key_h[s] = 0;
 		c->free_slots.insert(s);
 	}
-	c->csr_stamp = ~0ull; // the hosts' member lists are rebuilt, as after a registration
-	c->rb_host_nsvc = ~0u;
+	c->registry_gen++;
 	if (ndeleted) *ndeleted = nd;
 	{
 		// (a host whose upload fails here stays marked dirty: host_lst_add and the next delete rebuild its tables from the mirror first)
@@ -3001,8 +3042,7 @@ try {
 			c->free_slots.erase(s);
 		}
 		c->nsvc = top;
-		c->csr_stamp = ~0ull; // (a reused slot changes the hosts' member lists without changing the service count they are stamped with)
-		c->rb_host_nsvc = ~0u;
+		c->registry_gen++;
 	}
 	if (slots)
 		for (uint32_t i = 0; i < n_in; ++i) slots[i] = fresh_of[i] != GYS_NOSLOT ? sl[fresh_of[i]] : c->gid_map_h[arr_in[i].glob_id];
@@ -4130,31 +4170,48 @@ try {
 	return GYS_OK;
 } GYS_CATCH_ALL
 
-// host -> member services on the device (slot order inside a host)
-static int host_csr(gys_ctx *c)
+// ------------------------------------------------------------------------------------------------ the cached groupings
+#define GYS_RB_CHUNK_SERVICES 1024u // members a workgroup of k_rollup_accum adds up before it hands its bins to the group's
+#define GYS_RB_CHUNK_SLABS 32u
+
+// g, cut into chunks of GYS_RB_CHUNK_SERVICES members, becomes dg's lists on the host and on the device, as of the current generation
+static int groups_install(gys_ctx *c, DeviceGroups &dg, GroupLists g, bool with_off)
 {
-	const uint64_t stamp = ((uint64_t)c->hosts.size() << 32) | c->nsvc;
-	if (c->csr_stamp == stamp && c->csr_off) return GYS_OK;
-	const uint32_t nh = (uint32_t)c->hosts.size();
-	std::vector<uint32_t> off(nh + 1, 0), members;
-	members.reserve(c->nsvc);
-	for (uint32_t h = 0; h < nh; ++h) {
-		std::vector<uint32_t> sl = c->host_lst[h].all_slots;
-		std::sort(sl.begin(), sl.end());
-		members.insert(members.end(), sl.begin(), sl.end());
-		off[h + 1] = (uint32_t)members.size();
-	}
+	dg.gen = ~0ull;
+	dg.h = std::move(g);
+	groups_chunk(dg.h, GYS_RB_CHUNK_SERVICES);
+	dg.nchunks = (uint32_t)dg.h.chunks.size();
+	int rc = dg.members.upload(dg.h.members, c->stream);
+	if (rc == GYS_OK) rc = dg.chunks.upload(dg.h.chunks, c->stream);
+	if (rc == GYS_OK) rc = dg.gchunks.upload(dg.h.gchunks, c->stream);
+	if (rc == GYS_OK && with_off) rc = dg.off.upload(dg.h.off, c->stream);
+	if (rc) return rc;
 	HIPCHK(hipStreamSynchronize(c->stream));
-	if (c->csr_off) HIPCHK(hipFree(c->csr_off));
-	if (c->csr_mem) HIPCHK(hipFree(c->csr_mem));
-	c->csr_off = c->csr_mem = nullptr;
-	HIPCHK(hipMalloc((void **)&c->csr_off, off.size() * 4));
-	HIPCHK(hipMalloc((void **)&c->csr_mem, std::max<size_t>(members.size(), 1) * 4));
-	HIPCHK(hipMemcpy(c->csr_off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
-	if (!members.empty()) HIPCHK(hipMemcpy(c->csr_mem, members.data(), members.size() * 4, hipMemcpyHostToDevice));
-	c->csr_stamp = stamp;
+	dg.gen = c->registry_gen;
 	return GYS_OK;
 }
+
+// host -> member services (10^7 services: 40 MB), ascending slot inside a host: the order in which the top-N breaks ties.  The roll-ups
+// share the list: their kernels add integers and take maxima / minima per group (gys_rollup.hpp, gys_hllroll.hpp, gys_histroll.hpp), so
+// neither the order of a group's members nor where its chunks are cut changes a bit of their results.
+static int ensure_host_groups(gys_ctx *c)
+{
+	if (c->host_groups.gen == c->registry_gen) return GYS_OK;
+	std::vector<std::vector<uint32_t>> lists(c->hosts.size());
+	for (size_t h = 0; h < lists.size(); ++h) {
+		lists[h] = c->host_lst[h].all_slots;
+		std::sort(lists[h].begin(), lists[h].end());
+	}
+	return groups_install(c, c->host_groups, groups_from_lists(lists), true);
+}
+
+// cluster -> member hosts, ascending host slot inside a cluster
+static int ensure_cluster_groups(gys_ctx *c)
+{
+	if (c->cluster_groups.gen == c->registry_gen) return GYS_OK;
+	return groups_install(c, c->cluster_groups, groups_from_keys(c->host_cluster_h, (uint32_t)c->cluster_names.size()), false);
+}
+
 
 // the 10 best services of EVERY host for one kind (last closed window): slots[h * GYS_TOPN + r] (GYS_NOSLOT = none), metrics likewise
 static int topn_all_hosts(gys_ctx *c, int kind, std::vector<uint32_t> &slots, std::vector<uint64_t> &metrics)
@@ -4163,199 +4220,30 @@ static int topn_all_hosts(gys_ctx *c, int kind, std::vector<uint32_t> &slots, st
 	slots.assign((size_t)nh * GYS_TOPN, GYS_NOSLOT);
 	metrics.assign((size_t)nh * GYS_TOPN, 0);
 	if (!nh || !c->nsvc || c->epoch < 2) return GYS_OK;
-	int rc = host_csr(c);
+	int rc = ensure_host_groups(c);
 	if (rc) return rc;
-	uint32_t *d_slot = nullptr;
-	uint64_t *d_metric = nullptr;
-	HIPCHK(hipMalloc((void **)&d_slot, slots.size() * 4));
-	HIPCHK(hipMalloc((void **)&d_metric, metrics.size() * 8));
+	DevBuf<uint32_t> d_slot;
+	DevBuf<uint64_t> d_metric;
+	if ((rc = d_slot.grow(slots.size(), c->stream)) != GYS_OK || (rc = d_metric.grow(metrics.size(), c->stream)) != GYS_OK) return rc;
 	TopnHostsP tp{};
 	tp.svc_state = c->svc_state;
-	tp.off = c->csr_off;
-	tp.members = c->csr_mem;
+	tp.off = c->host_groups.off.p;
+	tp.members = c->host_groups.members.p;
 	tp.nhosts = nh;
 	tp.epoch = c->epoch - 1;
 	tp.kind = kind;
-	tp.out_slot = d_slot;
-	tp.out_metric = d_metric;
+	tp.out_slot = d_slot.p;
+	tp.out_metric = d_metric.p;
 	{
 		ProfScope ps(c, "topn_hosts");
 		hipLaunchKernelGGL(k_topn_hosts, dim3(std::min<uint32_t>(nh, (uint32_t)c->ncu * 8)), dim3(256), 0, c->stream, tp);
 	}
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpyAsync(slots.data(), d_slot, slots.size() * 4, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipMemcpyAsync(metrics.data(), d_metric, metrics.size() * 8, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipStreamSynchronize(c->stream));
-	HIPCHK(hipFree(d_slot));
-	HIPCHK(hipFree(d_metric));
+	HIPCHK(hipMemcpyAsync(slots.data(), d_slot.p, slots.size() * 4, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipMemcpyAsync(metrics.data(), d_metric.p, metrics.size() * 8, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream)); // (d_slot / d_metric go at scope exit)
 	return GYS_OK;
 }
-
-// ------------------------------------------------------------------------------------------------ roll-up digests
-#define GYS_RB_CHUNK_SERVICES 1024u // members a workgroup of k_rollup_accum adds up before it hands its bins to the group's
-#define GYS_RB_CHUNK_SLABS 32u
-
-static void rollup_chunks(const std::vector<uint32_t> &off, uint32_t per, std::vector<RollupChunk> &chunks)
-{
-	for (uint32_t g = 0; g + 1 < (uint32_t)off.size(); ++g)
-		for (uint32_t m = off[g]; m < off[g + 1]; m += per) chunks.push_back(RollupChunk{g, m, std::min(off[g + 1], m + per), 0u});
-}
-
-// the chunks of group g (rollup_chunks lays them out group after group) as ONE chunk of a second pass: {g, first chunk, end chunk}
-static void rollup_group_chunks(const std::vector<RollupChunk> &chunks, uint32_t ngroups, std::vector<RollupChunk> &gchunks)
-{
-	size_t i = 0;
-	for (uint32_t g = 0; g < ngroups; ++g) {
-		const uint32_t c0 = (uint32_t)i;
-		while (i < chunks.size() && chunks[i].group == g) ++i;
-		gchunks.push_back(RollupChunk{g, c0, (uint32_t)i, 0u});
-	}
-}
-
-// bins of `ngroups` groups <- the members the chunks name; slabs out.  d_chunks / d_members: DEVICE arrays.
-static int rollup_run(gys_ctx *c, int kind, const RollupChunk *d_chunks, uint32_t nchunks, const uint32_t *d_members, uint32_t ngroups,
-		      const gys_tdigest_slab *d_in, gys_tdigest_slab *d_out)
-{
-	if (!ngroups) return GYS_OK;
-	if (c->rb_bins_groups < ngroups) {
-		if (c->rb_bins) {
-			HIPCHK(hipStreamSynchronize(c->stream));
-			HIPCHK(hipFree(c->rb_bins));
-			c->rb_bins = nullptr;
-			c->rb_bins_groups = 0;
-		}
-		HIPCHK(hipMalloc((void **)&c->rb_bins, (size_t)ngroups * GYS_RB_STRIDE * 8));
-		c->rb_bins_groups = ngroups;
-	}
-	RollupP rp{};
-	rp.d = digest_params(c);
-	rp.chunks = d_chunks;
-	rp.nchunks = nchunks;
-	rp.members = d_members;
-	rp.kind = kind;
-	rp.in = d_in;
-	rp.bins = c->rb_bins;
-	rp.out = d_out;
-	rp.ngroups = ngroups;
-	{
-		ProfScope ps(c, kind == 0 ? "rollup_services" : "rollup_slabs");
-		const size_t words = (size_t)ngroups * (GYS_RB_HDR + 1u);
-		hipLaunchKernelGGL(k_rollup_init, dim3((uint32_t)std::min<size_t>((words + 255) / 256, (size_t)c->ncu * 16)), dim3(256), 0, c->stream, c->rb_bins, ngroups);
-		if (nchunks) hipLaunchKernelGGL(k_rollup_accum, dim3(std::min<uint32_t>(nchunks, (uint32_t)c->ncu * 16)), dim3(GYS_RB_NT), 0, c->stream, rp);
-		hipLaunchKernelGGL(k_rollup_mark, dim3(std::min<uint32_t>(ngroups, (uint32_t)c->ncu * 8)), dim3(256), 0, c->stream, rp);
-		if (nchunks) hipLaunchKernelGGL(k_rollup_refine, dim3(std::min<uint32_t>(nchunks, (uint32_t)c->ncu * 16)), dim3(GYS_RB_NT), 0, c->stream, rp);
-		hipLaunchKernelGGL(k_rollup_cluster, dim3(std::min<uint32_t>(ngroups, (uint32_t)c->ncu * 8)), dim3(256), 0, c->stream, rp);
-	}
-	HIPCHK(hipGetLastError());
-	return GYS_OK;
-}
-
-// groups of slabs (kind 1): the lists travel with the call
-static int rollup_slabs(gys_ctx *c, const std::vector<uint32_t> &off, const std::vector<uint32_t> &members, const gys_tdigest_slab *d_in, gys_tdigest_slab *d_out)
-{
-	const uint32_t ngroups = (uint32_t)off.size() - 1;
-	if (!ngroups) return GYS_OK;
-	std::vector<RollupChunk> chunks;
-	rollup_chunks(off, GYS_RB_CHUNK_SLABS, chunks);
-	RollupChunk *d_chunks = nullptr;
-	uint32_t *d_mem = nullptr;
-	HIPCHK(hipMalloc((void **)&d_chunks, std::max<size_t>(chunks.size(), 1) * sizeof(RollupChunk)));
-	HIPCHK(hipMalloc((void **)&d_mem, std::max<size_t>(members.size(), 1) * 4));
-	if (!chunks.empty()) HIPCHK(hipMemcpyAsync(d_chunks, chunks.data(), chunks.size() * sizeof(RollupChunk), hipMemcpyHostToDevice, c->stream));
-	if (!members.empty()) HIPCHK(hipMemcpyAsync(d_mem, members.data(), members.size() * 4, hipMemcpyHostToDevice, c->stream));
-	const int rc = rollup_run(c, 1, d_chunks, (uint32_t)chunks.size(), d_mem, ngroups, d_in, d_out);
-	HIPCHK(hipStreamSynchronize(c->stream)); // the lists are freed below
-	HIPCHK(hipFree(d_chunks));
-	HIPCHK(hipFree(d_mem));
-	return rc;
-}
-
-// host level: members = the host's services.  The lists stay on the device until a service or a host is registered (10^7 services: 40 MB).
-// rb_host_gchunks names each host's range of chunks (the distinct-count roll-up joins a host's chunk files in a second pass).
-static int rollup_host_lists(gys_ctx *c)
-{
-	const uint32_t nh = (uint32_t)c->hosts.size();
-	if (c->rb_host_nsvc != c->nsvc || c->rb_host_nh != nh) {
-		std::vector<uint32_t> off(nh + 1, 0), members;
-		members.reserve(c->nsvc);
-		for (uint32_t h = 0; h < nh; ++h) {
-			const std::vector<uint32_t> &sl = c->host_lst[h].all_slots;
-			members.insert(members.end(), sl.begin(), sl.end());
-			off[h + 1] = (uint32_t)members.size();
-		}
-		std::vector<RollupChunk> chunks, gchunks;
-		rollup_chunks(off, GYS_RB_CHUNK_SERVICES, chunks);
-		rollup_group_chunks(chunks, nh, gchunks);
-		HIPCHK(hipStreamSynchronize(c->stream));
-		if (c->rb_host_members) HIPCHK(hipFree(c->rb_host_members));
-		if (c->rb_host_chunks) HIPCHK(hipFree(c->rb_host_chunks));
-		if (c->rb_host_gchunks) HIPCHK(hipFree(c->rb_host_gchunks));
-		c->rb_host_members = nullptr;
-		c->rb_host_chunks = nullptr;
-		c->rb_host_gchunks = nullptr;
-		c->rb_host_nsvc = ~0u;
-		HIPCHK(hipMalloc((void **)&c->rb_host_members, std::max<size_t>(members.size(), 1) * 4));
-		HIPCHK(hipMalloc((void **)&c->rb_host_chunks, std::max<size_t>(chunks.size(), 1) * sizeof(RollupChunk)));
-		HIPCHK(hipMalloc((void **)&c->rb_host_gchunks, std::max<size_t>(gchunks.size(), 1) * sizeof(RollupChunk)));
-		if (!members.empty()) HIPCHK(hipMemcpy(c->rb_host_members, members.data(), members.size() * 4, hipMemcpyHostToDevice));
-		if (!chunks.empty()) HIPCHK(hipMemcpy(c->rb_host_chunks, chunks.data(), chunks.size() * sizeof(RollupChunk), hipMemcpyHostToDevice));
-		if (!gchunks.empty()) HIPCHK(hipMemcpy(c->rb_host_gchunks, gchunks.data(), gchunks.size() * sizeof(RollupChunk), hipMemcpyHostToDevice));
-		c->rb_host_nchunks = (uint32_t)chunks.size();
-		c->rb_host_nsvc = c->nsvc;
-		c->rb_host_nh = nh;
-	}
-	return GYS_OK;
-}
-
-int gys_tdigest_rollup_dev(gys_ctx *c, int scope, gys_tdigest_slab *d_out)
-try {
-	GYS_ENTER(c);
-	if (!c || !d_out || scope < GYS_ROLLUP_HOST || scope > GYS_ROLLUP_GLOBAL) return GYS_ERR_INVAL;
-	TDIGEST_CHECK();
-	const uint32_t nh = (uint32_t)c->hosts.size();
-	if (!nh) {
-		if (scope == GYS_ROLLUP_GLOBAL) HIPCHK(hipMemsetAsync(d_out, 0, sizeof(gys_tdigest_slab), c->stream));
-		return GYS_OK;
-	}
-	{
-		const int rcl = rollup_host_lists(c);
-		if (rcl) return rcl;
-	}
-	gys_tdigest_slab *d_hosts = d_out;
-	if (scope != GYS_ROLLUP_HOST) HIPCHK(hipMalloc((void **)&d_hosts, sizeof(gys_tdigest_slab) * nh));
-	int rc = rollup_run(c, 0, c->rb_host_chunks, c->rb_host_nchunks, c->rb_host_members, nh, nullptr, d_hosts);
-	if (rc == GYS_OK && scope != GYS_ROLLUP_HOST) {
-		std::vector<uint32_t> goff, gmem;
-		if (scope == GYS_ROLLUP_GLOBAL) { // one group: every host slab
-			goff = {0u, nh};
-			gmem.resize(nh);
-			for (uint32_t h = 0; h < nh; ++h) gmem[h] = h;
-		} else {
-			const uint32_t ncl = (uint32_t)c->cluster_names.size();
-			goff.assign(ncl + 1, 0);
-			for (uint32_t cl = 0; cl < ncl; ++cl) {
-				for (uint32_t h = 0; h < nh; ++h)
-					if (c->host_cluster_h[h] == cl) gmem.push_back(h);
-				goff[cl + 1] = (uint32_t)gmem.size();
-			}
-		}
-		rc = rollup_slabs(c, goff, gmem, d_hosts, d_out);
-	}
-	if (scope != GYS_ROLLUP_HOST) {
-		HIPCHK(hipStreamSynchronize(c->stream));
-		HIPCHK(hipFree(d_hosts));
-	}
-	return rc;
-} GYS_CATCH_ALL
-
-int gys_tdigest_merge_slabs_dev(gys_ctx *c, const gys_tdigest_slab *d_in, uint32_t n, gys_tdigest_slab *d_out)
-try {
-	GYS_ENTER(c);
-	if (!c || !d_in || !d_out || n == 0) return GYS_ERR_INVAL;
-	std::vector<uint32_t> off{0u, n}, mem(n);
-	for (uint32_t i = 0; i < n; ++i) mem[i] = i;
-	return rollup_slabs(c, off, mem, d_in, d_out);
-} GYS_CATCH_ALL
 
 int gys_tdigest_slab_quantiles(gys_ctx *c, const gys_tdigest_slab *d_slab, const double *q, uint32_t nq, double *out)
 try {
@@ -4563,9 +4451,11 @@ try {
 	RCCL_API(R);
 	NCCLCHK(R->CommCount((ncclComm_t)comm, &nranks));
 	NCCLCHK(R->CommUserRank((ncclComm_t)comm, &rank));
-	gys_tdigest_slab *d_all = nullptr;
-	HIPCHK(hipMalloc((void **)&d_all, sizeof(gys_tdigest_slab) * (size_t)nranks));
-	int rc = gys_tdigest_rollup_dev(c, GYS_ROLLUP_GLOBAL, d_all + rank); // in place: this rank's slab sits at its own position
+	DevBuf<gys_tdigest_slab> all;
+	int rc = all.grow((size_t)nranks, c->stream);
+	if (rc) return rc;
+	gys_tdigest_slab *d_all = all.p;
+	rc = gys_tdigest_rollup_dev(c, GYS_ROLLUP_GLOBAL, d_all + rank); // in place: this rank's slab sits at its own position
 	if (rc == GYS_OK) {
 		const ncclResult_t r = R->AllGather(d_all + rank, d_all, sizeof(gys_tdigest_slab), ncclUint8, (ncclComm_t)comm, c->stream);
 		if (r != ncclSuccess) {
@@ -4573,8 +4463,9 @@ try {
 			rc = GYS_ERR_HIP;
 		}
 	}
-	if (rc == GYS_OK) rc = gys_tdigest_merge_slabs_dev(c, d_all, (uint32_t)nranks, d_out); // (synchronises the stream)
-	hipFree(d_all);
+	if (rc == GYS_OK) rc = gys_tdigest_merge_slabs_dev(c, d_all, (uint32_t)nranks, d_out);
+	const hipError_t es = hipStreamSynchronize(c->stream); // d_all is freed at scope exit
+	if (rc == GYS_OK) HIPCHK(es);
 	return rc;
 } GYS_CATCH_ALL
 
@@ -4586,91 +4477,12 @@ try {
 	}
 #define HLL_ALIGNED(ptr) (((uintptr_t)(ptr) & 15u) == 0)
 
-// the scratch buffer: [partial files: one per chunk][host files][group files], each part 256-byte aligned.  Grows, never shrinks; its
-// size follows from the registered services / hosts / clusters (chunks <= services / 1024 + hosts), not from how often it is asked for.
-static int hll_scratch(gys_ctx *c, size_t nparts, size_t nhostfiles, size_t ngroupfiles, uint8_t **parts, uint8_t **hostfiles, uint8_t **groupfiles)
-{
-	const size_t m = (size_t)1 << c->cfg.svc_hll_p;
-	const size_t a = align_up(std::max<size_t>(nparts, 1) * m, 256), b = align_up(nhostfiles * m, 256), g = align_up(ngroupfiles * m, 256);
-	if (c->hl_buf_bytes < a + b + g) {
-		if (c->hl_buf) {
-			HIPCHK(hipStreamSynchronize(c->stream));
-			HIPCHK(hipFree(c->hl_buf));
-			c->hl_buf = nullptr;
-			c->hl_buf_bytes = 0;
-		}
-		HIPCHK(hipMalloc((void **)&c->hl_buf, a + b + g));
-		c->hl_buf_bytes = a + b + g;
-	}
-	*parts = c->hl_buf;
-	if (hostfiles) *hostfiles = c->hl_buf + a;
-	if (groupfiles) *groupfiles = c->hl_buf + a + b;
-	return GYS_OK;
-}
-
-static void hll_union_launch(gys_ctx *c, const HllUnionP &q)
-{
-	if (q.nchunks) hipLaunchKernelGGL(k_hll_union, dim3(std::min<uint32_t>(q.nchunks, (uint32_t)c->ncu * 8)), dim3(GYS_HLL_NT), 0, c->stream, q);
-}
 static void hll_estimate_launch(gys_ctx *c, const uint8_t *files, uint32_t n, double *d_out)
 {
 	const uint64_t pieces = (uint64_t)n << (c->cfg.svc_hll_p - 4);
 	if (n) hipLaunchKernelGGL(k_hll_estimate, dim3((uint32_t)std::min<uint64_t>((pieces + GYS_HLL_NT - 1) / GYS_HLL_NT, (uint64_t)c->ncu * 16)), dim3(GYS_HLL_NT), 0, c->stream,
 				  files, n, (uint32_t)c->cfg.svc_hll_p, d_out);
 }
-// dst[0] = union of the n contiguous files at src: chunks of GYS_RB_CHUNK_SERVICES files into `parts`, then the chunks' files
-static void hll_union_contiguous(gys_ctx *c, const uint8_t *src, uint32_t n, uint8_t *parts, uint8_t *dst)
-{
-	const uint32_t p = c->cfg.svc_hll_p, nch = (n + GYS_RB_CHUNK_SERVICES - 1) / GYS_RB_CHUNK_SERVICES;
-	if (nch <= 1) {
-		hll_union_launch(c, HllUnionP{src, dst, nullptr, nullptr, 1u, n, std::max(n, 1u), p});
-		return;
-	}
-	hll_union_launch(c, HllUnionP{src, parts, nullptr, nullptr, nch, n, GYS_RB_CHUNK_SERVICES, p});
-	hll_union_launch(c, HllUnionP{parts, dst, nullptr, nullptr, 1u, nch, nch, p});
-}
-
-// the clusters' host lists on the device: rebuilt when a host was registered or moved to another cluster
-static int hll_cluster_lists(gys_ctx *c)
-{
-	const uint32_t ncl = (uint32_t)c->cluster_names.size();
-	if (c->hl_cl_ncl == ncl && c->hl_cl_snap == c->host_cluster_h) return GYS_OK;
-	const uint32_t nh = (uint32_t)c->hosts.size();
-	std::vector<uint32_t> off(ncl + 1, 0), members;
-	members.reserve(nh);
-	{
-		std::vector<uint32_t> cnt(ncl + 1, 0);
-		for (uint32_t h = 0; h < nh; ++h)
-			if (c->host_cluster_h[h] < ncl) cnt[c->host_cluster_h[h] + 1]++;
-		for (uint32_t cl = 0; cl < ncl; ++cl) off[cl + 1] = off[cl] + cnt[cl + 1];
-		members.resize(off[ncl]);
-		std::vector<uint32_t> at(off.begin(), off.end() - 1);
-		for (uint32_t h = 0; h < nh; ++h)
-			if (c->host_cluster_h[h] < ncl) members[at[c->host_cluster_h[h]]++] = h;
-	}
-	std::vector<RollupChunk> chunks, gchunks;
-	rollup_chunks(off, GYS_RB_CHUNK_SERVICES, chunks);
-	rollup_group_chunks(chunks, ncl, gchunks);
-	HIPCHK(hipStreamSynchronize(c->stream));
-	if (c->hl_cl_members) HIPCHK(hipFree(c->hl_cl_members));
-	if (c->hl_cl_chunks) HIPCHK(hipFree(c->hl_cl_chunks));
-	if (c->hl_cl_gchunks) HIPCHK(hipFree(c->hl_cl_gchunks));
-	c->hl_cl_members = nullptr;
-	c->hl_cl_chunks = nullptr;
-	c->hl_cl_gchunks = nullptr;
-	c->hl_cl_ncl = ~0u;
-	HIPCHK(hipMalloc((void **)&c->hl_cl_members, std::max<size_t>(members.size(), 1) * 4));
-	HIPCHK(hipMalloc((void **)&c->hl_cl_chunks, std::max<size_t>(chunks.size(), 1) * sizeof(RollupChunk)));
-	HIPCHK(hipMalloc((void **)&c->hl_cl_gchunks, std::max<size_t>(gchunks.size(), 1) * sizeof(RollupChunk)));
-	if (!members.empty()) HIPCHK(hipMemcpy(c->hl_cl_members, members.data(), members.size() * 4, hipMemcpyHostToDevice));
-	if (!chunks.empty()) HIPCHK(hipMemcpy(c->hl_cl_chunks, chunks.data(), chunks.size() * sizeof(RollupChunk), hipMemcpyHostToDevice));
-	if (!gchunks.empty()) HIPCHK(hipMemcpy(c->hl_cl_gchunks, gchunks.data(), gchunks.size() * sizeof(RollupChunk), hipMemcpyHostToDevice));
-	c->hl_cl_nchunks = (uint32_t)chunks.size();
-	c->hl_cl_snap = c->host_cluster_h;
-	c->hl_cl_ncl = ncl;
-	return GYS_OK;
-}
-
 int gys_scan_distinct_dev(gys_ctx *c, double *d_out)
 try {
 	GYS_ENTER(c);
@@ -4694,11 +4506,11 @@ try {
 		set_err("unknown glob_id %016llx", (unsigned long long)glob_id);
 		return GYS_ERR_INVAL;
 	}
-	uint8_t *d_tmp = nullptr;
 	{
-		const int rcs = hll_scratch(c, 1, 0, 0, &d_tmp, nullptr, nullptr);
+		const int rcs = c->hl_buf.grow(sizeof(double), c->stream);
 		if (rcs) return rcs;
 	}
+	uint8_t *d_tmp = c->hl_buf.p;
 	// the scan's kernel on this one slot: the same code turns the same bytes into the same double
 	hll_estimate_launch(c, c->svc_hll + ((size_t)it->second << c->cfg.svc_hll_p), 1u, (double *)d_tmp);
 	HIPCHK(hipGetLastError());
@@ -4708,77 +4520,6 @@ try {
 } GYS_CATCH_ALL
 
 uint32_t gys_hll_file_bytes(gys_ctx *c) { return c && c->cfg.svc_hll_p ? 1u << c->cfg.svc_hll_p : 0u; }
-
-// host / cluster / rank files and estimates of the services' files at src ([nsvc] files: the open registers, or a level's files)
-static int hll_rollup_src(gys_ctx *c, const uint8_t *src, int scope, uint8_t *d_regs, double *d_est)
-{
-	const uint32_t p = c->cfg.svc_hll_p, nh = (uint32_t)c->hosts.size(), ncl = (uint32_t)c->cluster_names.size();
-	const size_t m = (size_t)1 << p;
-	const uint32_t ngroups = scope == GYS_ROLLUP_HOST ? nh : (scope == GYS_ROLLUP_CLUSTER ? ncl : 1u);
-	if (!ngroups) return GYS_OK;
-	int rc = rollup_host_lists(c);
-	if (rc == GYS_OK && scope == GYS_ROLLUP_CLUSTER) rc = hll_cluster_lists(c);
-	if (rc) return rc;
-	const uint32_t nparts = std::max(std::max(c->rb_host_nchunks, scope == GYS_ROLLUP_CLUSTER ? c->hl_cl_nchunks : 0u), (nh + GYS_RB_CHUNK_SERVICES - 1) / GYS_RB_CHUNK_SERVICES);
-	uint8_t *parts = nullptr, *hostfiles = nullptr, *groupfiles = nullptr;
-	rc = hll_scratch(c, nparts, scope == GYS_ROLLUP_HOST && d_regs ? 0 : nh, scope == GYS_ROLLUP_HOST || d_regs ? 0 : ngroups, &parts, &hostfiles, &groupfiles);
-	if (rc) return rc;
-	if (scope == GYS_ROLLUP_HOST && d_regs) hostfiles = d_regs;
-	uint8_t *out = scope == GYS_ROLLUP_HOST ? hostfiles : (d_regs ? d_regs : groupfiles);
-	{
-		ProfScope ps(c, "hll_rollup_hosts"); // the services' files -> one file per chunk -> one per host
-		hll_union_launch(c, HllUnionP{src, parts, c->rb_host_chunks, c->rb_host_members, c->rb_host_nchunks, 0u, 0u, p});
-		hll_union_launch(c, HllUnionP{parts, hostfiles, c->rb_host_gchunks, nullptr, nh, 0u, 0u, p});
-	}
-	if (scope != GYS_ROLLUP_HOST) {
-		ProfScope ps(c, "hll_union_files");
-		if (scope == GYS_ROLLUP_GLOBAL) {
-			if (nh) hll_union_contiguous(c, hostfiles, nh, parts, out);
-			else HIPCHK(hipMemsetAsync(out, 0, m, c->stream));
-		} else {
-			hll_union_launch(c, HllUnionP{hostfiles, parts, c->hl_cl_chunks, c->hl_cl_members, c->hl_cl_nchunks, 0u, 0u, p});
-			hll_union_launch(c, HllUnionP{parts, out, c->hl_cl_gchunks, nullptr, ncl, 0u, 0u, p});
-		}
-	}
-	if (d_est) {
-		ProfScope ps(c, "hll_estimate_groups");
-		hll_estimate_launch(c, out, ngroups, d_est);
-	}
-	HIPCHK(hipGetLastError());
-	return GYS_OK;
-}
-
-int gys_hll_rollup_dev(gys_ctx *c, int scope, uint8_t *d_regs, double *d_est)
-try {
-	GYS_ENTER(c);
-	if (!c || (!d_regs && !d_est) || scope < GYS_ROLLUP_HOST || scope > GYS_ROLLUP_GLOBAL || !HLL_ALIGNED(d_regs)) {
-		set_err("gys_hll_rollup_dev: null outputs, an output that is not 16-byte aligned or an unknown scope");
-		return GYS_ERR_INVAL;
-	}
-	HLL_CHECK();
-	return hll_rollup_src(c, c->svc_hll, scope, d_regs, d_est);
-} GYS_CATCH_ALL
-
-int gys_hll_merge_files_dev(gys_ctx *c, const uint8_t *d_in, uint32_t n, uint8_t *d_out, double *d_est)
-try {
-	GYS_ENTER(c);
-	if (!c || !d_in || (!d_out && !d_est) || n == 0 || !HLL_ALIGNED(d_in) || !HLL_ALIGNED(d_out)) {
-		set_err("gys_hll_merge_files_dev: null pointers, a pointer that is not 16-byte aligned or n = 0");
-		return GYS_ERR_INVAL;
-	}
-	HLL_CHECK();
-	uint8_t *parts = nullptr, *groupfiles = nullptr;
-	const int rc = hll_scratch(c, (n + GYS_RB_CHUNK_SERVICES - 1) / GYS_RB_CHUNK_SERVICES, 0, d_out ? 0 : 1, &parts, nullptr, &groupfiles);
-	if (rc) return rc;
-	uint8_t *out = d_out ? d_out : groupfiles;
-	{
-		ProfScope ps(c, "hll_union_files");
-		hll_union_contiguous(c, d_in, n, parts, out);
-	}
-	if (d_est) hll_estimate_launch(c, out, 1u, d_est);
-	HIPCHK(hipGetLastError());
-	return GYS_OK;
-} GYS_CATCH_ALL
 
 int gys_hll_global_rccl(gys_ctx *c, void *comm, uint8_t *d_regs, double *d_est)
 try {
@@ -4790,9 +4531,11 @@ try {
 	NCCLCHK(R->CommCount((ncclComm_t)comm, &nranks));
 	NCCLCHK(R->CommUserRank((ncclComm_t)comm, &rank));
 	const size_t m = (size_t)1 << c->cfg.svc_hll_p;
-	uint8_t *d_all = nullptr;
-	HIPCHK(hipMalloc((void **)&d_all, m * (size_t)nranks));
-	int rc = gys_hll_rollup_dev(c, GYS_ROLLUP_GLOBAL, d_all + m * (size_t)rank, nullptr); // in place: this rank's file sits at its own position
+	DevBuf<uint8_t> all;
+	int rc = all.grow(m * (size_t)nranks, c->stream);
+	if (rc) return rc;
+	uint8_t *d_all = all.p;
+	rc = gys_hll_rollup_dev(c, GYS_ROLLUP_GLOBAL, d_all + m * (size_t)rank, nullptr); // in place: this rank's file sits at its own position
 	if (rc == GYS_OK) {
 		const ncclResult_t r = R->AllGather(d_all + m * (size_t)rank, d_all, m, ncclUint8, (ncclComm_t)comm, c->stream);
 		if (r != ncclSuccess) {
@@ -4801,8 +4544,7 @@ try {
 		}
 	}
 	if (rc == GYS_OK) rc = gys_hll_merge_files_dev(c, d_all, (uint32_t)nranks, d_regs, d_est);
-	const hipError_t es = hipStreamSynchronize(c->stream); // d_all is freed below
-	hipFree(d_all);
+	const hipError_t es = hipStreamSynchronize(c->stream); // d_all is freed at scope exit
 	if (rc == GYS_OK) HIPCHK(es);
 	return rc;
 } GYS_CATCH_ALL
@@ -4868,45 +4610,14 @@ try {
 		set_err("unknown glob_id %016llx", (unsigned long long)glob_id);
 		return GYS_ERR_INVAL;
 	}
-	uint8_t *d_tmp = nullptr;
-	int rc = hll_scratch(c, 1, 0, 0, &d_tmp, nullptr, nullptr);
+	int rc = c->hl_buf.grow(sizeof(double), c->stream);
 	if (rc) return rc;
+	uint8_t *d_tmp = c->hl_buf.p;
 	rc = hll_level_view(c, level, tusec, it->second, 1u, nullptr, (double *)d_tmp); // the scan's kernel on this one slot
 	if (rc) return rc;
 	HIPCHK(hipMemcpyAsync(out, d_tmp, sizeof(double), hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(hipStreamSynchronize(c->stream));
 	return GYS_OK;
-} GYS_CATCH_ALL
-
-// the level's files of every service once into c->hl_view (nsvc files; grows, never shrinks): the roll-ups of the open window then run on them
-static int hll_level_files(gys_ctx *c, int level, uint64_t tusec)
-{
-	const size_t need = std::max<size_t>((size_t)c->nsvc << c->cfg.svc_hll_p, 16);
-	if (c->hl_view_bytes < need) {
-		if (c->hl_view) {
-			HIPCHK(hipStreamSynchronize(c->stream));
-			HIPCHK(hipFree(c->hl_view));
-			c->hl_view = nullptr;
-			c->hl_view_bytes = 0;
-		}
-		HIPCHK(hipMalloc((void **)&c->hl_view, need));
-		c->hl_view_bytes = need;
-	}
-	ProfScope ps(c, "hll_level_files");
-	return hll_level_view(c, level, tusec, 0u, c->nsvc, c->hl_view, nullptr);
-}
-
-int gys_hll_rollup_level_dev(gys_ctx *c, int scope, int level, uint64_t tusec, uint8_t *d_regs, double *d_est)
-try {
-	GYS_ENTER(c);
-	if (!c || (!d_regs && !d_est) || scope < GYS_ROLLUP_HOST || scope > GYS_ROLLUP_GLOBAL || !HLL_ALIGNED(d_regs)) {
-		set_err("gys_hll_rollup_level_dev: null outputs, an output that is not 16-byte aligned or an unknown scope");
-		return GYS_ERR_INVAL;
-	}
-	HLL_LEVEL_CHECK(level);
-	const int rc = hll_level_files(c, level, tusec);
-	if (rc) return rc;
-	return hll_rollup_src(c, c->hl_view, scope, d_regs, d_est);
 } GYS_CATCH_ALL
 
 uint32_t gys_num_services(gys_ctx *c) { return c ? c->nsvc : 0; }
@@ -5069,16 +4780,12 @@ try {
 	RANGE_CHECK(first_slot, nslots);
 	HLL_LEVEL_CHECK(level);
 	if (!nslots) return GYS_OK;
-	uint8_t *tmp = nullptr;
-	HIPCHK(hipMalloc((void **)&tmp, (size_t)nslots << c->cfg.svc_hll_p));
-	const int rc = hll_level_view(c, level, tusec, first_slot, nslots, tmp, nullptr);
-	hipError_t e = hipSuccess;
-	if (rc == GYS_OK) e = hipMemcpyAsync(out, tmp, (size_t)nslots << c->cfg.svc_hll_p, hipMemcpyDeviceToHost, c->stream);
-	const hipError_t es = hipStreamSynchronize(c->stream);
-	hipFree(tmp);
+	DevBuf<uint8_t> tmp;
+	int rc = tmp.grow((size_t)nslots << c->cfg.svc_hll_p, c->stream);
+	if (rc == GYS_OK) rc = hll_level_view(c, level, tusec, first_slot, nslots, tmp.p, nullptr);
 	if (rc) return rc;
-	HIPCHK(e);
-	HIPCHK(es);
+	HIPCHK(hipMemcpyAsync(out, tmp.p, (size_t)nslots << c->cfg.svc_hll_p, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream)); // (tmp goes at scope exit)
 	return GYS_OK;
 } GYS_CATCH_ALL
 
@@ -5173,141 +4880,12 @@ try {
 	if (level < 0 || level >= GYS_NLEVELS) return GYS_ERR_INVAL;
 	LEVEL0_CHECK(level);
 	if (!nslots) return GYS_OK;
-	gys_hist_rec *tmp = nullptr;
-	HIPCHK(hipMalloc((void **)&tmp, (size_t)nslots * sizeof(gys_hist_rec)));
-	int rc = level_view(c, level, tusec, first_slot, nslots, tmp);
-	if (rc == GYS_OK) {
-		hipError_t e = hipMemcpyAsync(out, tmp, (size_t)nslots * sizeof(gys_hist_rec), hipMemcpyDeviceToHost, c->stream);
-		if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-		if (e != hipSuccess) {
-			set_err("level export copy: %s", hipGetErrorString(e));
-			rc = GYS_ERR_HIP;
-		}
-	}
-	hipFree(tmp);
-	return rc;
-} GYS_CATCH_ALL
-
-// ------------------------------------------------------------------------------------------------ group histograms of the levels (gys_histroll.hpp)
-// the scratch buffer: [partial records: one per chunk][host records].  Grows, never shrinks (chunks <= services / 1024 + groups).
-static int hist_union_scratch(gys_ctx *c, size_t nparts, size_t nhostrecs, gys_hist_rec **parts, gys_hist_rec **hostrecs)
-{
-	const size_t a = std::max<size_t>(nparts, 1);
-	if (c->hr_buf_recs < a + nhostrecs) {
-		if (c->hr_buf) {
-			HIPCHK(hipStreamSynchronize(c->stream));
-			HIPCHK(hipFree(c->hr_buf));
-			c->hr_buf = nullptr;
-			c->hr_buf_recs = 0;
-		}
-		HIPCHK(hipMalloc((void **)&c->hr_buf, (a + nhostrecs) * sizeof(gys_hist_rec)));
-		c->hr_buf_recs = a + nhostrecs;
-	}
-	*parts = c->hr_buf;
-	if (hostrecs) *hostrecs = c->hr_buf + a;
-	return GYS_OK;
-}
-
-static void hist_union_launch(gys_ctx *c, const HistUnionP &q)
-{
-	if (q.nchunks) hipLaunchKernelGGL(k_hist_level_union, dim3(std::min<uint32_t>(q.nchunks, (uint32_t)c->ncu * 8)), dim3(GYS_HR_NT), 0, c->stream, q);
-}
-
-// the sources of `level` at tusec for every service, exactly as level_view() reads them: the fold of the buffered values first, then
-// tq = max(tusec / 10^6, the last close) -- never the open window
-static int hist_union_level(gys_ctx *c, int level, uint64_t tusec, HistUnionP &q)
-{
-	int64_t tq = (int64_t)(tusec / 1000000ull);
-	if (tq < c->lvl_t_last) tq = c->lvl_t_last;
-	{
-		const int rcf = fold_range(c, 0, c->nsvc);
-		if (rcf) return rcf;
-	}
-	q = HistUnionP{};
-	q.v.win = c->hist_win;
-	q.v.all = c->hist_all;
-	q.v.meta = c->cfg.enable_tdigest ? c->td_meta : nullptr;
-	q.v.epoch_open = c->epoch + (c->prepared ? 1u : 0u);
-	level_source(c, level, tq, &q.v.mode, &q.v.sub);
-	q.v.last_tag = c->cfg.enable_tdigest ? c->lvl_last_tag : nullptr;
-	q.v.last_epoch = c->lvl_last_epoch;
-	return GYS_OK;
-}
-
-// the members' level records -> one record per chunk (parts) -> one per row (d_rows)
-static int hist_union_rows(gys_ctx *c, int level, uint64_t tusec, const RollupChunk *d_chunks, uint32_t nchunks, const uint32_t *d_members, const RollupChunk *d_gchunks,
-			   uint32_t nrows, gys_hist_rec *parts, gys_hist_rec *d_rows)
-{
-	HistUnionP q;
-	const int rc = hist_union_level(c, level, tusec, q);
+	DevBuf<gys_hist_rec> tmp;
+	int rc = tmp.grow(nslots, c->stream);
+	if (rc == GYS_OK) rc = level_view(c, level, tusec, first_slot, nslots, tmp.p);
 	if (rc) return rc;
-	ProfScope ps(c, "hist_rollup_union");
-	q.dst = parts;
-	q.chunks = d_chunks;
-	q.members = d_members;
-	q.nchunks = nchunks;
-	hist_union_launch(c, q);
-	HistUnionP g{};
-	g.plain = 1;
-	g.src = parts;
-	g.dst = d_rows;
-	g.chunks = d_gchunks;
-	g.nchunks = nrows;
-	hist_union_launch(c, g);
-	HIPCHK(hipGetLastError());
-	return GYS_OK;
-}
-
-int gys_hist_rollup_level_dev(gys_ctx *c, int scope, int level, uint64_t tusec, gys_hist_rec *d_out)
-try {
-	GYS_ENTER(c);
-	if (!c || !d_out || scope < GYS_ROLLUP_HOST || scope > GYS_ROLLUP_GLOBAL || level < 0 || level >= GYS_NLEVELS) {
-		set_err("gys_hist_rollup_level_dev: null output, an unknown scope or a level outside 0 .. %d", GYS_NLEVELS - 1);
-		return GYS_ERR_INVAL;
-	}
-	LEVELS_CHECK();
-	LEVEL0_CHECK(level);
-	const uint32_t nh = (uint32_t)c->hosts.size(), ncl = (uint32_t)c->cluster_names.size();
-	const uint32_t ngroups = scope == GYS_ROLLUP_HOST ? nh : (scope == GYS_ROLLUP_CLUSTER ? ncl : 1u);
-	if (!ngroups) return GYS_OK;
-	int rc = rollup_host_lists(c);
-	if (rc == GYS_OK && scope == GYS_ROLLUP_CLUSTER) rc = hll_cluster_lists(c);
-	if (rc) return rc;
-	const uint32_t nparts = std::max(std::max(c->rb_host_nchunks, scope == GYS_ROLLUP_CLUSTER ? c->hl_cl_nchunks : 0u), (nh + GYS_RB_CHUNK_SERVICES - 1) / GYS_RB_CHUNK_SERVICES);
-	gys_hist_rec *parts = nullptr, *hostrecs = nullptr;
-	if ((rc = hist_union_scratch(c, nparts, scope == GYS_ROLLUP_HOST ? 0 : nh, &parts, &hostrecs)) != GYS_OK) return rc;
-	if (scope == GYS_ROLLUP_HOST) hostrecs = d_out;
-	if ((rc = hist_union_rows(c, level, tusec, c->rb_host_chunks, c->rb_host_nchunks, c->rb_host_members, c->rb_host_gchunks, nh, parts, hostrecs)) != GYS_OK) return rc;
-	if (scope == GYS_ROLLUP_HOST) return GYS_OK;
-	ProfScope ps(c, "hist_rollup_groups"); // host records -> cluster records / the rank's record (plain)
-	HistUnionP g{};
-	g.plain = 1;
-	g.src = hostrecs;
-	g.dst = parts;
-	if (scope == GYS_ROLLUP_CLUSTER) {
-		g.chunks = c->hl_cl_chunks;
-		g.members = c->hl_cl_members;
-		g.nchunks = c->hl_cl_nchunks;
-	} else { // equal chunks of the contiguous host records (no host: one empty chunk)
-		g.n = nh;
-		g.per = GYS_RB_CHUNK_SERVICES;
-		g.nchunks = std::max(1u, (nh + GYS_RB_CHUNK_SERVICES - 1) / GYS_RB_CHUNK_SERVICES);
-	}
-	hist_union_launch(c, g);
-	HistUnionP f{};
-	f.plain = 1;
-	f.src = parts;
-	f.dst = d_out;
-	if (scope == GYS_ROLLUP_CLUSTER) {
-		f.chunks = c->hl_cl_gchunks;
-		f.nchunks = ncl;
-	} else {
-		f.n = g.nchunks;
-		f.per = std::max(g.nchunks, 1u);
-		f.nchunks = 1u;
-	}
-	hist_union_launch(c, f);
-	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(out, tmp.p, (size_t)nslots * sizeof(gys_hist_rec), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream)); // (tmp goes at scope exit)
 	return GYS_OK;
 } GYS_CATCH_ALL
 
@@ -5342,19 +4920,13 @@ try {
 	RANGE_CHECK(first_slot, nslots);
 	LEVELS_CHECK();
 	if (!nslots) return GYS_OK;
-	gys_hist_rec *tmp = nullptr;
-	HIPCHK(hipMalloc((void **)&tmp, (size_t)nslots * sizeof(gys_hist_rec)));
-	int rc = level_period(c, starttime, endtime + 1, tusec, first_slot, nslots, tmp, level_used);
-	if (rc == GYS_OK) {
-		hipError_t e = hipMemcpyAsync(out, tmp, (size_t)nslots * sizeof(gys_hist_rec), hipMemcpyDeviceToHost, c->stream);
-		if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-		if (e != hipSuccess) {
-			set_err("period export copy: %s", hipGetErrorString(e));
-			rc = GYS_ERR_HIP;
-		}
-	}
-	hipFree(tmp);
-	return rc;
+	DevBuf<gys_hist_rec> tmp;
+	int rc = tmp.grow(nslots, c->stream);
+	if (rc == GYS_OK) rc = level_period(c, starttime, endtime + 1, tusec, first_slot, nslots, tmp.p, level_used);
+	if (rc) return rc;
+	HIPCHK(hipMemcpyAsync(out, tmp.p, (size_t)nslots * sizeof(gys_hist_rec), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream)); // (tmp goes at scope exit)
+	return GYS_OK;
 } GYS_CATCH_ALL
 
 int gys_query_hist_period_stats(gys_ctx *c, uint64_t glob_id, int64_t starttime, int64_t endtime, uint64_t tusec, gys_time_hist_val *pstats,
@@ -5648,4 +5220,5 @@ try {
 #include "gys_json.hpp"
 #include "gys_regex.hpp"
 #include "gys_svcquery_host.hpp"
+#include "gys_rollup_host.hpp"
 #include "gys_rollsel_host.hpp"

@@ -1,6 +1,6 @@
 // gys_rollsel_host.hpp -- host side of the filtered, grouped roll-ups (kernels: gys_rollsel.hpp).  Included once by gys_engine.hip behind
-// gys_svcquery_host.hpp: the filter goes through q_fill_filter, the members through rollup_run / hll_union_launch / hist_union_rows as those of the
-// fixed roll-ups.
+// gys_svcquery_host.hpp and gys_rollup_host.hpp: the filter goes through q_fill_filter, the members through rollup_run / hll_union_launch /
+// hist_union_rows as those of the fixed roll-ups.
 #pragma once
 
 #define GYS_RS_ROWS_EAGER 65536u // up to this many possible rows (512 KB) the rows travel with the totals, before it is known how many there are
@@ -47,23 +47,14 @@ try {
 	}
 	for (uint32_t i = 0; i < n; ++i)
 		if (fin[i] != GYS_NO_GROUP) dom = std::max(dom, fin[i] + 1u);
-	uint32_t *d_slots = nullptr, *d_groups = nullptr;
-	HIPCHK(hipMalloc((void **)&d_slots, (size_t)n * 4));
-	if (hipMalloc((void **)&d_groups, (size_t)n * 4) != hipSuccess) {
-		hipFree(d_slots);
-		set_err("gys_set_service_groups: out of device memory");
-		return GYS_ERR_NOMEM;
-	}
-	hipError_t e = hipMemcpyAsync(d_slots, slots.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(d_groups, fin.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream);
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(k_rollsel_labels, dim3((uint32_t)std::min<uint64_t>(((uint64_t)n + 255u) / 256u, (uint64_t)c->ncu * 8)), dim3(256), 0, c->stream, d_slots, d_groups, n,
-				   c->svc_label);
-		e = hipGetLastError();
-	}
-	const hipError_t es = hipStreamSynchronize(c->stream); // the lists are freed below
-	hipFree(d_slots);
-	hipFree(d_groups);
+	DevBuf<uint32_t> d_slots, d_groups;
+	int rc = d_slots.upload(slots, c->stream);
+	if (rc == GYS_OK) rc = d_groups.upload(fin, c->stream);
+	if (rc) return rc;
+	hipLaunchKernelGGL(k_rollsel_labels, dim3((uint32_t)std::min<uint64_t>(((uint64_t)n + 255u) / 256u, (uint64_t)c->ncu * 8)), dim3(256), 0, c->stream, d_slots.p, d_groups.p, n,
+			   c->svc_label);
+	const hipError_t e = hipGetLastError();
+	const hipError_t es = hipStreamSynchronize(c->stream); // the lists are freed at scope exit
 	HIPCHK(e);
 	HIPCHK(es);
 	c->label_domain = dom; // (only once the device holds the labels)
@@ -73,7 +64,7 @@ try {
 } // extern "C"
 
 // the selection half of the filtered roll-ups: the filter's services grouped into rows (rows / *nrows are the caller's), their members in
-// c->rs_members, the chunk lists in c->rs_chunks (*pnchunks chunks) and the rows' chunk ranges in c->rs_gchunks (*pnr rows, 0: nothing to do)
+// c->rs_members.p, the chunk lists in c->rs_chunks.p (*pnchunks chunks) and the rows' chunk ranges in c->rs_gchunks.p (*pnr rows, 0: nothing to do)
 static int rollsel_select(gys_ctx *c, const gys_svc_filter *f, uint32_t flags, int group_by, gys_rollup_row *rows, uint32_t maxrows, uint32_t *nrows, uint32_t *pnr,
 			  uint32_t *pnchunks)
 {
@@ -96,30 +87,30 @@ static int rollsel_select(gys_ctx *c, const gys_svc_filter *f, uint32_t flags, i
 		p.ntiles = (p.nitems + GYS_RS_TILE - 1u) / GYS_RS_TILE;
 		nscan_tiles = (ndomain + GYS_RS_SCAN_TILE - 1u) / GYS_RS_SCAN_TILE;
 		const uint32_t rowcap = std::min(maxrows, ndomain);
-		if ((rc = q_grow(&c->rs_item_group, &c->rs_item_cap, p.nitems)) != GYS_OK) return rc;
-		if ((rc = q_grow(&c->rs_counts, &c->rs_counts_cap, (uint64_t)ndomain + 4u)) != GYS_OK) return rc;
-		if ((rc = q_grow(&c->rs_members, &c->rs_members_cap, p.nitems)) != GYS_OK) return rc;
-		if ((rc = q_grow(&c->rs_tiles, &c->rs_tiles_cap, 3ull * nscan_tiles)) != GYS_OK) return rc;
-		if ((rc = q_grow(&c->rs_tot, &c->rs_tot_cap, RS_TOT_WORDS)) != GYS_OK) return rc;
-		if ((rc = q_grow(&c->rs_rows, &c->rs_rows_cap, rowcap)) != GYS_OK) return rc;
-		if ((rc = q_grow(&c->rs_rowoff, &c->rs_rowoff_cap, rowcap)) != GYS_OK) return rc;
-		p.item_group = c->rs_item_group;
-		p.counts = c->rs_counts;
-		p.tot = c->rs_tot;
-		p.members = c->rs_members;
-		HIPCHK(hipMemsetAsync(c->rs_counts, 0, (size_t)ndomain * 4, c->stream));
+		if ((rc = c->rs_item_group.grow(p.nitems, c->stream)) != GYS_OK) return rc;
+		if ((rc = c->rs_counts.grow((uint64_t)ndomain + 4u, c->stream)) != GYS_OK) return rc;
+		if ((rc = c->rs_members.grow(p.nitems, c->stream)) != GYS_OK) return rc;
+		if ((rc = c->rs_tiles.grow(3ull * nscan_tiles, c->stream)) != GYS_OK) return rc;
+		if ((rc = c->rs_tot.grow(RS_TOT_WORDS, c->stream)) != GYS_OK) return rc;
+		if ((rc = c->rs_rows.grow(rowcap, c->stream)) != GYS_OK) return rc;
+		if ((rc = c->rs_rowoff.grow(rowcap, c->stream)) != GYS_OK) return rc;
+		p.item_group = c->rs_item_group.p;
+		p.counts = c->rs_counts.p;
+		p.tot = c->rs_tot.p;
+		p.members = c->rs_members.p;
+		HIPCHK(hipMemsetAsync(c->rs_counts.p, 0, (size_t)ndomain * 4, c->stream));
 		const uint32_t grid = std::max(1u, std::min<uint32_t>(p.ntiles, (uint32_t)c->ncu * 8));
 		hipLaunchKernelGGL(k_rollsel_count, dim3(grid), dim3(GYS_RS_THREADS), 0, c->stream, p);
 		RollScanP sp{};
-		sp.counts = c->rs_counts;
+		sp.counts = c->rs_counts.p;
 		sp.ndomain = ndomain;
 		sp.ntiles = nscan_tiles;
 		sp.per = GYS_RB_CHUNK_SERVICES;
 		sp.maxrows = maxrows;
-		sp.tiles = c->rs_tiles;
-		sp.tot = c->rs_tot;
-		sp.rows = c->rs_rows;
-		sp.rowoff = c->rs_rowoff;
+		sp.tiles = c->rs_tiles.p;
+		sp.tot = c->rs_tot.p;
+		sp.rows = c->rs_rows.p;
+		sp.rowoff = c->rs_rowoff.p;
 		const uint32_t sgrid = std::min<uint32_t>(nscan_tiles, (uint32_t)c->ncu * 8);
 		for (uint32_t phase = 0; phase < 3u; ++phase) {
 			sp.phase = phase;
@@ -130,8 +121,8 @@ static int rollsel_select(gys_ctx *c, const gys_svc_filter *f, uint32_t flags, i
 		// asks for more than GYS_RS_ROWS_EAGER rows pays a second small read of the rows there are).  Nothing after it waits for the host.
 		const bool eager = rowcap <= GYS_RS_ROWS_EAGER;
 		std::vector<gys_rollup_row> hrows(eager ? rowcap : 0u);
-		HIPCHK(hipMemcpyAsync(tot, c->rs_tot, sizeof(tot), hipMemcpyDeviceToHost, c->stream));
-		if (eager && rowcap) HIPCHK(hipMemcpyAsync(hrows.data(), c->rs_rows, (size_t)rowcap * sizeof(gys_rollup_row), hipMemcpyDeviceToHost, c->stream));
+		HIPCHK(hipMemcpyAsync(tot, c->rs_tot.p, sizeof(tot), hipMemcpyDeviceToHost, c->stream));
+		if (eager && rowcap) HIPCHK(hipMemcpyAsync(hrows.data(), c->rs_rows.p, (size_t)rowcap * sizeof(gys_rollup_row), hipMemcpyDeviceToHost, c->stream));
 		HIPCHK(hipStreamSynchronize(c->stream));
 		*nrows = tot[RS_TOT_ROWS];
 		const uint32_t nr = std::min(tot[RS_TOT_ROWS], maxrows);
@@ -139,20 +130,20 @@ static int rollsel_select(gys_ctx *c, const gys_svc_filter *f, uint32_t flags, i
 		if (eager) {
 			memcpy(rows, hrows.data(), (size_t)nr * sizeof(gys_rollup_row));
 		} else {
-			HIPCHK(hipMemcpyAsync(rows, c->rs_rows, (size_t)nr * sizeof(gys_rollup_row), hipMemcpyDeviceToHost, c->stream));
+			HIPCHK(hipMemcpyAsync(rows, c->rs_rows.p, (size_t)nr * sizeof(gys_rollup_row), hipMemcpyDeviceToHost, c->stream));
 			HIPCHK(hipStreamSynchronize(c->stream)); // (rows is the caller's: valid on return)
 		}
-		if ((rc = q_grow(&c->rs_chunks, &c->rs_chunks_cap, tot[RS_TOT_CHUNKS])) != GYS_OK) return rc;
-		if ((rc = q_grow(&c->rs_gchunks, &c->rs_gchunks_cap, nr)) != GYS_OK) return rc;
+		if ((rc = c->rs_chunks.grow(tot[RS_TOT_CHUNKS], c->stream)) != GYS_OK) return rc;
+		if ((rc = c->rs_gchunks.grow(nr, c->stream)) != GYS_OK) return rc;
 		hipLaunchKernelGGL(k_rollsel_scatter, dim3(grid), dim3(GYS_RS_THREADS), 0, c->stream, p);
 		RollChunksP cp{};
-		cp.rows = c->rs_rows;
-		cp.rowoff = c->rs_rowoff;
-		cp.tot = c->rs_tot;
+		cp.rows = c->rs_rows.p;
+		cp.rowoff = c->rs_rowoff.p;
+		cp.tot = c->rs_tot.p;
 		cp.maxrows = maxrows;
 		cp.per = GYS_RB_CHUNK_SERVICES;
-		cp.chunks = c->rs_chunks;
-		cp.gchunks = c->rs_gchunks;
+		cp.chunks = c->rs_chunks.p;
+		cp.gchunks = c->rs_gchunks.p;
 		hipLaunchKernelGGL(k_rollsel_chunks, dim3(std::min<uint32_t>((nr + 3u) / 4u, (uint32_t)c->ncu * 8)), dim3(GYS_RS_THREADS), 0, c->stream, cp);
 		HIPCHK(hipGetLastError());
 	}
@@ -187,21 +178,21 @@ try {
 	if (rc != GYS_OK || !nr) return rc;
 	if (d_slabs) {
 		ProfScope ps(c, "rollsel_digests");
-		if ((rc = rollup_run(c, 0, c->rs_chunks, nchunks, c->rs_members, nr, nullptr, d_slabs)) != GYS_OK) return rc;
+		if ((rc = rollup_run(c, 0, c->rs_chunks.p, nchunks, c->rs_members.p, nr, nullptr, d_slabs)) != GYS_OK) return rc;
 	}
 	if (want_hll) {
 		const uint8_t *src = c->svc_hll;
 		if (hll_level >= 0) {
 			if ((rc = hll_level_files(c, hll_level, tusec)) != GYS_OK) return rc;
-			src = c->hl_view;
+			src = c->hl_view.p;
 		}
 		uint8_t *parts = nullptr, *groupfiles = nullptr;
 		if ((rc = hll_scratch(c, nchunks, 0, d_regs ? 0 : nr, &parts, nullptr, &groupfiles)) != GYS_OK) return rc;
 		uint8_t *out = d_regs ? d_regs : groupfiles;
 		const uint32_t hp = c->cfg.svc_hll_p;
 		ProfScope ps(c, "rollsel_hll"); // the members' files -> one file per chunk -> one per row, then the estimates
-		hll_union_launch(c, HllUnionP{src, parts, c->rs_chunks, c->rs_members, nchunks, 0u, 0u, hp});
-		hll_union_launch(c, HllUnionP{parts, out, c->rs_gchunks, nullptr, nr, 0u, 0u, hp});
+		hll_union_launch(c, HllUnionP{src, parts, c->rs_chunks.p, c->rs_members.p, nchunks, 0u, 0u, hp});
+		hll_union_launch(c, HllUnionP{parts, out, c->rs_gchunks.p, nullptr, nr, 0u, 0u, hp});
 		if (d_est) hll_estimate_launch(c, out, nr, d_est);
 		HIPCHK(hipGetLastError());
 	}
@@ -225,7 +216,7 @@ try {
 	gys_hist_rec *parts = nullptr;
 	if ((rc = hist_union_scratch(c, nchunks, 0, &parts, nullptr)) != GYS_OK) return rc;
 	// the members' level records -> one record per chunk -> one per row
-	return hist_union_rows(c, level, tusec, c->rs_chunks, nchunks, c->rs_members, c->rs_gchunks, nr, parts, d_recs);
+	return hist_union_rows(c, level, tusec, c->rs_chunks.p, nchunks, c->rs_members.p, c->rs_gchunks.p, nr, parts, d_recs);
 } GYS_CATCH_ALL
 
 } // extern "C"

@@ -10,19 +10,6 @@
 
 namespace {
 
-template <typename T>
-int q_grow(T **p, uint64_t *cap, uint64_t need)
-{
-	if (*cap >= need && *p) return GYS_OK;
-	if (*p) HIPCHK(hipFree(*p));
-	*p = nullptr;
-	*cap = 0;
-	const uint64_t n = std::max<uint64_t>(need, 1);
-	HIPCHK(hipMalloc((void **)p, n * sizeof(T)));
-	*cap = n;
-	return GYS_OK;
-}
-
 // q_misc layout (u32 words): [0] candidate cursor, [1] want, [2] out count, [4..5] prefix (u64), [8 .. 8 + 2048) digit histogram
 constexpr uint32_t QM_CURSOR = 0, QM_WANT = 1, QM_OUT = 2, QM_PREFIX = 4, QM_HIST = 8, QM_WORDS = 8 + GYS_SVCQ_RADIX;
 
@@ -78,11 +65,11 @@ int q_fill_filter(gys_ctx *c, const gys_svc_filter *f, P &p)
 	for (uint32_t g = 0; g < GYS_SVCQ_MAX_GROUPS; ++g) p.group_oper[g] = f->group_oper[g] ? 1 : 0;
 	p.top_oper = f->top_oper ? 1u : 0u;
 	if (!setv.empty()) {
-		int rc = q_grow(&c->q_set, &c->q_set_cap, setv.size());
+		int rc = c->q_set.grow(setv.size(), c->stream);
 		if (rc) return rc;
-		HIPCHK(hipMemcpyAsync(c->q_set, setv.data(), setv.size() * 4, hipMemcpyHostToDevice, c->stream));
+		HIPCHK(hipMemcpyAsync(c->q_set.p, setv.data(), setv.size() * 4, hipMemcpyHostToDevice, c->stream));
 		HIPCHK(hipStreamSynchronize(c->stream)); // (setv is a local)
-		p.set_values = c->q_set;
+		p.set_values = c->q_set.p;
 	}
 	if (f->nmachine_ids || f->nclusters) { // the query names its hosts (is_multihost_ with host criteria: the walk over partha_tbl_ :4790-4860) and / or clusters
 		if ((f->nmachine_ids && !f->machine_ids) || (f->nclusters && !f->clusters)) return GYS_ERR_INVAL;
@@ -101,11 +88,11 @@ int q_fill_filter(gys_ctx *c, const gys_svc_filter *f, P &p)
 			for (uint32_t h = 0; h < c->hosts.size(); ++h)
 				if (!want[c->host_cluster_h[h]]) mask[h >> 5] &= ~(1u << (h & 31u));
 		}
-		int rc = q_grow(&c->q_host_mask, &c->q_mask_cap, words);
+		int rc = c->q_host_mask.grow(words, c->stream);
 		if (rc) return rc;
-		HIPCHK(hipMemcpyAsync(c->q_host_mask, mask.data(), words * 4, hipMemcpyHostToDevice, c->stream));
+		HIPCHK(hipMemcpyAsync(c->q_host_mask.p, mask.data(), words * 4, hipMemcpyHostToDevice, c->stream));
 		HIPCHK(hipStreamSynchronize(c->stream));
-		p.host_mask = c->q_host_mask;
+		p.host_mask = c->q_host_mask.p;
 	}
 	if (f->nsvcids) { // the query names its listeners: only their slots are visited
 		if (!f->svcids) return GYS_ERR_INVAL;
@@ -116,13 +103,13 @@ int q_fill_filter(gys_ctx *c, const gys_svc_filter *f, P &p)
 		}
 		std::sort(slots.begin(), slots.end());
 		slots.erase(std::unique(slots.begin(), slots.end()), slots.end());
-		int rc = q_grow(&c->q_slot_list, &c->q_slist_cap, slots.size());
+		int rc = c->q_slot_list.grow(slots.size(), c->stream);
 		if (rc) return rc;
 		if (!slots.empty()) {
-			HIPCHK(hipMemcpyAsync(c->q_slot_list, slots.data(), slots.size() * 4, hipMemcpyHostToDevice, c->stream));
+			HIPCHK(hipMemcpyAsync(c->q_slot_list.p, slots.data(), slots.size() * 4, hipMemcpyHostToDevice, c->stream));
 			HIPCHK(hipStreamSynchronize(c->stream));
 		}
-		p.slot_list = c->q_slot_list;
+		p.slot_list = c->q_slot_list.p;
 		p.nitems = (uint32_t)slots.size();
 	}
 	return GYS_OK;
@@ -140,25 +127,25 @@ int q_scan(gys_ctx *c, const gys_svc_filter *f, int sort_col, int sort_desc, uin
 	if (!c->nsvc || !maxrecs) return GYS_OK;
 	int rc;
 	static_assert(sizeof(gys_svc_row) == 96, "row layout");
-	if ((rc = q_grow(&c->q_cand_key, &c->q_cand_cap, c->nsvc)) != GYS_OK) return rc;
-	if ((rc = q_grow(&c->q_cand_slot, &c->q_slot_cap, c->nsvc)) != GYS_OK) return rc;
-	if (!c->q_misc) HIPCHK(hipMalloc((void **)&c->q_misc, QM_WORDS * 4));
-	HIPCHK(hipMemsetAsync(c->q_misc, 0, QM_WORDS * 4, c->stream));
+	if ((rc = c->q_cand_key.grow(c->nsvc, c->stream)) != GYS_OK) return rc;
+	if ((rc = c->q_cand_slot.grow(c->nsvc, c->stream)) != GYS_OK) return rc;
+	if ((rc = c->q_misc.grow(QM_WORDS, c->stream)) != GYS_OK) return rc;
+	HIPCHK(hipMemsetAsync(c->q_misc.p, 0, QM_WORDS * 4, c->stream));
 	const uint32_t k = (uint32_t)std::min<uint64_t>(maxrecs, c->nsvc);
-	if ((rc = q_grow(&c->q_out_rows, &c->q_out_cap, (uint64_t)k * 96)) != GYS_OK) return rc;
-	if ((rc = q_grow(&c->q_out_keys, &c->q_okeys_cap, k)) != GYS_OK) return rc;
+	if ((rc = c->q_out_rows.grow((uint64_t)k * 96, c->stream)) != GYS_OK) return rc;
+	if ((rc = c->q_out_keys.grow(k, c->stream)) != GYS_OK) return rc;
 	ProfScope ps(c, "svc_filter");
 	SvcFilterP p{};
 	if ((rc = q_fill_filter(c, f, p)) != GYS_OK) return rc;
 	p.sort_col = sort_col;
 	p.sort_desc = sort_desc ? 1u : 0u;
-	p.cand_key = c->q_cand_key;
-	p.cand_slot = c->q_cand_slot;
-	p.cursor = c->q_misc + QM_CURSOR;
+	p.cand_key = c->q_cand_key.p;
+	p.cand_slot = c->q_cand_slot.p;
+	p.cursor = c->q_misc.p + QM_CURSOR;
 	const uint32_t per_wg = GYS_SVCQ_THREADS * GYS_SVCQ_PER_THREAD;
 	hipLaunchKernelGGL(k_svc_filter, dim3(std::max(1u, (p.nitems + per_wg - 1) / per_wg)), dim3(GYS_SVCQ_THREADS), 0, c->stream, p);
 	uint32_t ncand = 0;
-	HIPCHK(hipMemcpyAsync(&ncand, c->q_misc + QM_CURSOR, 4, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipMemcpyAsync(&ncand, c->q_misc.p + QM_CURSOR, 4, hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(hipStreamSynchronize(c->stream));
 	if (nmatched) *nmatched = ncand;
 	if (!ncand) return GYS_OK;
@@ -166,12 +153,12 @@ int q_scan(gys_ctx *c, const gys_svc_filter *f, int sort_col, int sort_desc, uin
 	const bool select = ncand > k;
 	if (select) { // exact top-k: the k-th largest key, 11 bits per round, every round's bin chosen on the device
 		SvcSelectP sp{};
-		sp.cand_key = c->q_cand_key;
-		sp.ncand = c->q_misc + QM_CURSOR;
-		sp.hist = c->q_misc + QM_HIST;
-		sp.prefix = (unsigned long long *)(c->q_misc + QM_PREFIX);
-		sp.want = c->q_misc + QM_WANT;
-		HIPCHK(hipMemcpyAsync(c->q_misc + QM_WANT, &k, 4, hipMemcpyHostToDevice, c->stream));
+		sp.cand_key = c->q_cand_key.p;
+		sp.ncand = c->q_misc.p + QM_CURSOR;
+		sp.hist = c->q_misc.p + QM_HIST;
+		sp.prefix = (unsigned long long *)(c->q_misc.p + QM_PREFIX);
+		sp.want = c->q_misc.p + QM_WANT;
+		HIPCHK(hipMemcpyAsync(c->q_misc.p + QM_WANT, &k, 4, hipMemcpyHostToDevice, c->stream));
 		const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)ncand + 256u * 16u - 1) / (256u * 16u), (uint64_t)c->ncu * 4);
 		static const uint32_t shifts[GYS_SVCQ_ROUNDS] = {53, 42, 31, 20, 9, 0}, widths[GYS_SVCQ_ROUNDS] = {11, 11, 11, 11, 11, 9};
 		for (uint32_t r = 0; r < GYS_SVCQ_ROUNDS; ++r) {
@@ -183,19 +170,19 @@ int q_scan(gys_ctx *c, const gys_svc_filter *f, int sort_col, int sort_desc, uin
 	}
 	SvcGatherP gp{};
 	gp.svc_state = c->svc_state;
-	gp.cand_key = c->q_cand_key;
-	gp.cand_slot = c->q_cand_slot;
-	gp.ncand = c->q_misc + QM_CURSOR;
-	gp.threshold = select ? (const unsigned long long *)(c->q_misc + QM_PREFIX) : nullptr;
+	gp.cand_key = c->q_cand_key.p;
+	gp.cand_slot = c->q_cand_slot.p;
+	gp.ncand = c->q_misc.p + QM_CURSOR;
+	gp.threshold = select ? (const unsigned long long *)(c->q_misc.p + QM_PREFIX) : nullptr;
 	gp.maxout = k;
-	gp.out_count = c->q_misc + QM_OUT;
-	gp.out_rows = c->q_out_rows;
-	gp.out_keys = c->q_out_keys;
+	gp.out_count = c->q_misc.p + QM_OUT;
+	gp.out_rows = c->q_out_rows.p;
+	gp.out_keys = c->q_out_keys.p;
 	const uint32_t ggrid = (uint32_t)std::min<uint64_t>(((uint64_t)ncand + 255u) / 256u, (uint64_t)c->ncu * 8);
 	hipLaunchKernelGGL(k_svc_gather, dim3(std::max(1u, ggrid)), dim3(256), 0, c->stream, gp);
 	HIPCHK(hipGetLastError());
 	uint32_t nout = 0;
-	HIPCHK(hipMemcpyAsync(&nout, c->q_misc + QM_OUT, 4, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipMemcpyAsync(&nout, c->q_misc.p + QM_OUT, 4, hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(hipStreamSynchronize(c->stream));
 	if (nout != ntake) {
 		set_err("svcstate scan: selected %u records, expected %u", nout, ntake);
@@ -203,8 +190,8 @@ int q_scan(gys_ctx *c, const gys_svc_filter *f, int sort_col, int sort_desc, uin
 	}
 	std::vector<gys_svc_row> raw(nout);
 	std::vector<unsigned long long> keys(nout);
-	HIPCHK(hipMemcpyAsync(raw.data(), c->q_out_rows, (uint64_t)nout * 96, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipMemcpyAsync(keys.data(), c->q_out_keys, (uint64_t)nout * 8, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipMemcpyAsync(raw.data(), c->q_out_rows.p, (uint64_t)nout * 96, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipMemcpyAsync(keys.data(), c->q_out_keys.p, (uint64_t)nout * 8, hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(hipStreamSynchronize(c->stream));
 	std::vector<uint32_t> order(nout);
 	for (uint32_t i = 0; i < nout; ++i) order[i] = i;
@@ -263,16 +250,16 @@ try {
 	if (!c->nsvc || !ngroups) return GYS_OK;
 	const uint32_t nc = std::max(ncols, 1u);
 	int rc;
-	if ((rc = q_grow(&c->q_acc, &c->q_acc_cap, (uint64_t)ngroups * nc * 3)) != GYS_OK) return rc;
-	if ((rc = q_grow(&c->q_cnt, &c->q_cnt_cap, ngroups)) != GYS_OK) return rc;
+	if ((rc = c->q_acc.grow((uint64_t)ngroups * nc * 3, c->stream)) != GYS_OK) return rc;
+	if ((rc = c->q_cnt.grow(ngroups, c->stream)) != GYS_OK) return rc;
 	std::vector<long long> init((size_t)ngroups * nc * 3);
 	for (size_t i = 0; i < init.size(); i += 3) {
 		init[i] = 0;
 		init[i + 1] = std::numeric_limits<long long>::max();
 		init[i + 2] = std::numeric_limits<long long>::min();
 	}
-	HIPCHK(hipMemcpyAsync(c->q_acc, init.data(), init.size() * 8, hipMemcpyHostToDevice, c->stream));
-	HIPCHK(hipMemsetAsync(c->q_cnt, 0, (uint64_t)ngroups * 8, c->stream));
+	HIPCHK(hipMemcpyAsync(c->q_acc.p, init.data(), init.size() * 8, hipMemcpyHostToDevice, c->stream));
+	HIPCHK(hipMemsetAsync(c->q_cnt.p, 0, (uint64_t)ngroups * 8, c->stream));
 	ProfScope ps(c, "svc_aggr");
 	SvcAggrP p{};
 	if ((rc = q_fill_filter(c, f, p)) != GYS_OK) return rc;
@@ -280,14 +267,14 @@ try {
 	p.host_cluster = c->host_cluster;
 	p.ncols = ncols;
 	for (uint32_t a = 0; a < ncols; ++a) p.cols[a] = cols[a];
-	p.acc = c->q_acc;
-	p.count = c->q_cnt;
+	p.acc = c->q_acc.p;
+	p.count = c->q_cnt.p;
 	const uint32_t per_wg = GYS_SVCQ_THREADS * GYS_SVCQ_PER_THREAD;
 	hipLaunchKernelGGL(k_svc_aggr, dim3(std::max(1u, (p.nitems + per_wg - 1) / per_wg)), dim3(GYS_SVCQ_THREADS), 0, c->stream, p);
 	HIPCHK(hipGetLastError());
 	std::vector<unsigned long long> cnt(ngroups);
-	HIPCHK(hipMemcpyAsync(init.data(), c->q_acc, init.size() * 8, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipMemcpyAsync(cnt.data(), c->q_cnt, (uint64_t)ngroups * 8, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipMemcpyAsync(init.data(), c->q_acc.p, init.size() * 8, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipMemcpyAsync(cnt.data(), c->q_cnt.p, (uint64_t)ngroups * 8, hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(hipStreamSynchronize(c->stream));
 	uint32_t n = 0;
 	for (uint32_t g = 0; g < ngroups; ++g) {
@@ -574,31 +561,31 @@ try {
 	for (uint32_t i = 0; i < npcts; ++i) out[i] = 0;
 	if (!c->nsvc) return GYS_OK;
 	int rc;
-	if ((rc = q_grow(&c->q_cand_key, &c->q_cand_cap, c->nsvc)) != GYS_OK) return rc;
-	if ((rc = q_grow(&c->q_cand_slot, &c->q_slot_cap, c->nsvc)) != GYS_OK) return rc;
-	if (!c->q_misc) HIPCHK(hipMalloc((void **)&c->q_misc, QM_WORDS * 4));
-	HIPCHK(hipMemsetAsync(c->q_misc, 0, QM_WORDS * 4, c->stream));
+	if ((rc = c->q_cand_key.grow(c->nsvc, c->stream)) != GYS_OK) return rc;
+	if ((rc = c->q_cand_slot.grow(c->nsvc, c->stream)) != GYS_OK) return rc;
+	if ((rc = c->q_misc.grow(QM_WORDS, c->stream)) != GYS_OK) return rc;
+	HIPCHK(hipMemsetAsync(c->q_misc.p, 0, QM_WORDS * 4, c->stream));
 	ProfScope ps(c, "svc_filter");
 	SvcFilterP p{};
 	if ((rc = q_fill_filter(c, f, p)) != GYS_OK) return rc;
 	p.sort_col = col;
 	p.sort_desc = 1u;
-	p.cand_key = c->q_cand_key;
-	p.cand_slot = c->q_cand_slot;
-	p.cursor = c->q_misc + QM_CURSOR;
+	p.cand_key = c->q_cand_key.p;
+	p.cand_slot = c->q_cand_slot.p;
+	p.cursor = c->q_misc.p + QM_CURSOR;
 	const uint32_t per_wg = GYS_SVCQ_THREADS * GYS_SVCQ_PER_THREAD;
 	hipLaunchKernelGGL(k_svc_filter, dim3(std::max(1u, (p.nitems + per_wg - 1) / per_wg)), dim3(GYS_SVCQ_THREADS), 0, c->stream, p);
 	uint32_t ncand = 0;
-	HIPCHK(hipMemcpyAsync(&ncand, c->q_misc + QM_CURSOR, 4, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipMemcpyAsync(&ncand, c->q_misc.p + QM_CURSOR, 4, hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(hipStreamSynchronize(c->stream));
 	if (nmatched) *nmatched = ncand;
 	if (!ncand) return GYS_OK;
 	SvcSelectP sp{};
-	sp.cand_key = c->q_cand_key;
-	sp.ncand = c->q_misc + QM_CURSOR;
-	sp.hist = c->q_misc + QM_HIST;
-	sp.prefix = (unsigned long long *)(c->q_misc + QM_PREFIX);
-	sp.want = c->q_misc + QM_WANT;
+	sp.cand_key = c->q_cand_key.p;
+	sp.ncand = c->q_misc.p + QM_CURSOR;
+	sp.hist = c->q_misc.p + QM_HIST;
+	sp.prefix = (unsigned long long *)(c->q_misc.p + QM_PREFIX);
+	sp.want = c->q_misc.p + QM_WANT;
 	const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)ncand + 256u * 16u - 1) / (256u * 16u), (uint64_t)c->ncu * 4);
 	static const uint32_t shifts[GYS_SVCQ_ROUNDS] = {53, 42, 31, 20, 9, 0}, widths[GYS_SVCQ_ROUNDS] = {11, 11, 11, 11, 11, 9};
 	std::vector<unsigned long long> keys(npcts);
@@ -607,8 +594,8 @@ try {
 		uint64_t r = (uint64_t)std::ceil(pcts[i] * (double)ncand);
 		r = std::min<uint64_t>(std::max<uint64_t>(r, 1), ncand);
 		const uint32_t k = (uint32_t)(ncand - r + 1);
-		HIPCHK(hipMemsetAsync(c->q_misc + QM_PREFIX, 0, 8, c->stream));
-		HIPCHK(hipMemcpyAsync(c->q_misc + QM_WANT, &k, 4, hipMemcpyHostToDevice, c->stream));
+		HIPCHK(hipMemsetAsync(c->q_misc.p + QM_PREFIX, 0, 8, c->stream));
+		HIPCHK(hipMemcpyAsync(c->q_misc.p + QM_WANT, &k, 4, hipMemcpyHostToDevice, c->stream));
 		for (uint32_t rd = 0; rd < GYS_SVCQ_ROUNDS; ++rd) {
 			sp.shift = shifts[rd];
 			sp.bits = widths[rd];
@@ -616,7 +603,7 @@ try {
 			hipLaunchKernelGGL(k_svc_pick, dim3(1), dim3(256), 0, c->stream, sp);
 		}
 		HIPCHK(hipGetLastError());
-		HIPCHK(hipMemcpyAsync(&keys[i], c->q_misc + QM_PREFIX, 8, hipMemcpyDeviceToHost, c->stream));
+		HIPCHK(hipMemcpyAsync(&keys[i], c->q_misc.p + QM_PREFIX, 8, hipMemcpyDeviceToHost, c->stream));
 		HIPCHK(hipStreamSynchronize(c->stream)); // (k lives on this stack frame until its copy has been made)
 	}
 	for (uint32_t i = 0; i < npcts; ++i) out[i] = (int64_t)(int32_t)((uint32_t)(keys[i] >> 32) ^ 0x80000000u);
