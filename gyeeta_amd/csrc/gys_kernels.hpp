@@ -808,24 +808,8 @@ __global__ __launch_bounds__(256) void k_cms_reduce(const uint32_t *partial, uin
 //   SHARED: several workgroups may hold events of the same host (long segments cut into parts, a host named by two segments): buffer
 //           space is reserved with one device atomic per (tile, key) instead of an LDS cursor.
 //   SPILL:  second pass over the hosts that have spilled keys: only those keys' events, into their runs in `staged`.
-// RESP_TIME_HASH bucket of a response time through a 1 KiB LDS table (GYS_BUCKET_LUT; r3c: -0.09 ms per window): values below 1024 -- eleven of the
-// thirteen thresholds -- take one LDS read of four packed bucket numbers, the rest two compares; resp_bucket() costs 13 compare + add pairs
-#ifndef GYS_BUCKET_LUT
-#define GYS_BUCKET_LUT 1
-#endif
-// round 6: the instruction diet of the event phase, each step behind a switch of its own for A/B libraries (tools/ab_libs.sh)
-#ifndef GYS_SHIFT_SWITCH
-#define GYS_SHIFT_SWITCH 0 // (r6b: 5.40 ms with it, 5.32 - 5.33 without -- the scalar branches cost more than the 16 moves they save; left off) a group's results are stored at wd / lr[g .. g + 3] through a scalar branch on the (uniform) group number: 8 moves per group instead of the 24 of the shift by four
-#endif
-#ifndef GYS_PROBE_XOR
-#define GYS_PROBE_XOR 1 // listener probe: entry ^ (port << 16) < 0xFFFF and high word == netns; no tests for empty entries in the two-entry fast path (the table is insert-only: a key behind an empty entry cannot exist)
-#endif
-#ifndef GYS_BK_BYTES
-#define GYS_BK_BYTES 1 // RESP_TIME_HASH bucket table as 1024 bytes (one ds_read_u8 at min(t, 1023)) instead of 256 packed words + shift / mask
-#endif
-#ifndef GYS_PARK_INDEX
-#define GYS_PARK_INDEX 1 // the rank atomic of a place that kept nothing goes to s_ts[Lc_park + lane]: one select for the index, no select between two addresses
-#endif
+// RESP_TIME_HASH bucket of a response time through a 1 KiB LDS table: values below 1024 -- eleven of the thirteen thresholds -- take one LDS
+// byte read (ds_read_u8 at t & 1023), the rest two compares; resp_bucket() costs 13 compare + add pairs
 #ifndef GYS_EV_DMA
 #define GYS_EV_DMA 0 // (r6h / r6i: bit-exact and SLOWER -- 5.85 ms without, 6.22 ms with the requests one group ahead, against 5.24 - 5.39 ms; left off) (16 384-event tiles) a wave's events come in through LDS: six global_load_lds_dwordx4 per group of four event slots -- every 128-byte line of the wave's span requested ONCE, no destination registers -- into the wave's 6 KB of the (idle) tile-image area, then three 8-byte LDS reads per event.  r6g's counters: the vector-memory path stalls on pending lines half the time (TCP_PENDING_STALL_CYCLES 51 %, TD_TC_STALL 52 % of the kernel's cycles) with the strided 16 + 8-byte loads, which ask for every line twice
 #endif
@@ -842,38 +826,24 @@ __global__ __launch_bounds__(256) void k_cms_reduce(const uint32_t *partial, uin
 #define GYS_DMA16(gptr, ldsptr) memcpy((char *)(ldsptr) + 16u * (threadIdx.x & 63u), (const void *)(gptr), 16)
 #define GYS_DMA_WAIT() ((void)0)
 #endif
-#ifndef GYS_EV_PREFETCH
-#define GYS_EV_PREFETCH 0 // one load instruction per wave and group touches the 48 lines of the wave's NEXT group of events (a dword each, result unused): the demand loads of the next group then come from the L2 instead of HBM
-#endif
-#ifndef GYS_FLOOR_QUARTER
-#define GYS_FLOOR_QUARTER 1 // HLL floor: each tile re-reads a QUARTER of the register file (one 16-byte load per thread, issued before the flush's stores) and the floor is the minimum of the last four partial minima -- registers only grow, so an older minimum is still a lower bound -- instead of four loads per thread behind the stores
-#endif
-#ifndef GYS_HASH_FLAT
-#define GYS_HASH_FLAT 1 // the first hash half of the four events in straight-line code (no branch per event around it); an event with a 0.0.0.0 end or with all 18 rank bits zero goes through the rolled general path
-#endif
-#ifndef GYS_PROBE_JOINT
-#define GYS_PROBE_JOINT 0 // (r6b: 5.40 ms with it, 5.32 without; left off) third and later probes of the group's four events in ONE loop (one LDS round trip per step for all four, not one per event and step)
+#ifndef GYS_PARK_INDEX
+#define GYS_PARK_INDEX 1 // the rank atomic of a place that kept nothing goes to s_ts[Lc_park + lane]: one select for the index, no select between two addresses
 #endif
 __device__ __forceinline__ void resp_bucket_lut_init(uint32_t *s_bk, uint32_t tid, uint32_t nthreads)
 {
-	// (both table forms hold the same bytes: word i = buckets of 4 i .. 4 i + 3, little endian)
+	// (word i = buckets of 4 i .. 4 i + 3, little endian)
 	for (uint32_t i = tid; i < 256u; i += nthreads)
 		s_bk[i] = resp_bucket((int64_t)(4u * i)) | (resp_bucket((int64_t)(4u * i + 1u)) << 8) | (resp_bucket((int64_t)(4u * i + 2u)) << 16) |
 			  (resp_bucket((int64_t)(4u * i + 3u)) << 24);
 }
 __device__ __forceinline__ uint32_t resp_bucket_lut(const uint32_t *s_bk, uint32_t tresp)
 {
-	if (!GYS_BUCKET_LUT) return resp_bucket((int64_t)tresp);
-#if GYS_BK_BYTES
 	// (one ds_read_u8; the opaque statement keeps the compiler from turning it back into a word read + shift + mask)
 	uint32_t bix = tresp & 1023u;
 #if defined(__HIP_DEVICE_COMPILE__)
 	asm volatile("" : "+v"(bix));
 #endif
 	const uint32_t lo = ((const volatile uint8_t *)s_bk)[bix];
-#else
-	const uint32_t lo = (s_bk[(tresp >> 2) & 255u] >> ((tresp & 3u) * 8u)) & 0xFFu;
-#endif
 	const uint32_t hi = 12u + (tresp > 3000u) + (tresp > 15000u);
 	return tresp < 1024u ? lo : hi;
 }
@@ -952,41 +922,11 @@ __host__ __device__ __forceinline__ size_t resp_host_lds_bytes(uint32_t tbl_entr
 #ifndef GYS_RESP_DBG
 #define GYS_RESP_DBG 0 // 1: RespHostP.dbg switches parts of the kernel off (timing experiments only, tools/r3h_phases.sh)
 #endif
-#ifndef GYS_GH_PER_WAVE
-#define GYS_GH_PER_WAVE 0 // A/B: 1 = the cells per (wave, bucket) of rounds 1 - 3
-#endif
 #define GYS_GH_STRIDE 17u // cells per lane slot of the all-service histogram (15 buckets + the spare cell + 1: an odd stride)
 #define GYS_HQ_CAP 512u // HLL candidates queued per tile (late in a window ~0.1 % of a tile's events qualify; the queue is drained by the first GYS_HQ_CAP threads)
 #define GYS_DST_BIAS 65536ull // > the largest tile: (first word of a key's piece) - (start of its run in the image) + bias is positive
 #ifndef GYS_OPAQUE_LOADED4
 #define GYS_OPAQUE_LOADED4(a) asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]))
-#endif
-// the event words are read once: a non-temporal load leaves the L2 to the lines the flush is still filling (a key's piece of ~16 words ends inside
-// a 128-byte line that the key's next piece, one tile later, completes -- evicted in between, the line is written twice)
-#ifndef GYS_EV_NT
-#define GYS_EV_NT 0 // (r5f: 5.30 -> 5.80 ms with non-temporal event loads: the three 8-byte words of an event come from one line, the second and third read want it cached)
-#endif
-#ifndef GYS_EV_SADDR
-#define GYS_EV_SADDR 1 // (round 6: on, with the other steps of the diet; r5m measured it alone: (r5m: scalar tile base + one 32-bit offset per event -- the compiler then loads 16 + 8 bytes per event with one address register instead of three 64-bit addresses, 144 fewer static VALU instructions -- 5.28 / 5.29 against 5.33 / 5.30 ms: inside the noise; left off)
-#endif
-#ifndef GYS_EV_X3
-#define GYS_EV_X3 0 // (r5g: 5.27 -> 5.60 ms with two fully coalesced 12-byte loads per event + a DPP swap of halves between neighbouring lanes instead of the three strided 8-byte loads: the loads are not what the event phase waits for, the extra moves and registers cost more than the request efficiency gains)
-#endif
-struct __attribute__((packed, aligned(4))) Ev3 {
-	uint32_t x, y, z;
-};
-__device__ __forceinline__ uint32_t gys_swap_pair(uint32_t v) // the neighbouring lane's value (lanes 2j <-> 2j + 1): DPP quad_perm [1, 0, 3, 2]
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-	return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false);
-#else
-	return (uint32_t)__shfl_xor((int)v, 1, 64);
-#endif
-}
-#if GYS_EV_NT
-#define GYS_EV_LOAD(p) __builtin_nontemporal_load(p)
-#else
-#define GYS_EV_LOAD(p) (*(p))
 #endif
 #define GYS_MEM_FENCE() asm volatile("" ::: "memory") // compiler-only: memory operations are not moved across it (keeps a batch of LDS reads in front of the stores / the next batch)
 
@@ -996,10 +936,9 @@ __device__ __forceinline__ uint32_t gys_swap_pair(uint32_t v) // the neighbourin
 template <int TPT, bool SHARED, bool SPILL, bool SVCHLL, int MODE = 0>
 __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), GYS_RESP_WAVES_PER_SIMD(TPT)) void k_resp_host(RespHostP p_arg) // (4 waves per SIMD: one 1024-thread workgroup or two 512-thread ones per CU; TPT = 32: 2)
 {
-#ifndef GYS_RESP_KERNARG
-#define GYS_RESP_KERNARG 1 // the parameters are read from the kernel-argument segment where they are used (scalar loads), re-read per tile, instead of being held in SGPRs -- and spilled into VGPR lanes -- across the whole kernel
-#endif
-#if GYS_RESP_KERNARG && defined(__HIP_DEVICE_COMPILE__)
+	// the parameters are read from the kernel-argument segment where they are used (scalar loads), re-read per tile, instead of being held in
+	// SGPRs -- and spilled into VGPR lanes -- across the whole kernel; a host build (tests/cpp/kemu) takes the plain parameter
+#if defined(__HIP_DEVICE_COMPILE__)
 	typedef const RespHostP __attribute__((address_space(4))) *KernargP;
 	KernargP p_k = (KernargP)__builtin_amdgcn_kernarg_segment_ptr(); // (the only parameter: offset 0)
 #define GYS_RESP_P_RELOAD() asm volatile("" : "+s"(p_k))
@@ -1018,7 +957,7 @@ __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), GYS_RESP_WAVES_PER_SIMD(TPT)
 	__shared__ uint32_t s_wsum[T / 64];
 	__shared__ uint32_t s_drop[2];
 	__shared__ uint32_t s_floor[2]; // HLL floor of the even / odd tiles (refreshed per tile)
-	__shared__ uint32_t s_fqm[4];   // GYS_FLOOR_QUARTER: minimum of each quarter of the register file as last read (quarter q by the tiles with tile_no & 3 == q)
+	__shared__ uint32_t s_fqm[4];   // minimum of each quarter of the register file as last read (quarter q by the tiles with tile_no & 3 == q)
 	// all-service histogram of the window, packed count << 40 | sum per cell.  Round 4: the cells are per (LANE SLOT, bucket), not per (wave,
 	// bucket): the 64 lanes of one add hit at most 15 buckets, i.e. a handful of addresses each taken by many lanes, and LDS atomics on one
 	// address execute one after the other -- measured (profiles/r4b_lds_conflicts_by_access_and_stagger.txt) 36 % of the kernel's bank-conflict
@@ -1026,12 +965,12 @@ __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), GYS_RESP_WAVES_PER_SIMD(TPT)
 	// of 17 cells puts the 16 slots of a bucket on 16 different bank pairs.  (Same 2 KB of LDS as the per-wave form: the waves share the cells.)
 	__shared__ unsigned long long s_gh[16 * GYS_GH_STRIDE];
 	__shared__ int32_t s_gmax;
-	__shared__ uint32_t s_bk[GYS_BUCKET_LUT ? 256 : 1]; // (read as 1024 bytes with GYS_BK_BYTES)
+	__shared__ uint32_t s_bk[256]; // (read as 1024 bytes)
 	__shared__ uint32_t s_hq[SPILL ? 1 : GYS_HQ_CAP]; // the tile's HLL candidates: register index | rank << 16
 	__shared__ uint32_t s_hqn;
 	__shared__ FinWg s_fin;
 	__shared__ uint32_t s_park[64]; // the rank atomic of an event that is not kept lands here (one word per lane: no same-address serialisation)
-	if (GYS_BUCKET_LUT && !SPILL) resp_bucket_lut_init(s_bk, threadIdx.x, T);
+	if (!SPILL) resp_bucket_lut_init(s_bk, threadIdx.x, T);
 	const uint32_t Lc = p.lds_key_entries;
 	uint64_t *s_tbl = s_dyn;                            // [lds_tbl_entries + 2]
 	uint64_t *s_dst = s_dyn + p.lds_tbl_entries + 2u;   // [Lc] index into dst (+ GYS_DST_BIAS) the key's piece of the tile would have if it started at image entry 0 (0: piece dropped)
@@ -1108,9 +1047,6 @@ __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), GYS_RESP_WAVES_PER_SIMD(TPT)
 #ifdef GYS_RESP_TIMING
 	uint32_t tacc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 	unsigned long long t_prev__ = (unsigned long long)clock64();
-#endif
-#if GYS_EV_PREFETCH
-	uint32_t pf_sink = 0; // destination of the line-touching loads
 #endif
 	const uint32_t tid24 = 24u * tid;
 	int32_t tmax = INT32_MIN, wmax = -1;
@@ -1208,28 +1144,10 @@ __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), GYS_RESP_WAVES_PER_SIMD(TPT)
 						w0[u] = 0;
 						w1[u] = tb[GYS_EV6_WORDS * oo + 4u];
 						w2[u] = tb[GYS_EV6_WORDS * oo + 5u];
-					} else if (GYS_EV_X3) {
-						// Two 12-byte loads per lane instead of three 8-byte ones with a 24-byte stride: lane l of a wave reads HALF-events --
-						// load A the halves of the block's events 0..31 (lane 2j: first half of event j, lane 2j + 1: its second half), load B
-						// those of events 32..63 -- so every load instruction covers 768 contiguous bytes (six full lines; the strided form touches
-						// twelve lines per instruction and each line three times).  Neighbouring lanes then swap halves (DPP quad_perm): the even
-						// lane ends with event j, the odd lane with event 32 + j.
-						const uint32_t e_blk = (uint32_t)(g + u) * T + (tid & ~63u), par = lane & 1u;
-						const uint32_t ev_a = e_blk + (lane >> 1), ev_b = ev_a + 32u;
-						const Ev3 *hp = (const Ev3 *)tb;
-						const Ev3 a = hp[ev_a < rem ? 2u * ev_a + par : par], b = hp[ev_b < rem ? 2u * ev_b + par : par];
-						const uint32_t xa0 = gys_swap_pair(a.x), xa1 = gys_swap_pair(a.y), xa2 = gys_swap_pair(a.z);
-						const uint32_t xb0 = gys_swap_pair(b.x), xb1 = gys_swap_pair(b.y), xb2 = gys_swap_pair(b.z);
-						const uint32_t d0 = par ? xb0 : a.x, d1 = par ? xb1 : a.y, d2 = par ? xb2 : a.z; // first half: saddr, daddr, netns
-						const uint32_t d3 = par ? b.x : xa0, d4 = par ? b.y : xa1, d5 = par ? b.z : xa2; // second half: ports, lsndtime, lrcvtime
-						in[u] = (par ? ev_b : ev_a) < rem;
-						w0[u] = (uint64_t)d0 | ((uint64_t)d1 << 32);
-						w1[u] = (uint64_t)d2 | ((uint64_t)d3 << 32);
-						w2[u] = (uint64_t)d4 | ((uint64_t)d5 << 32);
 					} else if (DMA) {
 						in[u] = (uint32_t)(g + u) * T + tid < rem; // (the words are read from the wave's LDS area below, behind the requests of all four slots)
 						w0[u] = w1[u] = w2[u] = 0;
-					} else if (GYS_EV_SADDR) {
+					} else {
 						// the tile's base is uniform and an event's byte offset inside the tile fits 32 bits: written so, the three loads share ONE
 						// 32-bit offset register (scalar base + offset + immediate) instead of a 64-bit address each.  Round 6: the offset is
 						// 24 tid (kept) + 24 T (g + u) (scalar) -- no 32-bit multiply (a quarter-rate instruction) per event
@@ -1240,10 +1158,6 @@ __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), GYS_RESP_WAVES_PER_SIMD(TPT)
 						w0[u] = *(const uint64_t *)(tbb + ob);
 						w1[u] = *(const uint64_t *)(tbb + ob + 8u);
 						w2[u] = *(const uint64_t *)(tbb + ob + 16u);
-					} else {
-						w0[u] = GYS_EV_LOAD(&tb[3u * oo]);
-						w1[u] = GYS_EV_LOAD(&tb[3u * oo + 1u]);
-						w2[u] = GYS_EV_LOAD(&tb[3u * oo + 2u]);
 					}
 				}
 			}
@@ -1297,32 +1211,6 @@ __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), GYS_RESP_WAVES_PER_SIMD(TPT)
 			GYS_OPAQUE_LOADED4(w1);
 			GYS_OPAQUE_LOADED4(w2);
 			GYS_TICK(0); // group top: addresses, the event loads issued and arrived
-#if GYS_EV_PREFETCH && defined(__HIP_DEVICE_COMPILE__)
-			if (!PF && !V6 && !SPILL) {
-				// the wave's events of place u of a group are 64 consecutive 24-byte records = twelve 128-byte lines: lanes 0..47 touch one line
-				// each of the NEXT group (this tile's, or the first of the next tile).  Issued once this group's own loads HAVE ARRIVED (r6d: issued
-				// before that wait it was waited for as well -- the compiler's vmcnt(0) cannot tell it apart -- and cost 9 %): it runs under this group's
-				// work and is older than every load that is waited for later; nothing reads pf_sink
-				const uint32_t g2 = (uint32_t)g + 4u;
-				const uint64_t *nb = nullptr;
-				uint32_t nlim = 0, nfirst = 0;
-				if (g2 < (uint32_t)TPT && g2 * T < rem) {
-					nb = tb; nlim = rem; nfirst = g2 * T;
-				} else if (t0 + TILE < e1) {
-					const uint64_t left2 = e1 - t0 - TILE;
-					nb = tb + 3u * TILE; nlim = left2 < (uint64_t)TILE ? (uint32_t)left2 : TILE; nfirst = 0;
-				}
-				if (nb != nullptr && lane < 48u) {
-					const uint32_t pu = lane / 12u, pl = lane - 12u * pu;
-					const uint32_t ev0 = nfirst + pu * T + (tid & ~63u);           // first event of the wave's 64 in place pu
-					const uint32_t byte = 24u * ev0 + 128u * pl;                   // (the tile's base is 8-byte aligned only: "line" = 128-byte piece of the wave's span)
-					if (byte + 4u <= 24u * nlim) {
-						const char *pa = (const char *)nb + byte;
-						asm volatile("global_load_dword %0, %1, off" : "=v"(pf_sink) : "v"(pa) : "memory");
-					}
-				}
-			}
-#endif
 			// struct ipv4_tuple_t {u32 saddr, daddr, netns; u16 sport, dport;} + u32 lsndtime, lrcvtime  (24 bytes)
 			uint32_t tresp[4], local[4];
 			uint64_t ea[4], eb[4];
@@ -1349,7 +1237,6 @@ __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), GYS_RESP_WAVES_PER_SIMD(TPT)
 				// entry = netns : 32 | port : 16 | local index : 16 -- compared as two 32-bit words
 				const uint32_t netns = (uint32_t)w1[u], sport = (uint32_t)bswap16((uint16_t)(w1[u] >> 32));
 				const uint32_t alo = (uint32_t)ea[u], ahi = (uint32_t)(ea[u] >> 32), blo = (uint32_t)eb[u], bhi = (uint32_t)(eb[u] >> 32);
-#if GYS_PROBE_XOR
 				// low word of an entry = port << 16 | local: xor-ed with the event's port << 16 it IS the local index when the ports agree
 				// (< 0xFFFF: an empty entry -- all ones -- never matches, whatever the event's key).  The sub-tables are insert-only linear
 				// probing (host_tbl_put): a key found in the second entry implies a used first one, and a miss in both goes to the walk
@@ -1360,42 +1247,12 @@ __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), GYS_RESP_WAVES_PER_SIMD(TPT)
 				l = hit_a ? xa : l;
 				local[u] = l;
 				more[u] = ok[u] && !hit_a && !hit_b; // (r6t measured what a one-probe table would save with `&& !(DBG && (p.dbg & 64u))` here: 5.32 -> 5.11 ms)
-#else
-				const bool hit_a = ahi == netns && (alo >> 16) == sport, hit_b = bhi == netns && (blo >> 16) == sport;
-				const bool end_a = (alo & ahi) == 0xFFFFFFFFu, end_b = (blo & bhi) == 0xFFFFFFFFu;
-				uint32_t l = (hit_b && !end_a) ? (blo & 0xFFFFu) : GYS_NOSLOT;
-				l = hit_a ? (alo & 0xFFFFu) : l;
-				local[u] = l;
-				more[u] = ok[u] && !hit_a && !hit_b && !end_a && !end_b;
-#endif
 			}
 #ifdef GYS_RESP_TIMING
 			asm volatile("" : "+v"(local[0]), "+v"(local[1]), "+v"(local[2]), "+v"(local[3]));
 #endif
 			GYS_TICK(1); // hash, probe of two entries, compare
 			// third and later probes: 3 % of the events at a quarter-full table (one in eight at a half-full one)
-#if GYS_PROBE_JOINT
-			if (more[0] || more[1] || more[2] || more[3]) {
-				uint32_t hh[4];
-#pragma unroll
-				for (int u = 0; u < 4; ++u)
-					hh[u] = (host_tbl_slot(host_tbl_hash((uint32_t)w1[u], (uint32_t)bswap16((uint16_t)(w1[u] >> 32))), mask) + 2u) & mask;
-				for (uint32_t probes = 2; probes <= mask; ++probes) {
-					uint64_t e[4];
-#pragma unroll
-					for (int u = 0; u < 4; ++u) e[u] = s_tbl[hh[u]]; // (all four reads in flight together; a place that is done reads its last entry again)
-#pragma unroll
-					for (int u = 0; u < 4; ++u) {
-						const uint64_t key48 = ((uint64_t)(uint32_t)w1[u] << 16) | (uint64_t)bswap16((uint16_t)(w1[u] >> 32));
-						const bool hit = (e[u] >> 16) == key48 && e[u] != GYS_HOST_TBL_EMPTY;
-						if (more[u] && hit) local[u] = (uint32_t)(e[u] & 0xFFFFu);
-						more[u] = more[u] && !hit && e[u] != GYS_HOST_TBL_EMPTY;
-						hh[u] = more[u] ? ((hh[u] + 1u) & mask) : hh[u];
-					}
-					if (!(more[0] || more[1] || more[2] || more[3])) break;
-				}
-			}
-#else
 #pragma unroll
 			for (int u = 0; u < 4; ++u) {
 				if (more[u]) {
@@ -1412,7 +1269,6 @@ __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), GYS_RESP_WAVES_PER_SIMD(TPT)
 					}
 				}
 			}
-#endif
 #ifdef GYS_RESP_TIMING
 			asm volatile("" : "+v"(local[0]), "+v"(local[1]), "+v"(local[2]), "+v"(local[3]));
 #endif
@@ -1483,7 +1339,7 @@ __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), GYS_RESP_WAVES_PER_SIMD(TPT)
 				for (int u = 0; u < 4; ++u) {
 					// all-service histogram of the window (GY_HISTOGRAM::add_data on the aggregate): one packed LDS add per event
 					// (a place that kept nothing adds into the spare cell, which nobody reads: the add itself stays unconditional)
-					if (!(DBG && (p.dbg & 8u))) atomicAdd(&s_gh[(GYS_GH_PER_WAVE ? wave : (lane & 15u)) * GYS_GH_STRIDE + bk[u]], (1ull << 40) | (unsigned long long)tresp[u]);
+					if (!(DBG && (p.dbg & 8u))) atomicAdd(&s_gh[(lane & 15u) * GYS_GH_STRIDE + bk[u]], (1ull << 40) | (unsigned long long)tresp[u]);
 					// (largest response time through the staged word: value << GYS_ROW_BITS | row is monotone in the value and a place that kept
 					// nothing holds GYS_EV_DROPPED = -1 as a signed number -- one max per event, no select)
 					wmax = max(wmax, (int32_t)nwd[u]);
@@ -1502,7 +1358,6 @@ __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), GYS_RESP_WAVES_PER_SIMD(TPT)
 					// ends hash as 7 / 10 words; the per-service registers need all 64 bits) is rare or a non-default configuration and
 					// goes through ONE rolled copy of the general code below
 					if (DBG && (p.dbg & 4u)) {
-#if GYS_HASH_FLAT
 					} else if (!V6 && !SVCHLL) {
 						// flow_hll_idx_rank's common case without its branches: register index and the first 18 rank bits from the HIGH hash half,
 						// computed for every lane.  A 0.0.0.0 end (hashes as 7 / 10 words) or 18 zero rank bits (one event in 2^18: the low
@@ -1519,14 +1374,6 @@ __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), GYS_RESP_WAVES_PER_SIMD(TPT)
 						hidx[u] = up ? (hi >> (32 - GYS_HLL_P)) : 0u;
 						hrank[u] = up ? rk : 0u;
 						rare |= (kept[u] && !fast) ? (1u << u) : 0u;
-#else
-					} else if (!V6 && !SVCHLL && daddr != 0 && saddr != 0) {
-						uint32_t ix, rk;
-						flow_hll_idx_rank(daddr, dport, saddr, sport, &ix, &rk);
-						const bool up = kept[u] && rk > hll_floor; // (a rank at or below the floor cannot raise any register)
-						hidx[u] = up ? ix : 0u;
-						hrank[u] = up ? rk : 0u;
-#endif
 					} else if (kept[u]) {
 						rare |= 1u << u;
 					}
@@ -1537,7 +1384,7 @@ __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), GYS_RESP_WAVES_PER_SIMD(TPT)
 				for (uint32_t u = 0; u < 4u; ++u) {
 					if (!((rare >> u) & 1u)) continue;
 					// (the event this lane holds in place u of the group: see the load above)
-					const uint32_t o = (GYS_EV_X3 && !V6 && !PF) ? ((uint32_t)g + u) * T + (tid & ~63u) + (lane >> 1) + ((lane & 1u) ? 32u : 0u) : ((uint32_t)g + u) * T + tid;
+					const uint32_t o = ((uint32_t)g + u) * T + tid;
 					uint32_t idx, rank;
 					if (V6) {
 						const uint64_t a0 = tb[GYS_EV6_WORDS * o], a1 = tb[GYS_EV6_WORDS * o + 1u], d0 = tb[GYS_EV6_WORDS * o + 2u], d1 = tb[GYS_EV6_WORDS * o + 3u],
@@ -1601,21 +1448,6 @@ __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), GYS_RESP_WAVES_PER_SIMD(TPT)
 			}
 #pragma unroll
 			for (int u = 0; u < 4; ++u) nlr[u] |= kept[u] ? (rk12[u] << 12) : 0u;
-#if GYS_SHIFT_SWITCH
-			// the group's results go to places g .. g + 3: g is uniform, so this is one scalar branch into a block of eight moves (the empty
-			// asm statement keeps the blocks from being turned into 8 x TPT / 4 selects)
-#pragma unroll
-			for (int c = 0; c < TPT; c += 4) {
-				if (g == c) {
-					asm volatile("" ::: "memory");
-#pragma unroll
-					for (int u = 0; u < 4; ++u) {
-						wd[c + u] = nwd[u];
-						lr[c + u] = nlr[u];
-					}
-				}
-			}
-#else
 #pragma unroll
 			for (int j = 0; j + 4 < TPT; ++j) {
 				wd[j] = wd[j + 4];
@@ -1626,11 +1458,7 @@ __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), GYS_RESP_WAVES_PER_SIMD(TPT)
 				wd[TPT - 4 + u] = nwd[u];
 				lr[TPT - 4 + u] = nlr[u];
 			}
-#endif
 		}
-#if GYS_EV_PREFETCH && defined(__HIP_DEVICE_COMPILE__)
-		asm volatile("" ::"v"(pf_sink)); // (the register stays reserved across the group loop)
-#endif
 		GYS_TICK(5); // HLL queue, results stored, loop control
 		__syncthreads();
 		GYS_TICK(6); // barrier behind the event phase
@@ -1655,9 +1483,7 @@ __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), GYS_RESP_WAVES_PER_SIMD(TPT)
 				s_hqn = 0; // (every thread has read the queue length; the next event phase is two barriers away)
 				if (t0 + 2ull * TILE < e1) {
 					s_floor[tile_no & 1u] = 0xFFFFFFFFu; // (read by every thread at the top of this tile; refilled behind this tile's flush for tile t + 2)
-#if GYS_FLOOR_QUARTER
 					s_fqm[tile_no & 3u] = 0xFFFFFFFFu;   // (last read behind the previous tile's flush; refilled behind this tile's)
-#endif
 				}
 			}
 			{
@@ -1733,7 +1559,8 @@ __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), GYS_RESP_WAVES_PER_SIMD(TPT)
 			// consecutive image entries -> consecutive lanes -> consecutive addresses inside a key's piece.  8 entries per thread and round:
 			// keys and values of all eight, then the eight destinations, then the stores (two LDS round trips per round, not three per entry)
 			constexpr int FU = 8;
-#if GYS_FLOOR_QUARTER
+			// the next tiles' HLL floor: each tile re-reads a QUARTER of the register file (one 16-byte load per thread, issued before the flush's
+			// stores) and the floor is the minimum of the last four partial minima -- registers only grow, so an older minimum is still a lower bound
 			constexpr uint32_t NQ = (1u << GYS_HLL_P) / 16u / T; // 16-byte pieces of a quarter of the register file per thread (1 or 2)
 			uint4 fq[NQ];
 			const bool fq_on = !SPILL && t0 + 2ull * TILE < e1;
@@ -1741,7 +1568,6 @@ __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), GYS_RESP_WAVES_PER_SIMD(TPT)
 #pragma unroll
 				for (uint32_t j = 0; j < NQ; ++j) fq[j] = ((const uint4 *)p.hll32)[(tile_no & 3u) * ((1u << GYS_HLL_P) / 16u) + j * T + tid];
 			}
-#endif
 			for (uint32_t eb0 = 0; eb0 < ntile; eb0 += (uint32_t)FU * T) {
 				uint32_t kk[FU], vv[FU];
 				uint64_t dd[FU];
@@ -1762,7 +1588,6 @@ __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), GYS_RESP_WAVES_PER_SIMD(TPT)
 					if (e < ntile && dd[j]) dstb[dd[j] + e] = vv[j];
 				}
 			}
-#if GYS_FLOOR_QUARTER
 			if (fq_on) {
 				// quarter q of the register file was read by this tile; the slot (tile_no & 1) serves tile t + 2: min of this quarter's minimum
 				// and the running minima of the other quarters (s_fq[]: each at most four tiles old -- a lower bound all the same)
@@ -1776,21 +1601,6 @@ __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), GYS_RESP_WAVES_PER_SIMD(TPT)
 					atomicMin(&s_floor[tile_no & 1u], min(min(mn, s_fqm[(qn + 1u) & 3u]), min(s_fqm[(qn + 2u) & 3u], s_fqm[(qn + 3u) & 3u])));
 				}
 			}
-#else
-			// the next tile's HLL floor: the whole register file is re-read (L2 hits: every workgroup reads the same 64 KiB; behind the flush --
-			// held across it, the 16 registers of the four loads spill)
-			if (!SPILL && t0 + 2ull * TILE < e1) {
-				constexpr uint32_t NF = (1u << GYS_HLL_P) / 4u / T;
-				uint4 fv[NF];
-#pragma unroll
-				for (uint32_t j = 0; j < NF; ++j) fv[j] = ((const uint4 *)p.hll32)[tid + j * T];
-				uint32_t mn = 0xFFFFFFFFu;
-#pragma unroll
-				for (uint32_t j = 0; j < NF; ++j) mn = min(min(mn, min(fv[j].x, fv[j].y)), min(fv[j].z, fv[j].w));
-				mn = wave_min_u32(mn);
-				if (lane == 0) atomicMin(&s_floor[tile_no & 1u], mn);
-			}
-#endif
 		}
 		GYS_TICK(11); // flush + floor refresh
 		// (the next tile's event-phase barrier orders this tile's flush before destinations and image are rewritten)
@@ -2364,9 +2174,6 @@ __global__ __launch_bounds__(NT) void k_digest_merge(MergeP q)
 // consecutive bins touch at most two RESP_TIME_HASH buckets) instead of one contended LDS atomic per value.
 //   Weights are 32-bit here (total weight < 2^31: thresholds and mid-points fit a u32); an entry beyond that is handed to the
 //   general kernel through slow_list.
-#ifndef GYS_MB_PACKED
-#define GYS_MB_PACKED 1 // values accumulate into a packed {count, sum} word: one LDS atomic per value instead of two (r3c: -0.09 ms per window)
-#endif
 #ifndef GYS_MB_SKIP
 #define GYS_MB_SKIP 0 // TIMING EXPERIMENTS ONLY (results are wrong): 1 no per-bin pass, 2 no old-cluster / large-value placement, 4 no value pass 1,
 #endif                //   8 no bin scan, 16 no write-back, 32 nothing after the loads
@@ -2439,13 +2246,12 @@ __device__ __forceinline__ double td_quantile_dev(const uint32_t *c_cnt, const u
 #ifndef GYS_MB_WAVES16
 #define GYS_MB_WAVES16 5 // waves per SIMD the 4096-value instance is compiled for (8: 64 VGPRs -- sixteen values per thread then spill to scratch)
 #endif
-#ifndef GYS_MB_KERNARG
-#define GYS_MB_KERNARG 1 // the kernel's parameters are read from the kernel-argument segment where they are used (scalar loads, cached) instead of being held in ~90 SGPRs across the merge loop, which spilled 53 of them into VGPR lanes (170 v_readlane / v_writelane in the 2048-value instance)
-#endif
 template <bool SCAN, uint32_t VPT = 4u>
 __global__ __launch_bounds__(256, (VPT == 16u ? GYS_MB_WAVES16 : 8)) void k_digest_bins(MergeBP q_arg)
 {
-#if GYS_MB_KERNARG && defined(__HIP_DEVICE_COMPILE__)
+	// the parameters are read from the kernel-argument segment where they are used (scalar loads, cached) instead of being held in ~90 SGPRs
+	// across the merge loop, which spilled 53 of them into VGPR lanes; a host build (tests/cpp/kemu) takes the plain parameter
+#if defined(__HIP_DEVICE_COMPILE__)
 	typedef const MergeBP __attribute__((address_space(4))) *KernargP;
 	KernargP q_k = (KernargP)__builtin_amdgcn_kernarg_segment_ptr(); // (the only parameter: offset 0)
 #define GYS_MB_Q_RELOAD() asm volatile("" : "+s"(q_k))
@@ -2475,9 +2281,7 @@ __global__ __launch_bounds__(256, (VPT == 16u ? GYS_MB_WAVES16 : 8)) void k_dige
 	__shared__ uint32_t s_T[GYS_NBP];            // T_j, j = 1..NB-1; [0] = 0, [NB..] = ~0
 	__shared__ unsigned long long s_osum[GYS_TD_NB];
 	__shared__ uint32_t s_ocnt[GYS_TD_NB];
-#if GYS_MB_PACKED
-	__shared__ unsigned long long s_oval[GYS_TD_NB]; // the VALUES that land in an output cluster: {count : 24 | sum : 40}, one LDS atomic per value
-#endif
+	__shared__ unsigned long long s_oval[GYS_TD_NB]; // the VALUES that land in an output cluster: {count : 24 | sum : 40}, one LDS atomic per value instead of two
 	__shared__ unsigned long long s_fa[16], s_fw[16];
 	__shared__ uint32_t s_fbm[GYS_BM_WORDS];
 	__shared__ int32_t s_fmm[3];
@@ -2558,9 +2362,7 @@ __global__ __launch_bounds__(256, (VPT == 16u ? GYS_MB_WAVES16 : 8)) void k_dige
 		if (tid < GYS_TD_NB) {
 			s_osum[tid] = 0;
 			s_ocnt[tid] = 0;
-#if GYS_MB_PACKED
 			s_oval[tid] = 0;
-#endif
 		}
 		if (tid < 16u) {
 			s_fa[tid] = 0;
@@ -2718,10 +2520,6 @@ __global__ __launch_bounds__(256, (VPT == 16u ? GYS_MB_WAVES16 : 8)) void k_dige
 		__syncthreads();
 		const uint32_t nbig = s_nbig;
 		// ---- old clusters: preceded by the old weight before them and by the values below their mean
-#ifndef GYS_MB_FUSE_OLD
-#define GYS_MB_FUSE_OLD 0 // 1: the old cluster's threshold search runs in lockstep with the searches of the thread's first group of bins
-#endif
-		uint32_t mid2_old = 0;
 		const bool has_old = c0 && !(GYS_MB_SKIP & 2);
 		if (has_old) {
 			uint32_t nb = s_bin[mb_bin(thr)] & 0xFFFFu;
@@ -2733,16 +2531,12 @@ __global__ __launch_bounds__(256, (VPT == 16u ? GYS_MB_WAVES16 : 8)) void k_dige
 				}
 			}
 			const uint32_t mid2 = 2u * (e0 + nb) + c0;
-#if GYS_MB_FUSE_OLD
-			mid2_old = mid2; // (searched below, in lockstep with the thread's first group of bins)
-#else
 			uint32_t a = 0;
 #pragma unroll
 			for (uint32_t step = GYS_NBP / 2; step >= 1u; step >>= 1)
 				if (mid2 >= s_T[a + step]) a += step;
 			atomicAdd(&s_osum[a], (unsigned long long)sm0);
 			atomicAdd(&s_ocnt[a], c0);
-#endif
 		}
 		// ---- values, pass 2, PER BIN: the c values of a one-value bin are equal, so they take the consecutive mid-points
 		// first, first + 2, ... and only the cluster boundaries that fall between them matter: one threshold search per NON-EMPTY BIN
@@ -2752,15 +2546,12 @@ __global__ __launch_bounds__(256, (VPT == 16u ? GYS_MB_WAVES16 : 8)) void k_dige
 #define GYS_MB_GROUP 1u // the thread's four bins searched GROUP at a time (1, 2 or 4): with 2 / 4 the 8 dependent LDS reads of one threshold search overlap the others' -- measured in round 4 (profiles/r4a_ab_paired_search_and_tests.txt): 4.71 / 4.75 / 4.85 ms for 2 / 1 / 4 at full size, 1.265 / 1.255 / 1.281 at quarter size: no gain, the per-bin pass is not bound by that chain; 1 = the plain form stays the default
 #endif
 		constexpr uint32_t MBG = SCAN ? 1u : GYS_MB_GROUP; // (the scan form sits at 63 VGPRs: left as it was)
-#ifndef GYS_MB_COMPACT
-#define GYS_MB_COMPACT 1 // the per-bin pass walks a compacted list of the NON-EMPTY one-value bins
-#endif
 		// Round 5: of the 1 024 one-value bins a merge touches ~200 - 400 (integer-millisecond response times repeat), spread so that every
 		// wave of every one of the four rounds below has some non-empty bin among its 64 -- each round then runs the 8-step threshold search
 		// for the whole wave.  The non-empty bins are compacted first (four ballots per thread, wave totals through LDS, a 16-bit list in
 		// the unused upper half of the large-value list): ~300 bins are 5 wave-rounds instead of 16.  The kernel is bound by VALU issue
 		// (DESIGN 10): the instructions saved are time saved.  (A merge with more than half of the list's room in large values keeps the plain form.)
-		const bool compact = GYS_MB_COMPACT && MBG == 1u && !GYS_MB_FUSE_OLD && nbig <= BIG_CAP / 2u;
+		const bool compact = MBG == 1u && nbig <= BIG_CAP / 2u;
 		if (compact) {
 			uint16_t *const s_ne = (uint16_t *)(s_big + BIG_CAP / 2u); // [<= 1024] bin numbers
 			const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
@@ -2796,12 +2587,7 @@ __global__ __launch_bounds__(256, (VPT == 16u ? GYS_MB_WAVES16 : 8)) void k_dige
 				while (rem) { // (nearly always one round: a cluster spans far more mid-points than a bin's values)
 					const uint32_t Tn = s_T[a + 1u]; // first mid-point of the next cluster (~0 after the last)
 					const uint32_t kk = min(rem, (Tn - mid2 + 1u) >> 1); // values with mid2 + 2 r < Tn
-#if GYS_MB_PACKED
 					atomicAdd(&s_oval[a], ((unsigned long long)kk << 40) | (unsigned long long)(kk * b));
-#else
-					atomicAdd(&s_osum[a], (unsigned long long)(kk * b));
-					atomicAdd(&s_ocnt[a], kk);
-#endif
 					rem -= kk;
 					mid2 += 2u * kk;
 					++a;
@@ -2820,29 +2606,18 @@ __global__ __launch_bounds__(256, (VPT == 16u ? GYS_MB_WAVES16 : 8)) void k_dige
 				aq[u] = 0;
 				call |= cq[u];
 			}
-			const bool fuse = GYS_MB_FUSE_OLD && !SCAN && k0 == 0u;
-			if (!call && !(fuse && has_old)) continue;
-			uint32_t a_old = 0;
+			if (!call) continue;
 #pragma unroll
 			for (uint32_t step = GYS_NBP / 2; step >= 1u; step >>= 1) {
-				uint32_t tq[MBG], t_old = 0;
+				uint32_t tq[MBG];
 #pragma unroll
 				for (uint32_t u = 0; u < MBG; ++u) tq[u] = s_T[aq[u] + step];
-				if (fuse) t_old = s_T[a_old + step];
 #pragma unroll
 				for (uint32_t u = 0; u < MBG; ++u)
 					if (mq[u] >= tq[u]) aq[u] += step;
-				if (fuse && mid2_old >= t_old) a_old += step;
 			}
 #pragma unroll
 			for (uint32_t u = 0; u < MBG; ++u) GYS_OPAQUE_VGPR(aq[u]); // (the searches stay in this block: sunk into the `while (rem)` bodies below they would run one after the other)
-			if (fuse) {
-				GYS_OPAQUE_VGPR(a_old);
-				if (has_old) {
-					atomicAdd(&s_osum[a_old], (unsigned long long)sm0);
-					atomicAdd(&s_ocnt[a_old], c0);
-				}
-			}
 #pragma unroll
 			for (uint32_t u = 0; u < MBG; ++u) {
 				uint32_t rem = cq[u], mid2 = mq[u], a = aq[u];
@@ -2850,12 +2625,7 @@ __global__ __launch_bounds__(256, (VPT == 16u ? GYS_MB_WAVES16 : 8)) void k_dige
 				while (rem) { // (nearly always one round: a cluster spans far more mid-points than a bin's values)
 					const uint32_t Tn = s_T[a + 1u]; // first mid-point of the next cluster (~0 after the last)
 					const uint32_t kk = min(rem, (Tn - mid2 + 1u) >> 1); // values with mid2 + 2 r < Tn
-#if GYS_MB_PACKED
 					atomicAdd(&s_oval[a], ((unsigned long long)kk << 40) | (unsigned long long)(kk * b));
-#else
-					atomicAdd(&s_osum[a], (unsigned long long)(kk * b));
-					atomicAdd(&s_ocnt[a], kk);
-#endif
 					rem -= kk;
 					mid2 += 2u * kk;
 					++a;
@@ -2881,22 +2651,15 @@ __global__ __launch_bounds__(256, (VPT == 16u ? GYS_MB_WAVES16 : 8)) void k_dige
 #pragma unroll
 			for (uint32_t step = GYS_NBP / 2; step >= 1u; step >>= 1)
 				if (mid2 >= s_T[a + step]) a += step;
-#if GYS_MB_PACKED
 			atomicAdd(&s_oval[a], GYS_PACK_ONE | (unsigned long long)uv);
-#else
-			atomicAdd(&s_osum[a], (unsigned long long)uv);
-			atomicAdd(&s_ocnt[a], 1u);
-#endif
 		}
 		__syncthreads();
-#if GYS_MB_PACKED
 		if (tid < GYS_TD_NB) { // (own entry only; the consumers below read after their own barrier or read their own entry)
 			const unsigned long long pv = s_oval[tid];
 			s_osum[tid] += GYS_PACK_SUM(pv);
 			s_ocnt[tid] += (uint32_t)(pv >> 40);
 		}
 		if (SCAN) __syncthreads();
-#endif
 		} // (SCAN && m == 0)
 		if (SCAN) {
 			// ---- quantiles of the merged view: compact the non-empty clusters (order preserving), weight before each, one thread per quantile
@@ -3442,12 +3205,6 @@ __device__ __forceinline__ void conn_one(const ConnP &p, const ConnRec &rc, bool
 // SIXTEEN waves fit (r4x: 1.02 -> 0.98 ms).  A workgroup is 1024 threads and walks its span of records (conn_span) in rounds of 1024.
 #define GYS_CONN_STAGE_STRIDE 120u // bytes per staged record (112 used; 30 words: 8-byte accesses at this stride spread over all banks)
 #define GYS_CONN_UNITS 14u
-#ifndef GYS_CONN_PREFETCH
-#define GYS_CONN_PREFETCH 0 // 1: the units of round k + 1 are requested before round k is worked on (see k_conn_ingest)
-#endif
-#ifndef GYS_CONN_FLOOR
-#define GYS_CONN_FLOOR 1
-#endif
 // record offset of unit k: [64, 128) = nat_cli_, nat_ser_ (k = 0..7), 136 tusec_close_ (8), 144 cli_task_aggr_id_ (9), 208 bytes_sent_ (10),
 // 216 bytes_rcvd_ (11), 192 ser_glob_id_ (12), 272 the flag bytes (13)
 #define GYS_CONN_UNIT_OFF(k) ((k) < 8u ? 64u + 8u * (k) : 8u * (uint32_t)((0x22181B1A1211ull >> (((k) - 8u) * 8u)) & 0xFFull))
@@ -3464,9 +3221,8 @@ __global__ __launch_bounds__(GYS_CONN_THREADS) void k_conn_ingest(ConnP p)
 	__shared__ uint32_t s_tally[CONN_T_NUM + 3]; // (+ the table's fill count, + the HLL floor, + the parked candidates)
 	__shared__ __align__(16) uint8_t s_stage[GYS_CONN_THREADS / 64u][64u * GYS_CONN_STAGE_STRIDE];
 	uint32_t fl = 0xFFFFFFFFu;
-	if (!(GYS_CONN_SKIP & 1) && GYS_CONN_FLOOR)
+	if (!(GYS_CONN_SKIP & 1))
 		for (uint32_t k = threadIdx.x; k < (1u << GYS_HLL_P); k += GYS_CONN_THREADS) fl = min(fl, p.hll32[k]);
-	else if (!GYS_CONN_FLOOR) fl = 0; // (A/B: every record reads its register)
 	for (uint32_t k = threadIdx.x; k < GYS_CONN_AGG; k += GYS_CONN_THREADS) {
 		s_gid[k] = GYS_CONN_EMPTY;
 		s_acc[k][0] = 0;
@@ -3493,10 +3249,8 @@ __global__ __launch_bounds__(GYS_CONN_THREADS) void k_conn_ingest(ConnP p)
 	const uint32_t first = (uint32_t)first64, end = (uint32_t)min((uint64_t)p.n, first64 + p.span); // the workgroup's records [first, end)
 	// ---- 896 units of 8 bytes per wave and round: unit q = 14 r + k is bytes [GYS_CONN_UNIT_OFF(k), + 8) of the wave's record r, so that
 	// neighbouring lanes cover one record and a load instruction covers ~4.6 records (each lane reading its own record at the 280-byte stride
-	// was 3.3 ms, r3v).  GYS_CONN_PREFETCH 1 requests the units of round k + 1 right after round k's were stored to the LDS.  That paid at
-	// eight waves per CU (1.35 -> 1.29 ms, r4h); at twelve waves, with nothing in the walk waiting for a global read any more, the waves
-	// cover each other and the early request costs: 1.06 with, 1.02 ms without (r4v / r4w; the r4n kernel, whose walk read the HLL register
-	// and the glob_id table per record, was 1.05 with and 1.07 without) -- so it is off.
+	// was 3.3 ms, r3v).  A round's units are requested when the round is worked on, not a round ahead: with twelve and more waves per CU the
+	// waves cover each other and the early request costs (EXPERIMENTS.md, "Retired compile-time variants").
 	// The record offsets of a round are loaded one round before its units are requested: the unit addresses depend on them, and a load
 	// issued at request time put its whole latency in front of the fourteen unit loads (s_waitcnt vmcnt(0) before the first shuffle).
 	uint2 pc[GYS_CONN_UNITS];
@@ -3521,17 +3275,12 @@ __global__ __launch_bounds__(GYS_CONN_THREADS) void k_conn_ingest(ConnP p)
 		}
 	};
 	uint32_t off_nx = load_off(0);
-	if (GYS_CONN_PREFETCH) {
-		const uint32_t o = off_nx;
-		off_nx = load_off(1);
-		request(0, o);
-	}
 #pragma unroll 1
 	for (uint32_t round = 0;; ++round) {
 		const uint32_t i0 = first + round * GYS_CONN_THREADS + wave * 64u; // the wave's first record
 		if (i0 >= end) break;
 		const uint32_t i = i0 + lane;
-		if (!GYS_CONN_PREFETCH) {
+		{
 			const uint32_t o = off_nx;
 			off_nx = load_off(round + 1u);
 			request(round, o);
@@ -3542,11 +3291,6 @@ __global__ __launch_bounds__(GYS_CONN_THREADS) void k_conn_ingest(ConnP p)
 			const uint32_t r = (q * 4682u) >> 16;
 			const uint32_t k = q - r * GYS_CONN_UNITS;
 			*(uint64_t *)(st + r * GYS_CONN_STAGE_STRIDE + 8u * k) = (uint64_t)pc[t].x | ((uint64_t)pc[t].y << 32);
-		}
-		if (GYS_CONN_PREFETCH) {
-			const uint32_t o = off_nx;
-			off_nx = load_off(round + 2u);
-			request(round + 1u, o);
 		}
 		GYS_WAVE_SYNC();
 		{
