@@ -30,6 +30,7 @@
 #include "gys_kernels.hpp"
 #include "gys_rollup.hpp"
 #include "gys_groups.hpp"
+#include "gys_resp_plan.hpp"
 #include "gys_hllroll.hpp"
 #include "gys_histroll.hpp"
 #include "gys_huge.hpp"
@@ -96,6 +97,36 @@ struct DevBuf {
 		const int rc = grow(v.size(), stream);
 		if (rc) return rc;
 		if (!v.empty()) HIPCHK(hipMemcpyAsync(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, stream));
+		return GYS_OK;
+	}
+};
+
+// A pinned host buffer and a device buffer of the same `cap` elements: filled on the host, copied per batch.  grow() keeps a pair that is
+// large enough; otherwise it frees both and allocates anew (at least `floor` elements): the contents are NOT kept, and the caller knows
+// that nothing in flight reads the old ones.  The destructor frees.
+template <typename T>
+struct PinnedPair {
+	T *host = nullptr, *dev = nullptr;
+	size_t cap = 0;
+	PinnedPair() = default;
+	PinnedPair(const PinnedPair &) = delete;
+	PinnedPair &operator=(const PinnedPair &) = delete;
+	~PinnedPair() { release(); }
+	void release()
+	{
+		if (host) hipHostFree(host);
+		if (dev) hipFree(dev);
+		host = dev = nullptr;
+		cap = 0;
+	}
+	int grow(size_t n, size_t floor)
+	{
+		if (n <= cap) return GYS_OK;
+		release();
+		n = std::max(n, floor);
+		HIPCHK(hipHostMalloc((void **)&host, n * sizeof(T), hipHostMallocDefault));
+		HIPCHK(hipMalloc((void **)&dev, n * sizeof(T)));
+		cap = n;
 		return GYS_OK;
 	}
 };
@@ -284,7 +315,7 @@ struct gys_ctx {
 	uint32_t pcap = 0;
 	uint32_t pend_cap = GYS_TD_PEND_CAP, merge_fast = GYS_TDIGEST_MERGE_FAST; // the t-digest rule's buffer size (gys_config.td_pend_cap) and its fast merge class
 	MergeEnt *merge_list = nullptr, *merge_list_slow = nullptr, *merge_list1 = nullptr, *merge_list2 = nullptr, *huge_list = nullptr, *query_list = nullptr;
-	uint32_t *merge_count = nullptr; // [FIN_*]: merge list lengths by size class, huge list length, run allocation cursor; [8] = 1 (query list)
+	uint32_t *merge_count = nullptr; // [FIN_*]: the words of the FIN_* enum (gys_kernels.hpp); [FIN_QUERY_ONE] = 1 (query list)
 	uint32_t *resp_win = nullptr;    // per service: response events of the open window (-> Count-Min rows at the window boundary)
 	uint32_t *cms_partial = nullptr; // [cms_nch][GYS_CMS_D][GYS_CMS_W] partial rows of k_cms_partial
 	uint32_t cms_nch = 0;
@@ -329,14 +360,13 @@ struct gys_ctx {
 	// queued on the stream, so each call copies it into one of GYS_SEG_RING pinned host buffers (+ its own device buffer); a slot is
 	// reused only after the kernels that read it have finished (event)
 	struct SegSlot {
-		gys_resp_seg *host = nullptr, *dev = nullptr;
-		uint32_t cap = 0;
+		PinnedPair<gys_resp_seg> segs;
 		hipEvent_t done = nullptr;
-		// long segments cut into parts: the part descriptors (gys_resp_seg each)
-		uint8_t *xhost = nullptr, *xdev = nullptr;
-		uint64_t xcap = 0;
+		PinnedPair<gys_resp_seg> vsegs; // long segments cut into parts, many-listener hosts: the virtual segments
 	} seg_ring[GYS_SEG_RING];
 	uint32_t seg_next = 0;
+	std::vector<RespSegView> resp_sv; // the current batch as gys_resp_plan.hpp sees it (kept for their capacity)
+	std::vector<RespPartView> resp_pv;
 
 	// reduce arena + last-window results
 	uint8_t *arena = nullptr;
@@ -678,9 +708,8 @@ inline uint32_t host_part_of(uint64_t key48, uint32_t nparts) { return host_tbl_
 #define GYS_HOST_TBL_SPARSE 4096u
 inline uint32_t host_tbl_capacity(size_t n)
 {
-	static const uint32_t sparse = [] { const char *e = getenv("GYS_TBL_SPARSE"); return e ? (uint32_t)atoi(e) : GYS_HOST_TBL_SPARSE; }(); // (A/B: 0 = half full always)
 	const uint32_t c4 = next_pow2(std::max<uint64_t>(16, (uint64_t)n * 4));
-	return c4 <= sparse ? c4 : std::max<uint32_t>(std::min<uint32_t>(sparse, c4), next_pow2(std::max<uint64_t>(16, (uint64_t)n * 2)));
+	return c4 <= GYS_HOST_TBL_SPARSE ? c4 : std::max<uint32_t>(GYS_HOST_TBL_SPARSE, next_pow2(std::max<uint64_t>(16, (uint64_t)n * 2)));
 }
 
 // (re)uploads one sub-table, its slot list and its descriptor hdesc[desc]; regions only ever grow, an outgrown region is abandoned in
@@ -1094,106 +1123,105 @@ hipError_t resp_host_lds_attr(uint32_t *dyn_max)
 	return hipSuccess;
 }
 
-// resp pipeline on a device-resident batch
-// v6: the events are 48-byte tcp_ipv6_resp_event_t (handle_ipv6_resp_event, common/gy_socket_stat.cc:1535-1551)
-int run_resp_batch(gys_ctx *c, const gys_resp_seg *segs_host, uint32_t nsegs, const void *d_ev, uint64_t n, bool v6 = false)
+// ---- the response pipeline on a device-resident batch: run_resp_batch (below) is the list of these stages
+struct RespBatch {
+	const gys_resp_seg *segs_host;
+	uint32_t nsegs;
+	const void *d_ev;
+	uint64_t n;
+	bool v6; // the events are 48-byte tcp_ipv6_resp_event_t (handle_ipv6_resp_event, common/gy_socket_stat.cc:1535-1551)
+	bool td;
+	gys_ctx::SegSlot *slot = nullptr;
+	RespFront front;
+	int mode = 0;      // host-local: MODE of the k_resp_host instances
+	uint32_t tile = 0; // host-local: events per tile of the k_resp_host form (gys_resp_plan.hpp)
+	bool pre = false;  // predicted runs: only for the host-local front end, and only when the batch is large enough for a key to overflow a buffer at all
+	FinP fin{};
+	RespHostP hp{};
+	uint32_t hgrid = 0;
+	size_t dyn = 0;
+};
+
+int resp_check_segments(gys_ctx *c, const RespBatch &b)
 {
-	if (n == 0) return GYS_OK;
-	if (nsegs == 0 || !segs_host || segs_host[0].first_event != 0) {
+	if (b.nsegs == 0 || !b.segs_host || b.segs_host[0].first_event != 0) {
 		set_err("resp batch needs >= 1 segment starting at event 0");
 		return GYS_ERR_INVAL;
 	}
-	const bool td = c->cfg.enable_tdigest != 0;
-	if (td && n > c->cfg.max_batch_events) {
-		set_err("batch of %llu events exceeds max_batch_events %llu", (unsigned long long)n, (unsigned long long)c->cfg.max_batch_events);
+	if (b.td && b.n > c->cfg.max_batch_events) {
+		set_err("batch of %llu events exceeds max_batch_events %llu", (unsigned long long)b.n, (unsigned long long)c->cfg.max_batch_events);
 		return GYS_ERR_NOMEM;
 	}
-	if (n >= (1ull << 31)) {
+	if (b.n >= (1ull << 31)) {
 		set_err("batch too large (u32 offsets)");
 		return GYS_ERR_INVAL;
 	}
-	for (uint32_t s = 0; s < nsegs; ++s) {
-		if (segs_host[s].host_slot >= c->hosts.size() || segs_host[s].first_event > n || (s && segs_host[s].first_event < segs_host[s - 1].first_event)) {
+	for (uint32_t s = 0; s < b.nsegs; ++s) {
+		if (b.segs_host[s].host_slot >= c->hosts.size() || b.segs_host[s].first_event > b.n || (s && b.segs_host[s].first_event < b.segs_host[s - 1].first_event)) {
 			set_err("bad resp segment %u", s);
 			return GYS_ERR_INVAL;
 		}
 	}
+	return GYS_OK;
+}
+
+// the caller's segments into the next slot of the ring, and from there to the device
+int resp_upload_segments(gys_ctx *c, RespBatch &b)
+{
 	gys_ctx::SegSlot &slot = c->seg_ring[c->seg_next];
 	c->seg_next = (c->seg_next + 1) % GYS_SEG_RING;
+	b.slot = &slot;
 	if (!slot.done) HIPCHK(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
 	HIPCHK(hipEventSynchronize(slot.done)); // the batch that used this slot GYS_SEG_RING calls ago has consumed it
-	if (nsegs > slot.cap) {
-		if (slot.host) HIPCHK(hipHostFree(slot.host));
-		if (slot.dev) HIPCHK(hipFree(slot.dev));
-		slot.host = slot.dev = nullptr;
-		slot.cap = std::max<uint32_t>(nsegs, 1024);
-		HIPCHK(hipHostMalloc((void **)&slot.host, (uint64_t)slot.cap * sizeof(gys_resp_seg), hipHostMallocDefault));
-		HIPCHK(hipMalloc((void **)&slot.dev, (uint64_t)slot.cap * sizeof(gys_resp_seg)));
-	}
-	memcpy(slot.host, segs_host, (uint64_t)nsegs * sizeof(gys_resp_seg));
-	// `reserved` is the engine's own part-descriptor index (descriptor + 1, written only into the engine-built segment lists below): whatever
+	int rc = slot.segs.grow(b.nsegs, 1024);
+	if (rc) return rc;
+	memcpy(slot.segs.host, b.segs_host, (uint64_t)b.nsegs * sizeof(gys_resp_seg));
+	// `reserved` is the engine's own part-descriptor index (descriptor + 1, written only into the engine-built virtual segments): whatever
 	// the caller left in the field must never reach k_resp_host's hdesc[] lookup
-	for (uint32_t s = 0; s < nsegs; ++s) ((gys_resp_seg *)slot.host)[s].reserved = 0;
-	HIPCHK(hipMemcpyAsync(slot.dev, slot.host, (uint64_t)nsegs * sizeof(gys_resp_seg), hipMemcpyHostToDevice, c->stream));
-	const gys_resp_seg *segs_dev = slot.dev;
+	for (uint32_t s = 0; s < b.nsegs; ++s) slot.segs.host[s].reserved = 0;
+	HIPCHK(hipMemcpyAsync(slot.segs.dev, slot.segs.host, (uint64_t)b.nsegs * sizeof(gys_resp_seg), hipMemcpyHostToDevice, c->stream));
+	return GYS_OK;
+}
 
-	// ---- front end choice: host-local (one workgroup per host segment, LDS sub-table + tile-wise LDS counting sort straight into the
-	// services' value buffers) when every segment is a distinct host with an LDS-sized listener table; otherwise the general front end
-	bool host_local = td && c->cfg.resp_path != 1 && c->nsvc != 0, host_split = false, host_parts = false;
-	uint32_t max_tbl = 16, max_l = 1;
-	uint64_t max_len = 0, nwg = 0;
-	bool cands = false; // some host of the batch has keys with candidates: the instances that resolve them by the server address
-	if (host_local) {
-		c->batch_stamp++;
-		for (uint32_t s = 0; s < nsegs && host_local; ++s) {
-			const uint32_t host = segs_host[s].host_slot;
-			const HostListeners &hl = c->host_lst[host];
-			cands = cands || !hl.chain.empty();
-			const uint64_t len = (s + 1 < nsegs ? segs_host[s + 1].first_event : n) - segs_host[s].first_event;
-			if (c->host_seen[host] == c->batch_stamp || hl.overflow) host_local = false;
-			c->host_seen[host] = c->batch_stamp;
-			max_len = std::max(max_len, len);
-			if (hl.sub.empty()) {
-				if (!hl.on_device) host_local = false;
-				max_tbl = std::max<uint32_t>(max_tbl, (uint32_t)hl.tbl.size());
-				max_l = std::max<uint32_t>(max_l, (uint32_t)hl.slots.size());
-				nwg += 1;
-			} else { // a many-listener host: one workgroup per part of its listeners
-				host_parts = true;
-				for (const HostListeners &t : hl.sub) {
-					if (!t.on_device) host_local = false;
-					max_tbl = std::max<uint32_t>(max_tbl, (uint32_t)t.tbl.size());
-					max_l = std::max<uint32_t>(max_l, (uint32_t)t.slots.size());
-				}
-				nwg += hl.sub.size();
-			}
-		}
-		// few hosts with long segments: one workgroup per segment would leave most of the chip idle, so the segments are cut into parts
-		// of GYS_SPLIT_PART events (SHARED form: buffer space reserved with device atomics).  A workgroup walks ~0.35 G events/s.
-		const double t_host = (double)((nwg + c->ncu - 1) / c->ncu) * (double)max_len / 0.35e9;
-		const double t_split = (double)n * (double)std::max<uint64_t>(nwg, 1) / (double)std::max<uint32_t>(nsegs, 1) / 40.0e9 + 20e-6;
-		if (host_local && max_len > GYS_SPLIT_PART && (c->cfg.resp_path == 3 || (c->cfg.resp_path == 0 && t_split < t_host))) host_split = true;
+// front end and tile form of the batch (gys_resp_plan.hpp decides; this describes the segments' hosts to it)
+void resp_plan_front(gys_ctx *c, RespBatch &b)
+{
+	if (!b.td || c->nsvc == 0) return; // the general front end
+	c->batch_stamp++;
+	c->resp_sv.clear();
+	c->resp_pv.clear();
+	for (uint32_t s = 0; s < b.nsegs; ++s) {
+		const uint32_t host = b.segs_host[s].host_slot;
+		const HostListeners &hl = c->host_lst[host];
+		const uint64_t first = b.segs_host[s].first_event;
+		c->resp_sv.push_back(RespSegView{host, first, (s + 1 < b.nsegs ? b.segs_host[s + 1].first_event : b.n) - first, c->host_seen[host] == c->batch_stamp,
+						 hl.overflow, !hl.chain.empty(), (uint32_t)hl.sub.size(), (uint32_t)c->resp_pv.size(), hl.sub_desc});
+		c->host_seen[host] = c->batch_stamp;
+		if (hl.sub.empty()) c->resp_pv.push_back(RespPartView{(uint32_t)hl.tbl.size(), (uint32_t)hl.slots.size(), hl.on_device});
+		for (const HostListeners &t : hl.sub) c->resp_pv.push_back(RespPartView{(uint32_t)t.tbl.size(), (uint32_t)t.slots.size(), t.on_device});
 	}
-	const int mode = v6 ? 2 : cands ? 1 : 0;
-	const uint32_t nsvc = c->nsvc;
-	uint32_t *cms32 = (uint32_t *)(c->arena + c->al.off_u32) + c->al.u32_cms;
-	unsigned long long *ghist = (unsigned long long *)(c->arena + c->al.off_i64sum) + c->al.i64_ghist;
-	long long *gmax = (long long *)(c->arena + c->al.off_i64max);
-	if (td) {
-		HIPCHK(hipMemsetAsync(c->merge_count, 0, 8 * 4, c->stream)); // merge / huge / fallback list lengths, run allocation cursor ([8] is the constant 1 of the query list)
+	b.front = resp_front_choice(c->resp_sv.data(), b.nsegs, c->resp_pv.data(), b.n, c->ncu, c->cfg.resp_path);
+	if (!b.front.host_local) return;
+	b.mode = resp_mode(b.front, b.v6);
+	b.tile = resp_tile_events(b.mode, b.front.max_tbl, (uint32_t)align_up(b.front.max_l, 2), c->resp_dyn_max);
+	b.dyn = resp_host_lds_bytes(b.front.max_tbl, (uint32_t)align_up(b.front.max_l, 2), b.tile);
+	b.pre = c->prespill && b.n > (uint64_t)c->pcap - c->pend_cap;
+}
+
+// FinP (key finalize) and, for the host-local front end, RespHostP; clears the batch's words of merge_count
+int resp_fill_params(gys_ctx *c, RespBatch &b)
+{
+	FinP &fin = b.fin;
+	if (b.td) {
+		HIPCHK(hipMemsetAsync(c->merge_count, 0, FIN_BATCH_CLEARED * 4, c->stream)); // merge / huge / fallback list lengths, run allocation cursor
 		c->resp_dirty = true;
-	}
-	FinP fin{};
-	if (td) {
 		fin.td_cur = c->td_cur;
 		fin.td_meta = c->td_meta;
 		fin.nsvc = c->nsvc;
 		fin.pcap = c->pcap;
 		fin.pend_cap = c->pend_cap;
 		fin.merge_fast = c->merge_fast;
-		// Round 6: merges of 4097 .. 16 384 values (size class 2) through the streamed value-bin instance; GYS_CLASS2_HUGE: through the several-workgroup path as in rounds 3 - 5 (A/B)
-		static const bool class2_huge = getenv("GYS_CLASS2_HUGE") != nullptr || getenv("GYS_OLD_HUGE") != nullptr; // (GYS_OLD_HUGE's kernel does not read the fallback list the instance hands over to)
-		fin.class2_max = class2_huge ? 0u : GYS_MERGE_LDS_MAX;
+		fin.class2_max = GYS_MERGE_LDS_MAX; // merges of 4097 .. 16 384 values (size class 2) go through the streamed value-bin instance
 		fin.epoch = c->epoch;
 		fin.resp_win = c->resp_win;
 		fin.list[FIN_CLASS0] = c->merge_list;
@@ -1207,340 +1235,309 @@ int run_resp_batch(gys_ctx *c, const gys_resp_seg *segs_host, uint32_t nsegs, co
 		fin.counters = c->counters;
 		fin.staged_cap = (uint32_t)std::min<uint64_t>(c->staged_cap, 0xFFFFFFFFull);
 	}
-	// predicted runs: only for the host-local front end, and only when the batch is large enough for a key to overflow a buffer at all
-	const bool pre = td && host_local && c->prespill && n > (uint64_t)c->pcap - c->pend_cap;
-	if (td && c->prespill) {
+	if (b.td && c->prespill) {
 		fin.td_run0 = c->td_run0;
 		fin.td_run1 = c->td_run1;
 		fin.td_prevm = c->td_prevm;
 		fin.hot = c->pre_hot;
-		fin.hot_wr = pre ? ((c->pre_seq & 1u) ^ 1u) : (c->pre_seq & 1u); // the word the NEXT k_prespill reads (this batch's own one, if any, reads the other)
+		fin.hot_wr = b.pre ? ((c->pre_seq & 1u) ^ 1u) : (c->pre_seq & 1u); // the word the NEXT k_prespill reads (this batch's own one, if any, reads the other)
 		fin.append_list = c->append_list;
 		fin.append_cap = (uint32_t)c->append_cap;
 		fin.td_pend = c->td_pend;
 		fin.staged = c->staged;
-		HIPCHK(hipMemsetAsync(c->merge_count + FIN_APPEND, 0, 4 * 4, c->stream)); // ([12]: the append list's length; [14 .. 15]: the predicted runs' 64-bit reservation counter)
+		HIPCHK(hipMemsetAsync(c->merge_count + FIN_APPEND, 0, (FIN_NWORDS - FIN_APPEND) * 4, c->stream)); // (the append list's length; the predicted runs' reservation counter)
 	}
-	RespHostP hp{};
-	uint32_t hgrid = 0;
-	size_t dyn = 0;
-	// tile form: 512 threads x 12 events (6144-event tiles) when the batch's tables leave room for TWO such workgroups per CU (hosts of up
-	// to ~500 listeners: one workgroup's load / scan / flush phases run under the other's event phase -- r3t: 1.59 against 1.79 ms at 480
-	// listeners per host); else 1024 threads x 16 events (16384-event tiles, one workgroup per CU: 1000-listener hosts -- there the two-
-	// workgroup form needs half-full tables and 6-value pieces and loses, r3l / r3n); else 1024 x 8.  GYS_TPT = 8 / 12 / 16 pins a form (A/B).
-	static const int tpt = [] { const char *e = getenv("GYS_TPT"); const int v = e ? atoi(e) : 0; return (v == 8 || v == 12 || v == 16 || v == 32) ? v : 0; }();
-	bool tpt16 = false, tpt12 = false, tpt32 = false;
-	if (host_local) {
-		hp.ev = (const uint64_t *)d_ev;
-		hp.n = n;
-		hp.segs = segs_dev;
-		hp.nsegs = nsegs;
-		hp.hdesc = c->hdesc;
-		hp.htbl = c->htbl;
-		hp.hlst = c->hlst;
-		hp.cand = c->cand_pool;
-		hp.hll32 = c->hll32;
-		hp.td_cur = c->td_cur;
-		hp.td_pend = c->td_pend;
-		hp.pcap = c->pcap;
-		hp.td_run = c->td_run;
-		hp.td_run1 = c->td_run1;
-		hp.run_delta = (long long)(((intptr_t)c->staged - (intptr_t)c->td_pend) / 4);
-		hp.staged = c->staged;
-		hp.host_spill = c->host_spill;
-		hp.spill_stamp = ++c->spill_stamp;
-		fin.spill_stamp = hp.spill_stamp;
-		hp.fin = fin;
-		{
-			static const uint32_t dbg = [] { const char *e = getenv("GYS_DBG"); return e ? (uint32_t)atoi(e) : 0u; }();
-			hp.dbg = dbg;
-		}
-		hp.counters = c->counters;
-		hp.svc_hll = c->svc_hll;
-		hp.svc_hll_p = c->cfg.svc_hll_p;
-		hp.ghist = ghist;
-		hp.gmax = gmax;
-		hp.lds_tbl_entries = max_tbl;
-		hp.lds_key_entries = (uint32_t)align_up(max_l, 2);
-		hgrid = nsegs;
-		if (host_split || host_parts) {
-			// virtual segments: every segment cut into parts of GYS_SPLIT_PART events (host_split) and, for a many-listener host, one
-			// entry per part of its listeners (reserved = descriptor index + 1), the listener parts of one piece next to each other
-			uint64_t nparts = 0;
-			for (uint32_t s = 0; s < nsegs; ++s) {
-				const uint64_t len = (s + 1 < nsegs ? segs_host[s + 1].first_event : n) - segs_host[s].first_event;
-				const uint64_t pieces = host_split ? (len + GYS_SPLIT_PART - 1) / GYS_SPLIT_PART : (len ? 1 : 0);
-				nparts += pieces * std::max<size_t>(c->host_lst[segs_host[s].host_slot].sub.size(), 1);
-			}
-			const uint64_t xbytes = nparts * sizeof(gys_resp_seg);
-			if (xbytes > slot.xcap) {
-				if (slot.xhost) HIPCHK(hipHostFree(slot.xhost));
-				if (slot.xdev) HIPCHK(hipFree(slot.xdev));
-				slot.xhost = slot.xdev = nullptr;
-				slot.xcap = std::max<uint64_t>(xbytes, 1u << 16);
-				HIPCHK(hipHostMalloc((void **)&slot.xhost, slot.xcap, hipHostMallocDefault));
-				HIPCHK(hipMalloc((void **)&slot.xdev, slot.xcap));
-			}
-			gys_resp_seg *vseg = (gys_resp_seg *)slot.xhost;
-			uint64_t v = 0;
-			for (uint32_t s = 0; s < nsegs; ++s) {
-				const uint64_t first = segs_host[s].first_event;
-				const uint64_t len = (s + 1 < nsegs ? segs_host[s + 1].first_event : n) - first;
-				const HostListeners &hl = c->host_lst[segs_host[s].host_slot];
-				const uint64_t step = host_split ? (uint64_t)GYS_SPLIT_PART : std::max<uint64_t>(len, 1);
-				for (uint64_t q = 0; q * step < len; ++q) {
-					if (hl.sub.empty()) {
-						vseg[v++] = gys_resp_seg{segs_host[s].host_slot, 0u, first + q * step};
-					} else {
-						for (uint32_t lp = 0; lp < hl.sub.size(); ++lp)
-							vseg[v++] = gys_resp_seg{segs_host[s].host_slot, c->cfg.max_hosts + hl.sub_desc + lp + 1u, first + q * step};
-					}
-				}
-			}
-			HIPCHK(hipMemcpyAsync(slot.xdev, slot.xhost, v * sizeof(gys_resp_seg), hipMemcpyHostToDevice, c->stream));
-			hp.segs = (const gys_resp_seg *)slot.xdev;
-			hp.nsegs = (uint32_t)v;
-			hgrid = (uint32_t)v;
-			if (host_split) c->n_batches_host_split++;
-			else c->n_batches_host_local++;
-		} else {
-			c->n_batches_host_local++;
-		}
-		// (two workgroups per CU: each gets half of the CU's LDS -- resp_dyn_max is 160 KiB minus ONE static part)
-		tpt12 = mode == 0 && (tpt == 12 || tpt == 0) && resp_host_lds_bytes(max_tbl, hp.lds_key_entries, 6144u) + 160u * 1024u - c->resp_dyn_max <= 80u * 1024u;
-		tpt16 = !tpt12 && (mode != 0 || tpt == 16 || tpt == 32 || tpt == 0) && resp_host_lds_bytes(max_tbl, hp.lds_key_entries, 16384u) <= c->resp_dyn_max;
-		// GYS_TPT=32 (experiment): the fused first pass as 512 threads x 32 events with the next group's events prefetched into registers --
-		// the same 16 384-event tile and LDS layout as the 1024 x 16 form, which the split form and the second pass keep using
-		tpt32 = tpt16 && tpt == 32 && !host_split;
-		dyn = resp_host_lds_bytes(max_tbl, hp.lds_key_entries, tpt12 ? 6144u : tpt16 ? 16384u : 8192u);
-		if (pre) {
-			// runs for the keys whose last batch, repeated, would overflow their buffer (nothing but a flag read when no key was that large)
-			ProfScope ps(c, "prespill");
-			PreSpillP pp{};
-			pp.td_cur = c->td_cur;
-			pp.td_prevm = c->td_prevm;
-			pp.td_run = c->td_run;
-			pp.td_run0 = c->td_run0;
-			pp.td_run1 = c->td_run1;
-			pp.counts = c->merge_count;
-			pp.hot = c->pre_hot;
-			pp.hot_rd = c->pre_seq & 1u;
-			pp.svc_host = c->svc_host;
-			pp.host_batch = c->host_batch;
-			pp.batch_stamp = c->batch_stamp;
-			pp.nsvc = nsvc;
-			pp.pcap = c->pcap;
-			pp.pend_cap = c->pend_cap;
-			pp.resv = (unsigned long long *)(c->merge_count + 14); // (merge_count[14 .. 15]: cleared with the list lengths at the start of the batch)
-			pp.run_limit = (uint32_t)std::min<uint64_t>(c->staged_cap - std::min<uint64_t>(n, c->staged_cap), 0xFFFFFFFFull); // the exact runs of the fall-back (<= n words) keep their room
-			++c->pre_seq;
-			hipLaunchKernelGGL(k_mark_hosts, dim3((nsegs + 255) / 256), dim3(256), 0, c->stream, segs_dev, nsegs, c->host_batch, c->batch_stamp);
-			hipLaunchKernelGGL(k_prespill, dim3((nsvc + 255) / 256), dim3(256), 0, c->stream, pp);
-		}
-		{
-			ProfScope ps(c, "resp_host");
-			if (mode != 0) {
-				if (host_split) launch_resp_host_mode<true, false>(c, mode, tpt16, hgrid, dyn, hp);
-				else launch_resp_host_mode<false, false>(c, mode, tpt16, hgrid, dyn, hp);
-			} else if (host_split) {
-				if (tpt12) launch_resp_host<12, true, false>(c, hgrid, dyn, hp);
-				else if (tpt16) launch_resp_host<16, true, false>(c, hgrid, dyn, hp);
-				else launch_resp_host<8, true, false>(c, hgrid, dyn, hp);
-			} else {
-				if (tpt12) launch_resp_host<12, false, false>(c, hgrid, dyn, hp);
-				else if (tpt32) launch_resp_host<32, false, false>(c, hgrid, dyn, hp);
-				else if (tpt16) launch_resp_host<16, false, false>(c, hgrid, dyn, hp);
-				else launch_resp_host<8, false, false>(c, hgrid, dyn, hp);
-			}
-		}
+	if (!b.front.host_local) return GYS_OK;
+	RespHostP &hp = b.hp;
+	hp.ev = (const uint64_t *)b.d_ev;
+	hp.n = b.n;
+	hp.segs = b.slot->segs.dev;
+	hp.nsegs = b.nsegs;
+	hp.hdesc = c->hdesc;
+	hp.htbl = c->htbl;
+	hp.hlst = c->hlst;
+	hp.cand = c->cand_pool;
+	hp.hll32 = c->hll32;
+	hp.td_cur = c->td_cur;
+	hp.td_pend = c->td_pend;
+	hp.pcap = c->pcap;
+	hp.td_run = c->td_run;
+	hp.td_run1 = c->td_run1;
+	hp.run_delta = (long long)(((intptr_t)c->staged - (intptr_t)c->td_pend) / 4);
+	hp.staged = c->staged;
+	hp.host_spill = c->host_spill;
+	hp.spill_stamp = ++c->spill_stamp;
+	fin.spill_stamp = hp.spill_stamp;
+	hp.fin = fin;
+	static const uint32_t dbg = [] { const char *e = getenv("GYS_DBG"); return e ? (uint32_t)atoi(e) : 0u; }();
+	hp.dbg = dbg;
+	hp.counters = c->counters;
+	hp.svc_hll = c->svc_hll;
+	hp.svc_hll_p = c->cfg.svc_hll_p;
+	hp.ghist = (unsigned long long *)(c->arena + c->al.off_i64sum) + c->al.i64_ghist;
+	hp.gmax = (long long *)(c->arena + c->al.off_i64max);
+	hp.lds_tbl_entries = b.front.max_tbl;
+	hp.lds_key_entries = (uint32_t)align_up(b.front.max_l, 2);
+	b.hgrid = b.nsegs;
+	return GYS_OK;
+}
+
+// the mode-0 k_resp_host instance of the batch's tile form
+template <bool SHARED, bool SPILL>
+void launch_resp_host_tile(gys_ctx *c, const RespBatch &b)
+{
+	if (b.tile == 6144u) return launch_resp_host<12, SHARED, SPILL>(c, b.hgrid, b.dyn, b.hp);
+	if (b.tile == 16384u) launch_resp_host<16, SHARED, SPILL>(c, b.hgrid, b.dyn, b.hp);
+	else launch_resp_host<8, SHARED, SPILL>(c, b.hgrid, b.dyn, b.hp);
+}
+
+// host-local front end: the virtual segments of the split / parts forms, the predicted runs, k_resp_host
+int resp_launch_host_local(gys_ctx *c, RespBatch &b)
+{
+	if (b.front.host_split || b.front.host_parts) {
+		PinnedPair<gys_resp_seg> &vs = b.slot->vsegs;
+		const uint64_t nv = resp_virtual_segments(c->resp_sv.data(), b.nsegs, b.front.host_split, c->cfg.max_hosts, nullptr);
+		int rc = vs.grow(nv, (1u << 16) / sizeof(gys_resp_seg));
+		if (rc) return rc;
+		resp_virtual_segments(c->resp_sv.data(), b.nsegs, b.front.host_split, c->cfg.max_hosts, vs.host);
+		HIPCHK(hipMemcpyAsync(vs.dev, vs.host, nv * sizeof(gys_resp_seg), hipMemcpyHostToDevice, c->stream));
+		b.hp.segs = vs.dev;
+		b.hp.nsegs = b.hgrid = (uint32_t)nv;
+	}
+	if (b.front.host_split) c->n_batches_host_split++;
+	else c->n_batches_host_local++;
+	if (b.pre) {
+		// runs for the keys whose last batch, repeated, would overflow their buffer (nothing but a flag read when no key was that large)
+		ProfScope ps(c, "prespill");
+		PreSpillP pp{};
+		pp.td_cur = c->td_cur;
+		pp.td_prevm = c->td_prevm;
+		pp.td_run = c->td_run;
+		pp.td_run0 = c->td_run0;
+		pp.td_run1 = c->td_run1;
+		pp.counts = c->merge_count;
+		pp.hot = c->pre_hot;
+		pp.hot_rd = c->pre_seq & 1u;
+		pp.svc_host = c->svc_host;
+		pp.host_batch = c->host_batch;
+		pp.batch_stamp = c->batch_stamp;
+		pp.nsvc = c->nsvc;
+		pp.pcap = c->pcap;
+		pp.pend_cap = c->pend_cap;
+		pp.resv = (unsigned long long *)(c->merge_count + FIN_PRE_RESV); // (cleared at the start of the batch)
+		pp.run_limit = (uint32_t)std::min<uint64_t>(c->staged_cap - std::min<uint64_t>(b.n, c->staged_cap), 0xFFFFFFFFull); // the exact runs of the fall-back (<= n words) keep their room
+		++c->pre_seq;
+		hipLaunchKernelGGL(k_mark_hosts, dim3((b.nsegs + 255) / 256), dim3(256), 0, c->stream, b.slot->segs.dev, b.nsegs, c->host_batch, c->batch_stamp);
+		hipLaunchKernelGGL(k_prespill, dim3((c->nsvc + 255) / 256), dim3(256), 0, c->stream, pp);
+	}
+	ProfScope ps(c, "resp_host");
+	if (b.mode != 0) {
+		if (b.front.host_split) launch_resp_host_mode<true, false>(c, b.mode, b.tile == 16384u, b.hgrid, b.dyn, b.hp);
+		else launch_resp_host_mode<false, false>(c, b.mode, b.tile == 16384u, b.hgrid, b.dyn, b.hp);
+	} else if (b.front.host_split) {
+		launch_resp_host_tile<true, false>(c, b);
 	} else {
-		c->n_batches_general++;
-		RespP1 p{};
-		p.ev = (const uint64_t *)d_ev;
-		p.cand = c->cand_pool;
-		p.n = n;
-		p.segs = segs_dev;
-		p.nsegs = nsegs;
-		p.lk = c->lk_tbl;
-		p.svc_gid = c->svc_gid;
-		p.hist_win = c->hist_win;
-		p.bitmap = c->bitmap;
-		p.hll32 = c->hll32;
-		p.cms32 = cms32;
-		p.batch_cnt = td ? c->batch_cnt : nullptr;
-		p.ev_kv = td ? c->ev_kv : nullptr;
-		p.counters = c->counters;
-		p.svc_hll = c->svc_hll;
-		p.svc_hll_p = c->cfg.svc_hll_p;
-		p.ghist = ghist;
-		p.gmax = gmax;
-		{
-			ProfScope ps(c, "resp_pass1");
-			if (v6) hipLaunchKernelGGL(k_resp_pass1<true>, dim3(grid_for(n, 256, (uint32_t)c->ncu * 8)), dim3(256), 0, c->stream, p);
-			else hipLaunchKernelGGL(k_resp_pass1<false>, dim3(grid_for(n, 256, (uint32_t)c->ncu * 8)), dim3(256), 0, c->stream, p);
-		}
-		HIPCHK(hipGetLastError());
-		if (!td || nsvc == 0) {
-			HIPCHK(hipEventRecord(slot.done, c->stream));
-			return GYS_OK;
-		}
-		const uint32_t nblk = (nsvc + GYS_SCAN_TILE - 1) / GYS_SCAN_TILE;
-		{
-			ProfScope ps(c, "scan");
-			hipLaunchKernelGGL(k_scan_block_sums, dim3(nblk), dim3(256), 0, c->stream, c->batch_cnt, nsvc, c->scan_block_sums);
-			hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(256), 0, c->stream, c->scan_block_sums, nblk);
-			hipLaunchKernelGGL(k_scan_final, dim3(nblk), dim3(256), 0, c->stream, c->batch_cnt, nsvc, c->scan_block_sums, c->batch_off);
-		}
-		{
-			ProfScope ps(c, "scatter");
-			hipLaunchKernelGGL(k_resp_scatter, dim3(grid_for(n, 256, (uint32_t)c->ncu * 8)), dim3(256), 0, c->stream, c->ev_kv, n, c->batch_off, c->staged);
-		}
-		{
-			ProfScope ps(c, "key_append");
-			AppendP ap{};
-			ap.batch_cnt = c->batch_cnt;
-			ap.off_end = c->batch_off;
-			ap.staged = c->staged;
-			ap.td_cur = c->td_cur;
-			ap.td_pend = c->td_pend;
-			ap.pcap = c->pcap;
-			ap.nsvc = nsvc;
-			const uint32_t nchunks = (nsvc + 63u) / 64u;
-			hipLaunchKernelGGL(k_key_append, dim3(std::min<uint32_t>((nchunks + 3u) / 4u, (uint32_t)c->ncu * 8)), dim3(256), 0, c->stream, ap);
-		}
+		launch_resp_host_tile<false, false>(c, b);
 	}
-	HIPCHK(hipGetLastError());
-	if (!host_local || host_split) { // (the fused host-local form finalizes its keys in the tail of k_resp_host)
+	return GYS_OK;
+}
+
+// general front end, first pass: the per-event sketches; with t-digests also the events' (key, value) pairs and the keys' counts
+void resp_launch_pass1(gys_ctx *c, const RespBatch &b)
+{
+	c->n_batches_general++;
+	RespP1 p{};
+	p.ev = (const uint64_t *)b.d_ev;
+	p.cand = c->cand_pool;
+	p.n = b.n;
+	p.segs = b.slot->segs.dev;
+	p.nsegs = b.nsegs;
+	p.lk = c->lk_tbl;
+	p.svc_gid = c->svc_gid;
+	p.hist_win = c->hist_win;
+	p.bitmap = c->bitmap;
+	p.hll32 = c->hll32;
+	p.cms32 = (uint32_t *)(c->arena + c->al.off_u32) + c->al.u32_cms;
+	p.batch_cnt = b.td ? c->batch_cnt : nullptr;
+	p.ev_kv = b.td ? c->ev_kv : nullptr;
+	p.counters = c->counters;
+	p.svc_hll = c->svc_hll;
+	p.svc_hll_p = c->cfg.svc_hll_p;
+	p.ghist = (unsigned long long *)(c->arena + c->al.off_i64sum) + c->al.i64_ghist;
+	p.gmax = (long long *)(c->arena + c->al.off_i64max);
+	ProfScope ps(c, "resp_pass1");
+	if (b.v6) hipLaunchKernelGGL(k_resp_pass1<true>, dim3(grid_for(b.n, 256, (uint32_t)c->ncu * 8)), dim3(256), 0, c->stream, p);
+	else hipLaunchKernelGGL(k_resp_pass1<false>, dim3(grid_for(b.n, 256, (uint32_t)c->ncu * 8)), dim3(256), 0, c->stream, p);
+}
+
+// general front end, the rest: the values sorted by key into `staged`, the keys' runs appended to their buffers
+void resp_launch_general(gys_ctx *c, const RespBatch &b)
+{
+	const uint32_t nsvc = c->nsvc, nblk = (nsvc + GYS_SCAN_TILE - 1) / GYS_SCAN_TILE;
+	{
+		ProfScope ps(c, "scan");
+		hipLaunchKernelGGL(k_scan_block_sums, dim3(nblk), dim3(256), 0, c->stream, c->batch_cnt, nsvc, c->scan_block_sums);
+		hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(256), 0, c->stream, c->scan_block_sums, nblk);
+		hipLaunchKernelGGL(k_scan_final, dim3(nblk), dim3(256), 0, c->stream, c->batch_cnt, nsvc, c->scan_block_sums, c->batch_off);
+	}
+	{
+		ProfScope ps(c, "scatter");
+		hipLaunchKernelGGL(k_resp_scatter, dim3(grid_for(b.n, 256, (uint32_t)c->ncu * 8)), dim3(256), 0, c->stream, c->ev_kv, b.n, c->batch_off, c->staged);
+	}
+	ProfScope ps(c, "key_append");
+	AppendP ap{};
+	ap.batch_cnt = c->batch_cnt;
+	ap.off_end = c->batch_off;
+	ap.staged = c->staged;
+	ap.td_cur = c->td_cur;
+	ap.td_pend = c->td_pend;
+	ap.pcap = c->pcap;
+	ap.nsvc = nsvc;
+	const uint32_t nchunks = (nsvc + 63u) / 64u;
+	hipLaunchKernelGGL(k_key_append, dim3(std::min<uint32_t>((nchunks + 3u) / 4u, (uint32_t)c->ncu * 8)), dim3(256), 0, c->stream, ap);
+}
+
+// what follows either front end: the keys finalized (queued for their merges), predicted runs that fit after all, the second pass
+void resp_launch_finalize(gys_ctx *c, RespBatch &b)
+{
+	const bool host_local = b.front.host_local;
+	if (!host_local || b.front.host_split) { // (the fused host-local form finalizes its keys in the tail of k_resp_host)
 		ProfScope ps(c, "key_finalize");
-		fin.batch_off = host_local ? nullptr : c->batch_off;
-		hipLaunchKernelGGL(k_key_finalize, dim3((nsvc + 255) / 256), dim3(256), 0, c->stream, fin);
+		b.fin.batch_off = host_local ? nullptr : c->batch_off;
+		hipLaunchKernelGGL(k_key_finalize, dim3((c->nsvc + 255) / 256), dim3(256), 0, c->stream, b.fin);
 	}
-	if (pre) // keys whose predicted run fits their buffer after all: the run is copied behind the buffered values (before the merges read either)
+	if (b.pre) // keys whose predicted run fits their buffer after all: the run is copied behind the buffered values (before the merges read either)
 		hipLaunchKernelGGL(k_run_append, dim3((uint32_t)c->ncu), dim3(256), 0, c->stream, c->append_list, c->merge_count + FIN_APPEND, c->staged, c->td_pend, c->pcap);
 	// (a key spills / lands in a larger merge class only when THIS batch brought it more values than its buffer had room for: a small
 	// batch -- a partha message of a few thousand events -- cannot, and the launches for those cases are not made)
-	if (host_local && n > (uint64_t)c->pcap - c->pend_cap) {
+	if (host_local && b.n > (uint64_t)c->pcap - c->pend_cap) {
 		// second pass over the hosts that have spilled services (a workgroup of any other host returns at once): their events again,
 		// only the spilled services' values, into the runs k_key_finalize allocated in `staged`
 		ProfScope ps(c, "resp_spill");
-		if (mode != 0) launch_resp_host_mode<true, true>(c, mode, tpt16, hgrid, dyn, hp);
-		else if (tpt12) launch_resp_host<12, true, true>(c, hgrid, dyn, hp);
-		else if (tpt16) launch_resp_host<16, true, true>(c, hgrid, dyn, hp);
-		else launch_resp_host<8, true, true>(c, hgrid, dyn, hp);
+		if (b.mode != 0) launch_resp_host_mode<true, true>(c, b.mode, b.tile == 16384u, b.hgrid, b.dyn, b.hp);
+		else launch_resp_host_tile<true, true>(c, b);
+	}
+}
+
+// the slow list through the general kernel, in the instance that holds the largest merge of size class `top`
+void resp_launch_slow_pass(gys_ctx *c, const DigestP &d, uint32_t cap, int top)
+{
+	MergeP mp{};
+	mp.d = d;
+	mp.list = c->merge_list_slow;
+	mp.count = c->merge_count + FIN_SLOW;
+	const dim3 grid(std::max(1u, std::min<uint32_t>(cap, (uint32_t)c->ncu)));
+	if (top == 2) hipLaunchKernelGGL((k_digest_merge<GYS_MERGE_LDS_MAX, 1024u>), grid, dim3(1024), 0, c->stream, mp);
+	else if (top == 0 && c->merge_fast <= GYS_MERGE_CLASS0) hipLaunchKernelGGL((k_digest_merge<GYS_MERGE_CLASS0, 256u>), grid, dim3(256), 0, c->stream, mp);
+	else hipLaunchKernelGGL((k_digest_merge<GYS_MERGE_CLASS1, 256u>), grid, dim3(256), 0, c->stream, mp);
+}
+
+// the merges of the keys the batch queued, by size class.  The value-bin launches run for the classes the batch can reach (a key lands in
+// class 1 / 2 only when THIS batch brought it more values than the class below holds).  Then exactly ONE pass of the general kernel over the
+// slow list -- what a value-bin launch handed over: entries whose total weight needs 64-bit arithmetic, or with more large values than the
+// bin kernel's list holds (normally none) -- behind the last value-bin launch, so that an entry is merged once; its instance is the one
+// of the highest class reached.  (Entries above class 2 take the several-workgroup path, resp_launch_huge.)
+void resp_launch_merges(gys_ctx *c, const RespBatch &b)
+{
+	const uint32_t nsvc = c->nsvc, ncu = (uint32_t)c->ncu;
+	const uint32_t cap = (uint32_t)std::min<uint64_t>(nsvc, b.n);
+	const bool reach[3] = {true, c->merge_fast < GYS_MERGE_CLASS1 && b.n > c->merge_fast - c->pend_cap, b.n > GYS_MERGE_CLASS1 - c->pend_cap};
+	const int top = reach[2] ? 2 : reach[1] ? 1 : 0;
+	MergeEnt *const lists[3] = {c->merge_list, c->merge_list1, c->merge_list2};
+	MergeBP bp{};
+	bp.d = digest_params(c);
+	bp.slow_list = c->merge_list_slow;
+	bp.slow_count = c->merge_count + FIN_SLOW;
+	for (int cls = 0; cls < 3; ++cls) {
+		if (!reach[cls]) continue;
+		ProfScope ps(c, cls ? "digest_merge_big" : "digest_merge");
+		bp.list = lists[cls];
+		bp.count = c->merge_count + FIN_CLASS0 + cls;
+		if (cls == 0) {
+			const dim3 bgrid(std::max(1u, std::min<uint32_t>(cap, ncu * 8)));
+			if (c->merge_fast <= 1024u) hipLaunchKernelGGL((k_digest_bins<false, 4u>), bgrid, dim3(256), 0, c->stream, bp);
+			else if (c->merge_fast <= 2048u) hipLaunchKernelGGL((k_digest_bins<false, 8u>), bgrid, dim3(256), 0, c->stream, bp);
+			else hipLaunchKernelGGL((k_digest_bins<false, 16u>), bgrid, dim3(256), 0, c->stream, bp);
+		} else if (cls == 1) { // up to 4096 values: the same exact-integer definition, bit-identical
+			hipLaunchKernelGGL((k_digest_bins<false, 16u>), dim3(std::max(1u, std::min<uint32_t>(cap, ncu * GYS_MB_WAVES16))), dim3(256), 0, c->stream, bp);
+		} else { // 4097 .. 16 384 values: the streamed instance
+			const uint32_t cap2 = (uint32_t)std::min<uint64_t>(nsvc, b.n / (GYS_MERGE_CLASS1 - c->pend_cap) + 1);
+			hipLaunchKernelGGL((k_digest_bins<false, 64u>), dim3(std::max(1u, std::min<uint32_t>(cap2, ncu * 8))), dim3(256), 0, c->stream, bp);
+		}
+		if (cls == top) resp_launch_slow_pass(c, bp.d, cap, top);
+	}
+}
+
+// huge keys (> 16 384 values in this call): several workgroups per key (gys_huge.hpp); what that path cannot take -- entries beyond its
+// pool, more than 4 096 values >= 16 384 in one key -- is handed to the one-workgroup kernel through a fallback list
+void resp_launch_huge(gys_ctx *c, const RespBatch &b)
+{
+	ProfScope ps(c, "digest_huge");
+	Huge2P q{};
+	q.d = digest_params(c);
+	q.list = c->huge_list;
+	q.count = c->merge_count + FIN_HUGE;
+	q.bins = c->huge_scratch;
+	q.acc = c->huge_acc;
+	q.bm = c->huge_bm;
+	q.chunk_off = c->huge_chunk_off;
+	q.tail = c->huge_tail;
+	q.tail_count = c->merge_count + FIN_HUGE_TAIL;
+	q.tail_cap = 1u << 20;
+	q.maxent = c->huge_maxent;
+	q.fb_list = c->huge_fb_list;
+	q.fb_count = c->merge_count + FIN_HUGE_FB;
+	q.nent_used = c->merge_count + FIN_HUGE_NENT;
+	q.tb_list = c->huge_tb_list;
+	q.tb_count = c->merge_count + FIN_HUGE_TB;
+#ifdef GYS_HUGE_TIMING
+	q.dbg = (unsigned long long *)c->counters + 20;
+#endif
+	// the pool holds huge_maxent entries: the list is walked in rounds (a round beyond the list's end costs four empty launches)
+	const uint64_t list_cap = std::min<uint64_t>(std::min<uint64_t>(c->nsvc, b.n / (GYS_MERGE_CLASS1 - c->pend_cap) + 1), c->huge_list_cap);
+	for (uint64_t first = 0; first < list_cap; first += c->huge_maxent) {
+		q.first = (uint32_t)first;
+		hipLaunchKernelGGL(k_huge_plan, dim3(1), dim3(1024), 0, c->stream, q);
+		hipLaunchKernelGGL(k_huge_clear, dim3((uint32_t)c->ncu * 8), dim3(256), 0, c->stream, q);
+		hipLaunchKernelGGL(k_huge_count, dim3((uint32_t)c->ncu * 2), dim3(1024), GYS_HB_BINS * 4, c->stream, q);
+		// tier A: two 512-thread workgroups per CU (79 KiB of LDS each); tier B: whatever tier A handed over (usually nothing)
+		hipLaunchKernelGGL((k_huge_merge<512, GYS_HB_TAIL_A, false>), dim3((uint32_t)c->ncu * 2), dim3(512), (GYS_HB_BINS + GYS_HB_TAIL_A) * 4, c->stream, q);
+		hipLaunchKernelGGL((k_huge_merge<1024, GYS_HB_TAIL_LDS, true>), dim3((uint32_t)c->ncu), dim3(1024), (GYS_HB_BINS + GYS_HB_TAIL_LDS) * 4, c->stream, q);
+	}
+	HugeP h{};
+	h.d = q.d;
+	h.scratch = c->huge_scratch;
+	h.huge_list = c->huge_fb_list;
+	h.huge_count = c->merge_count + FIN_HUGE_FB;
+	hipLaunchKernelGGL(k_digest_huge, dim3(c->huge_blocks), dim3(256), 0, c->stream, h);
+}
+
+int run_resp_batch(gys_ctx *c, const gys_resp_seg *segs_host, uint32_t nsegs, const void *d_ev, uint64_t n, bool v6 = false)
+{
+	if (n == 0) return GYS_OK;
+	RespBatch b{segs_host, nsegs, d_ev, n, v6, c->cfg.enable_tdigest != 0};
+	int rc = resp_check_segments(c, b);
+	if (rc) return rc;
+	if ((rc = resp_upload_segments(c, b)) != GYS_OK) return rc;
+	resp_plan_front(c, b);
+	if ((rc = resp_fill_params(c, b)) != GYS_OK) return rc;
+	if (b.front.host_local) {
+		if ((rc = resp_launch_host_local(c, b)) != GYS_OK) return rc;
+	} else {
+		resp_launch_pass1(c, b);
+		HIPCHK(hipGetLastError());
+		if (!b.td || c->nsvc == 0) {
+			HIPCHK(hipEventRecord(b.slot->done, c->stream));
+			return GYS_OK;
+		}
+		resp_launch_general(c, b);
 	}
 	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(slot.done, c->stream)); // the segment descriptors have been consumed once the stream gets here
-	{
-		MergeP mp{};
-		mp.d = digest_params(c);
-		const uint32_t cap = (uint32_t)std::min<uint64_t>(nsvc, n);
-		static const bool old_merge = getenv("GYS_OLD_MERGE") != nullptr; // A/B: the general kernel for class 0 as well
-		// Round 6: class 1 (more values than the fast class, up to 4096) through the value-bin kernel's 4096-value instance as well (the same
-		// exact-integer definition: bit-identical), the general kernel only for what either instance hands over (GYS_CLASS1_GENERAL: round 5's routing, A/B)
-		static const bool class1_general = getenv("GYS_CLASS1_GENERAL") != nullptr;
-		const bool class1 = c->merge_fast < GYS_MERGE_CLASS1 && n > c->merge_fast - c->pend_cap;
-		const bool class1_bins = class1 && !class1_general && !(old_merge && c->merge_fast <= GYS_MERGE_CLASS0);
-		// size class 2 (4097 .. 16 384 values) through the streamed value-bin instance (finalize_one queues such keys on list 2 unless GYS_CLASS2_HUGE / GYS_OLD_HUGE is set)
-		static const bool class2_huge = getenv("GYS_CLASS2_HUGE") != nullptr || getenv("GYS_OLD_HUGE") != nullptr;
-		const bool class2 = !class2_huge && n > GYS_MERGE_CLASS1 - c->pend_cap;
-		MergeBP bp{};
-		bp.d = mp.d;
-		bp.slow_list = c->merge_list_slow;
-		bp.slow_count = c->merge_count + FIN_SLOW;
-		auto slow_pass = [&](bool up_to_class1) { // entries whose total weight needs 64-bit arithmetic, or with more large values than the bin kernel's list holds (normally none)
-			mp.list = c->merge_list_slow;
-			mp.count = c->merge_count + FIN_SLOW;
-			if (class2) hipLaunchKernelGGL((k_digest_merge<GYS_MERGE_LDS_MAX, 1024u>), dim3(std::max(1u, std::min<uint32_t>(cap, (uint32_t)c->ncu))), dim3(1024), 0, c->stream, mp); // (ONE pass over the list, behind the last value-bin launch: an entry is merged once)
-			else if (!up_to_class1) hipLaunchKernelGGL((k_digest_merge<GYS_MERGE_CLASS0, 256u>), dim3(std::max(1u, std::min<uint32_t>(cap, (uint32_t)c->ncu))), dim3(256), 0, c->stream, mp);
-			else hipLaunchKernelGGL((k_digest_merge<GYS_MERGE_CLASS1, 256u>), dim3(std::max(1u, std::min<uint32_t>(cap, (uint32_t)c->ncu))), dim3(256), 0, c->stream, mp);
-		};
-		{
-			ProfScope ps(c, "digest_merge");
-			mp.list = c->merge_list;
-			mp.count = c->merge_count + FIN_CLASS0;
-			if (old_merge && c->merge_fast <= GYS_MERGE_CLASS0) {
-				hipLaunchKernelGGL((k_digest_merge<GYS_MERGE_CLASS0, 256u>), dim3(std::max(1u, std::min<uint32_t>(cap, (uint32_t)c->ncu * 7))), dim3(256), 0, c->stream, mp);
-			} else {
-				bp.list = c->merge_list;
-				bp.count = c->merge_count + FIN_CLASS0;
-				const dim3 bgrid(std::max(1u, std::min<uint32_t>(cap, (uint32_t)c->ncu * 8)));
-				if (c->merge_fast <= 1024u) hipLaunchKernelGGL((k_digest_bins<false, 4u>), bgrid, dim3(256), 0, c->stream, bp);
-				else if (c->merge_fast <= 2048u) hipLaunchKernelGGL((k_digest_bins<false, 8u>), bgrid, dim3(256), 0, c->stream, bp);
-				else hipLaunchKernelGGL((k_digest_bins<false, 16u>), bgrid, dim3(256), 0, c->stream, bp);
-				if (!class1_bins && !class2) slow_pass(c->merge_fast > GYS_MERGE_CLASS0); // (else: one pass over the list behind the last value-bin launch -- an entry is merged once)
-			}
-		}
-		if (class1) {
-			ProfScope ps(c, "digest_merge_big");
-			if (class1_bins) {
-				bp.list = c->merge_list1;
-				bp.count = c->merge_count + FIN_CLASS1;
-				hipLaunchKernelGGL((k_digest_bins<false, 16u>), dim3(std::max(1u, std::min<uint32_t>(cap, (uint32_t)c->ncu * GYS_MB_WAVES16))), dim3(256), 0, c->stream, bp);
-				if (!class2) slow_pass(true);
-			} else {
-				mp.list = c->merge_list1;
-				mp.count = c->merge_count + FIN_CLASS1;
-				hipLaunchKernelGGL((k_digest_merge<GYS_MERGE_CLASS1, 256u>), dim3(std::max(1u, std::min<uint32_t>(cap, (uint32_t)c->ncu * 3))), dim3(256), 0, c->stream, mp);
-			}
-			// (entries above class 2 take the several-workgroup path below)
-		}
-		if (class2) {
-			ProfScope ps(c, "digest_merge_big");
-			bp.list = c->merge_list2;
-			bp.count = c->merge_count + FIN_CLASS2;
-			const uint32_t cap2 = (uint32_t)std::min<uint64_t>(nsvc, n / (GYS_MERGE_CLASS1 - c->pend_cap) + 1);
-			hipLaunchKernelGGL((k_digest_bins<false, 64u>), dim3(std::max(1u, std::min<uint32_t>(cap2, (uint32_t)c->ncu * 8))), dim3(256), 0, c->stream, bp);
-			slow_pass(true); // (what a value-bin launch handed over -- 64-bit weights, more than 1024 values of a second or longer -- through the general kernel's 16 384-value instance)
-		}
-	}
-	if (n > GYS_MERGE_CLASS1 - c->pend_cap) {
-		// huge keys (> 16 384 values in this call): several workgroups per key (gys_huge.hpp); what that path cannot take -- entries
-		// beyond its pool, more than 4 096 values >= 16 384 in one key -- is handed to the one-workgroup kernel through a fallback list
-		ProfScope ps(c, "digest_huge");
-		static const bool old_huge = getenv("GYS_OLD_HUGE") != nullptr; // A/B
-		HugeP h{};
-		h.d = digest_params(c);
-		h.scratch = c->huge_scratch;
-		if (old_huge) {
-			h.huge_list = c->huge_list;
-			h.huge_count = c->merge_count + FIN_HUGE;
-		} else {
-			Huge2P q{};
-			q.d = h.d;
-			q.list = c->huge_list;
-			q.count = c->merge_count + FIN_HUGE;
-			q.bins = c->huge_scratch;
-			q.acc = c->huge_acc;
-			q.bm = c->huge_bm;
-			q.chunk_off = c->huge_chunk_off;
-			q.tail = c->huge_tail;
-			q.tail_count = c->merge_count + 9;
-			q.tail_cap = 1u << 20;
-			q.maxent = c->huge_maxent;
-			q.fb_list = c->huge_fb_list;
-			q.fb_count = c->merge_count + 6;
-			q.nent_used = c->merge_count + 7;
-			q.tb_list = c->huge_tb_list;
-			q.tb_count = c->merge_count + 10;
-#ifdef GYS_HUGE_TIMING
-			q.dbg = (unsigned long long *)c->counters + 20;
-#endif
-			// the pool holds huge_maxent entries: the list is walked in rounds (a round beyond the list's end costs four empty launches)
-			const uint64_t list_cap = std::min<uint64_t>(std::min<uint64_t>(nsvc, n / (GYS_MERGE_CLASS1 - c->pend_cap) + 1), c->huge_list_cap);
-			for (uint64_t first = 0; first < list_cap; first += c->huge_maxent) {
-				q.first = (uint32_t)first;
-				hipLaunchKernelGGL(k_huge_plan, dim3(1), dim3(1024), 0, c->stream, q);
-				hipLaunchKernelGGL(k_huge_clear, dim3((uint32_t)c->ncu * 8), dim3(256), 0, c->stream, q);
-				hipLaunchKernelGGL(k_huge_count, dim3((uint32_t)c->ncu * 2), dim3(1024), GYS_HB_BINS * 4, c->stream, q);
-				// tier A: two 512-thread workgroups per CU (79 KiB of LDS each); tier B: whatever tier A handed over (usually nothing)
-				hipLaunchKernelGGL((k_huge_merge<512, GYS_HB_TAIL_A, false>), dim3((uint32_t)c->ncu * 2), dim3(512), (GYS_HB_BINS + GYS_HB_TAIL_A) * 4, c->stream, q);
-				hipLaunchKernelGGL((k_huge_merge<1024, GYS_HB_TAIL_LDS, true>), dim3((uint32_t)c->ncu), dim3(1024), (GYS_HB_BINS + GYS_HB_TAIL_LDS) * 4, c->stream, q);
-			}
-			h.huge_list = c->huge_fb_list;
-			h.huge_count = c->merge_count + 6;
-		}
-		hipLaunchKernelGGL(k_digest_huge, dim3(c->huge_blocks), dim3(256), 0, c->stream, h);
-	}
+	resp_launch_finalize(c, b);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(b.slot->done, c->stream)); // the segment descriptors have been consumed once the stream gets here
+	resp_launch_merges(c, b);
+	if (n > GYS_MERGE_CLASS1 - c->pend_cap) resp_launch_huge(c, b);
 	HIPCHK(hipGetLastError());
 	return GYS_OK;
 }
@@ -1934,11 +1931,9 @@ int ingest_staged_records(gys_ctx *c, uint32_t host, const void *batch, uint64_t
 		std::lock_guard<std::mutex> g(c->enq_mu);
 		// (copy on the copy stream, kernels on the engine stream behind an event -- as for the response submissions: the copy of one
 		// message runs under the kernels of the message before it)
-		hipError_t e = hipMemcpyAsync(st.d, st.h, total, hipMemcpyHostToDevice, c->copy_stream ? c->copy_stream : c->stream);
-		if (e == hipSuccess && c->copy_stream) {
-			e = hipEventRecord(st.copied, c->copy_stream);
-			if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, st.copied, 0);
-		}
+		hipError_t e = hipMemcpyAsync(st.d, st.h, total, hipMemcpyHostToDevice, c->copy_stream);
+		if (e == hipSuccess) e = hipEventRecord(st.copied, c->copy_stream);
+		if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, st.copied, 0);
 		if (e == hipSuccess) {
 			rc = conn ? run_conn(c, st.d, (const uint32_t *)(st.d + off_at), (uint32_t)offs.size())
 				  : run_lstate(c, st.d, (const uint32_t *)(st.d + off_at), nullptr, host, (uint32_t)offs.size());
@@ -1985,15 +1980,13 @@ int subq_submit_one(gys_ctx *c, SubQ &q, SubQ::Batch &b)
 	std::lock_guard<std::mutex> g(c->enq_mu);
 	// copy on its own stream, kernels on the engine stream behind an event: with everything on one stream the 48-MiB copy of a response
 	// submission (0.85 ms at 57 GB/s) and its kernels alternate; the batch's buffers are not reused before `done` has fired
-	hipStream_t cs = c->copy_stream ? c->copy_stream : c->stream;
+	hipStream_t cs = c->copy_stream;
 	const uint64_t off_at = q.cap, host_at = q.cap + (uint64_t)q.cap_recs * 4;
 	hipError_t e = hipMemcpyAsync(b.d, b.h, resp ? b.fill * 24 : b.fill, hipMemcpyHostToDevice, cs);
 	if (e == hipSuccess && !resp) e = hipMemcpyAsync(b.d + off_at, b.h + off_at, (uint64_t)b.nrec * 4, hipMemcpyHostToDevice, cs);
 	if (e == hipSuccess && q.kind == SubQ::LSTATE) e = hipMemcpyAsync(b.d + host_at, b.h + host_at, (uint64_t)b.nrec * 4, hipMemcpyHostToDevice, cs);
-	if (e == hipSuccess && c->copy_stream) {
-		e = hipEventRecord(b.copied, c->copy_stream);
-		if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, b.copied, 0);
-	}
+	if (e == hipSuccess) e = hipEventRecord(b.copied, cs);
+	if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, b.copied, 0);
 	if (e == hipSuccess) {
 		if (resp) rc = run_resp_batch(c, b.segs.data(), (uint32_t)b.segs.size(), b.d, b.fill);
 		else if (q.kind == SubQ::CONN) rc = run_conn(c, b.d, (const uint32_t *)(b.d + off_at), b.nrec);
@@ -2351,7 +2344,7 @@ try {
 		HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
 		c->own_stream = true;
 	}
-	if (!getenv("GYS_RQ_ONE_STREAM")) HIPCHK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking)); // H2D copies of the host-pointer response submissions (the variable: A/B)
+	HIPCHK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking)); // H2D copies of the host-pointer submissions
 	const uint64_t S = cfg->max_services, H = cfg->max_hosts;
 	const uint32_t cap = next_pow2(S * 2);
 	int rc;
@@ -2401,10 +2394,9 @@ try {
 	HIPCHK((resp_host_lds_attr<8, true, false>(&c->resp_dyn_max)));
 	HIPCHK((resp_host_lds_attr<8, true, true>(&c->resp_dyn_max)));
 	HIPCHK((resp_host_lds_attr<16, false, false>(&c->resp_dyn_max)));
-	HIPCHK((resp_host_lds_attr<32, false, false>(&c->resp_dyn_max)));
 	HIPCHK((resp_host_lds_attr<16, true, false>(&c->resp_dyn_max)));
 	HIPCHK((resp_host_lds_attr<16, true, true>(&c->resp_dyn_max)));
-	HIPCHK((resp_host_lds_attr<12, false, false>(&c->resp_dyn_max))); // (GYS_TPT=12: half of the room per workgroup, two per CU)
+	HIPCHK((resp_host_lds_attr<12, false, false>(&c->resp_dyn_max))); // (half of the room per workgroup, two per CU)
 	HIPCHK((resp_host_lds_attr<12, true, false>(&c->resp_dyn_max)));
 	HIPCHK((resp_host_lds_attr<12, true, true>(&c->resp_dyn_max)));
 	HIPCHK((resp_host_lds_attr<16, false, false, 1>(&c->resp_dyn_max))); // keys with candidates (bound-address listeners)
@@ -2470,7 +2462,7 @@ try {
 		c->huge_list_cap = std::min<uint64_t>(S, B / (GYS_MERGE_CLASS1 - c->pend_cap) + 1);
 		ALLOC(c->huge_list, c->huge_list_cap + 1);
 		ALLOC(c->query_list, 4);
-		ALLOC(c->merge_count, 16);
+		ALLOC(c->merge_count, FIN_NWORDS);
 		ALLOC(c->query_sum, GYS_TD_NB);
 		ALLOC(c->query_cnt, GYS_TD_NB);
 		ALLOC(c->batch_cnt, align_up(S, 16));
@@ -2480,7 +2472,7 @@ try {
 		c->ev_kv_cap = B;
 		// `staged`: the runs of one batch.  With predicted runs (k_prespill) a batch may need the predicted runs (the last batch's counts
 		// plus a quarter, + 64 per key) AND the exact runs of the keys the prediction missed (<= B): 5/2 B + slack, while indices stay 32-bit
-		c->prespill = getenv("GYS_NO_PRESPILL") == nullptr && B * 5 / 2 + (1u << 24) < (1ull << 32);
+		c->prespill = B * 5 / 2 + (1u << 24) < (1ull << 32);
 		c->staged_cap = c->prespill ? B * 5 / 2 + (1u << 24) : B;
 		if ((rc = dev_alloc(&c->staged, c->staged_cap, false)) != GYS_OK) { // (runs are written before they are read)
 			gys_destroy(c);
@@ -2529,7 +2521,7 @@ try {
 	if (cfg->enable_tdigest) {
 		hipLaunchKernelGGL(k_minmax_init, dim3(grid_for(S, 256, 2048)), dim3(256), 0, c->stream, c->td_minmax, S);
 		static const uint32_t one = 1; // static: the source of an async copy must outlive the call
-		HIPCHK(hipMemcpyAsync(c->merge_count + 8, &one, 4, hipMemcpyHostToDevice, c->stream));
+		HIPCHK(hipMemcpyAsync(c->merge_count + FIN_QUERY_ONE, &one, 4, hipMemcpyHostToDevice, c->stream));
 	}
 	hipLaunchKernelGGL(k_hist_init, dim3(grid_for(S, 256, 2048)), dim3(256), 0, c->stream, c->hist_win, (uint64_t)0, S, (int64_t)INT64_MIN);
 	hipLaunchKernelGGL(k_hist_init, dim3(grid_for(S, 256, 2048)), dim3(256), 0, c->stream, c->hist_all, (uint64_t)0, S, (int64_t)INT64_MIN);
@@ -2586,10 +2578,6 @@ void gys_destroy(gys_ctx *c)
 		if (cg.g) hipGraphDestroy(cg.g);
 	}
 	for (auto &sl : c->seg_ring) {
-		if (sl.host) hipHostFree(sl.host);
-		if (sl.dev) hipFree(sl.dev);
-		if (sl.xhost) hipHostFree(sl.xhost);
-		if (sl.xdev) hipFree(sl.xdev);
 		if (sl.done) hipEventDestroy(sl.done);
 	}
 	for (auto &q : c->sq)
@@ -3131,8 +3119,7 @@ try {
 	int rc = lookup_host(c, machine_id, &host);
 	if (rc) return rc;
 	if (!nevents) return GYS_OK;
-	static const bool no_queue = getenv("GYS_NO_RESP_QUEUE") != nullptr; // A/B: one submission per call through the staging ring
-	if (!no_queue && (uint64_t)nevents <= std::min<uint64_t>(GYS_RQ_EVENTS, c->cfg.max_batch_events))
+	if ((uint64_t)nevents <= std::min<uint64_t>(GYS_RQ_EVENTS, c->cfg.max_batch_events))
 		return subq_ingest(c, c->sq[SubQ::RESP], host, ev24, 0, nevents, nullptr); // combined with the other callers' pending calls
 	return ingest_staged_resp(c, host, ev24, nevents, 24, false, "gys_ingest_resp_events"); // larger than a combined batch
 } GYS_CATCH_ALL
@@ -3806,7 +3793,7 @@ static int td_merged_view(gys_ctx *c, uint32_t slot, int64_t *sum, uint32_t *cnt
 	MergeP mp{};
 	mp.d = digest_params(c);
 	mp.list = c->query_list;
-	mp.count = c->merge_count + 8;
+	mp.count = c->merge_count + FIN_QUERY_ONE;
 	mp.out_sum = c->query_sum;
 	mp.out_cnt = c->query_cnt;
 	if (mt.npend <= GYS_MERGE_CLASS0) hipLaunchKernelGGL((k_digest_merge<GYS_MERGE_CLASS0, 256u>), dim3(1), dim3(256), 0, c->stream, mp);

@@ -456,8 +456,22 @@ __global__ void k_minmax_init(int2 *mm, uint64_t n)
 #define GYS_MERGE_CLASS0 1024u // largest (buffered + run) value count of merge size class 0 / 1 (class 2: up to GYS_MERGE_LDS_MAX)
 #define GYS_MERGE_CLASS1 4096u
 static_assert(GYS_TDIGEST_MERGE_FAST == GYS_MERGE_CLASS0, "the early re-clustering rule keeps a key's merges inside merge size class 0 (default buffer size)");
-enum { FIN_CLASS0 = 0, FIN_CLASS1, FIN_CLASS2, FIN_HUGE, FIN_RUN_ALLOC, FIN_SLOW, FIN_NCOUNTS }; // FIN_SLOW: k_digest_bins' hand-over list
-#define FIN_APPEND 12 // counts[FIN_APPEND]: length of the append list (keys whose predicted run turned out to fit their buffer; 6..10: the large-key path)
+// the words of the engine's merge_count array (FinP::counts)
+enum {
+	FIN_CLASS0 = 0, FIN_CLASS1, FIN_CLASS2, // lengths of the merge lists by size class
+	FIN_HUGE,          // length of the huge list
+	FIN_RUN_ALLOC,     // bump cursor into `staged`
+	FIN_SLOW,          // length of k_digest_bins' hand-over list
+	FIN_HUGE_FB,       // large-key path: length of the fallback list (k_digest_huge)
+	FIN_HUGE_NENT,     // large-key path: pool entries in use
+	FIN_BATCH_CLEARED, // words [0, FIN_BATCH_CLEARED) are cleared at the start of every batch
+	FIN_QUERY_ONE = FIN_BATCH_CLEARED, // the constant 1: length of the one-entry query list
+	FIN_HUGE_TAIL,     // large-key path: fill of the tail pool
+	FIN_HUGE_TB,       // large-key path: length of tier B's list
+	FIN_APPEND = 12,   // length of the append list (keys whose predicted run turned out to fit their buffer)
+	FIN_PRE_RESV = 14, // [14 .. 15]: the predicted runs' 64-bit reservation counter
+	FIN_NWORDS = 16
+};
 
 struct FinP {
 	uint32_t *td_cur;
@@ -466,7 +480,7 @@ struct FinP {
 	uint32_t pend_cap, merge_fast; // the t-digest rule's two numbers (gys_config.td_pend_cap; merge_fast = pend_cap + 128 = the largest merge of size class 0)
 	uint32_t *resp_win;        // per service: response events of the open window
 	MergeEnt *list[4];         // merge lists by size class, [FIN_HUGE] = the huge list
-	uint32_t *counts;          // [FIN_NCOUNTS]: list lengths, bump cursor into `staged`
+	uint32_t *counts;          // [FIN_NWORDS]: list lengths, bump cursor into `staged`
 	uint32_t *td_run;
 	const uint32_t *batch_off; // general front end: end of the key's run in `staged` (nullptr: host-local front end)
 	const uint32_t *svc_host;
@@ -865,11 +879,7 @@ struct HostDesc {
 // workgroup size of k_resp_host by tile form: 16 / 8 events per thread with 1024 threads (one workgroup per CU), or 12 events per thread
 // with 512 threads (6144-event tiles, 76 KB of LDS at 1000 listeners: TWO workgroups per CU, so that one's prologue / scan / flush phases
 // run under the other's event phase)
-#define GYS_RESP_THREADS(TPT) (((TPT) == 12 || (TPT) == 32) ? 512 : 1024)
-// TPT = 32 (round 4, experiment behind GYS_TPT=32): 512 threads x 32 events = the same 16 384-event tile as 1024 x 16, ONE workgroup per CU
-// at two waves per SIMD, i.e. a budget of 256 VGPRs -- room to hold the NEXT group's twelve event words in registers while the current
-// group is processed (at 128 VGPRs that prefetch spilled and lost, r3j / r3l / r3n), across the tile boundary too
-#define GYS_RESP_WAVES_PER_SIMD(TPT) ((TPT) == 32 ? 2 : 4)
+#define GYS_RESP_THREADS(TPT) ((TPT) == 12 ? 512 : 1024)
 #define GYS_SPLIT_PART 65536u // events per part when long segments are cut (SHARED)
 
 // EXPERIMENT builds only (-DGYS_RESP_TIMING): shader-clock ticks per phase of k_resp_host, summed over the waves of a launch (every wave adds
@@ -934,7 +944,7 @@ __host__ __device__ __forceinline__ size_t resp_host_lds_bytes(uint32_t tbl_entr
 // measured configurations: nothing below costs it an instruction); 1: IPv4 events, keys with candidates (bound-address listeners) are
 // resolved by the event's server address; 2: IPv6 events (48 bytes; flow hash through the general word packing, candidates as in 1)
 template <int TPT, bool SHARED, bool SPILL, bool SVCHLL, int MODE = 0>
-__global__ __launch_bounds__(GYS_RESP_THREADS(TPT), GYS_RESP_WAVES_PER_SIMD(TPT)) void k_resp_host(RespHostP p_arg) // (4 waves per SIMD: one 1024-thread workgroup or two 512-thread ones per CU; TPT = 32: 2)
+__global__ __launch_bounds__(GYS_RESP_THREADS(TPT), 4) void k_resp_host(RespHostP p_arg) // (4 waves per SIMD: one 1024-thread workgroup or two 512-thread ones per CU)
 {
 	// the parameters are read from the kernel-argument segment where they are used (scalar loads), re-read per tile, instead of being held in
 	// SGPRs -- and spilled into VGPR lanes -- across the whole kernel; a host build (tests/cpp/kemu) takes the plain parameter
@@ -952,7 +962,6 @@ __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), GYS_RESP_WAVES_PER_SIMD(TPT)
 	constexpr bool DBG = GYS_RESP_DBG != 0;
 	constexpr bool V6 = MODE == 2;
 	constexpr uint32_t SW = V6 ? GYS_EV6_WORDS : 3u; // 8-byte words per event
-	static_assert(MODE == 0 || TPT != 32, "the register-prefetch form exists for the plain IPv4 instance only");
 	GYS_DYN_LDS(uint64_t, s_dyn);
 	__shared__ uint32_t s_wsum[T / 64];
 	__shared__ uint32_t s_drop[2];
@@ -1050,9 +1059,6 @@ __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), GYS_RESP_WAVES_PER_SIMD(TPT)
 #endif
 	const uint32_t tid24 = 24u * tid;
 	int32_t tmax = INT32_MIN, wmax = -1;
-	// PF: the twelve words of the NEXT group of four events per thread are requested while the current group is processed and wait in
-	// n0 / n1 / n2 (the group after a tile's last one is the next tile's first: its loads run under the scan / image / flush phases)
-	constexpr bool PF = TPT == 32 && !SPILL;
 	// events through LDS (GYS_EV_DMA): the tile image of 6 bytes per event is 6 KB per wave with 16 events per thread -- room for the 4 x 1536 bytes of a
 	// group's four event slots.  Layout of a wave's area: the first KB of slot u at 1024 u, its last 512 bytes at 4096 + 512 u (the tails of two slots
 	// are one full-width request).  The 8-byte piece k of lane l's event (byte 24 l + 8 k of the slot) never straddles the KB boundary.
@@ -1064,21 +1070,6 @@ __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), GYS_RESP_WAVES_PER_SIMD(TPT)
 		const uint32_t byte = 24u * lane + 8u * k;
 		dma_a[k] = byte < 1024u ? byte : 4096u + (byte - 1024u);
 		dma_s[k] = byte < 1024u ? 1024u : 512u;
-	}
-	uint64_t n0[4], n1[4], n2[4];
-	auto pf_issue = [&](const uint64_t *base, uint32_t first_o, uint32_t lim) {
-#pragma unroll
-		for (int u = 0; u < 4; ++u) {
-			const uint32_t o = first_o + (uint32_t)u * T + tid;
-			const uint32_t oo = o < lim ? o : 0u; // (lanes past the end read the tile's first event and ignore it)
-			n0[u] = base[3u * oo];
-			n1[u] = base[3u * oo + 1u];
-			n2[u] = base[3u * oo + 2u];
-		}
-	};
-	if (PF) {
-		const uint64_t left0 = e1 - e0;
-		pf_issue(p.ev + 3u * e0, 0u, left0 < (uint64_t)TILE ? (uint32_t)left0 : TILE);
 	}
 	GYS_TICK(10); // prologue: tables, floor
 	for (uint64_t t0 = e0; t0 < e1; t0 += TILE, ++tile_no) {
@@ -1118,47 +1109,29 @@ __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), GYS_RESP_WAVES_PER_SIMD(TPT)
 			if ((uint32_t)g * T >= rem) break; // the segment's last tile is usually short (C3: 53 687 events = 3.28 tiles): no empty groups
 			uint64_t w0[4], w1[4], w2[4];
 			bool in[4];
-			if (PF) {
 #pragma unroll
-				for (int u = 0; u < 4; ++u) {
-					in[u] = (uint32_t)(g + u) * T + tid < rem;
-					w0[u] = n0[u];
-					w1[u] = n1[u];
-					w2[u] = n2[u];
-				}
-				// the group that runs next: this tile's, or the first one of the next tile
-				const uint32_t g2 = (uint32_t)g + 4u;
-				if (g2 < (uint32_t)TPT && g2 * T < rem) {
-					pf_issue(tb, g2 * T, rem);
-				} else if (t0 + TILE < e1) {
-					const uint64_t left2 = e1 - t0 - TILE;
-					pf_issue(tb + 3u * TILE, 0u, left2 < (uint64_t)TILE ? (uint32_t)left2 : TILE);
-				}
-			} else {
-#pragma unroll
-				for (int u = 0; u < 4; ++u) {
-					const uint32_t o = (uint32_t)(g + u) * T + tid;
-					in[u] = o < rem;
-					const uint32_t oo = in[u] ? o : 0u; // (lanes past the end read the tile's first event and ignore it: no branch around the loads)
-					if (V6) { // the name space / ports word and the times word; the addresses are read where they are needed (candidates, flow hash)
-						w0[u] = 0;
-						w1[u] = tb[GYS_EV6_WORDS * oo + 4u];
-						w2[u] = tb[GYS_EV6_WORDS * oo + 5u];
-					} else if (DMA) {
-						in[u] = (uint32_t)(g + u) * T + tid < rem; // (the words are read from the wave's LDS area below, behind the requests of all four slots)
-						w0[u] = w1[u] = w2[u] = 0;
-					} else {
-						// the tile's base is uniform and an event's byte offset inside the tile fits 32 bits: written so, the three loads share ONE
-						// 32-bit offset register (scalar base + offset + immediate) instead of a 64-bit address each.  Round 6: the offset is
-						// 24 tid (kept) + 24 T (g + u) (scalar) -- no 32-bit multiply (a quarter-rate instruction) per event
-						const uint32_t ob_raw = tid24 + (uint32_t)(g + u) * (24u * T);
-						in[u] = ob_raw < 24u * rem; // (== o < rem)
-						const uint32_t ob = in[u] ? ob_raw : 0u;
-						const char *const tbb = (const char *)tb;
-						w0[u] = *(const uint64_t *)(tbb + ob);
-						w1[u] = *(const uint64_t *)(tbb + ob + 8u);
-						w2[u] = *(const uint64_t *)(tbb + ob + 16u);
-					}
+			for (int u = 0; u < 4; ++u) {
+				const uint32_t o = (uint32_t)(g + u) * T + tid;
+				in[u] = o < rem;
+				const uint32_t oo = in[u] ? o : 0u; // (lanes past the end read the tile's first event and ignore it: no branch around the loads)
+				if (V6) { // the name space / ports word and the times word; the addresses are read where they are needed (candidates, flow hash)
+					w0[u] = 0;
+					w1[u] = tb[GYS_EV6_WORDS * oo + 4u];
+					w2[u] = tb[GYS_EV6_WORDS * oo + 5u];
+				} else if (DMA) {
+					in[u] = (uint32_t)(g + u) * T + tid < rem; // (the words are read from the wave's LDS area below, behind the requests of all four slots)
+					w0[u] = w1[u] = w2[u] = 0;
+				} else {
+					// the tile's base is uniform and an event's byte offset inside the tile fits 32 bits: written so, the three loads share ONE
+					// 32-bit offset register (scalar base + offset + immediate) instead of a 64-bit address each.  Round 6: the offset is
+					// 24 tid (kept) + 24 T (g + u) (scalar) -- no 32-bit multiply (a quarter-rate instruction) per event
+					const uint32_t ob_raw = tid24 + (uint32_t)(g + u) * (24u * T);
+					in[u] = ob_raw < 24u * rem; // (== o < rem)
+					const uint32_t ob = in[u] ? ob_raw : 0u;
+					const char *const tbb = (const char *)tb;
+					w0[u] = *(const uint64_t *)(tbb + ob);
+					w1[u] = *(const uint64_t *)(tbb + ob + 8u);
+					w2[u] = *(const uint64_t *)(tbb + ob + 16u);
 				}
 			}
 			if (DMA) {

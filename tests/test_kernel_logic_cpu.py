@@ -57,7 +57,6 @@ PROGRAMS = {
     "bins-16384-values-streamed-7": ("test_bins.cc", ["KEMU_BINS_VPT=64"] + BINS, ["7"], "kemu bins ok"),
     "resp-tiles-16384": ("test_resp.cc", ["KEMU_TPT=16"] + BINS, ["4242"], "kemu resp ok"),
     "resp-tiles-6144": ("test_resp.cc", ["KEMU_TPT=12"] + BINS, ["4242"], "kemu resp ok"),
-    "resp-512x32-prefetch": ("test_resp.cc", ["KEMU_TPT=32"] + BINS, ["4242"], "kemu resp ok"),
     "resp-split-form": ("test_resp.cc", ["KEMU_TPT=16", "KEMU_SPLIT", "KEMU_NB=3"] + BINS, ["4242"], "kemu resp ok"),
     # the whole pipeline with td_pend_cap 1536 / 3072 (fast merge classes of 2048 / 4096 values) against the oracle engine with the same buffer size
     "resp-pend-cap-1536": ("test_resp.cc", ["KEMU_TPT=16", "KEMU_PEND_CAP=1536", "KEMU_NB=12"] + BINS, ["4246"], "kemu resp ok"),

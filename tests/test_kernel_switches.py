@@ -22,6 +22,25 @@ RETIRED = ["GYS_BUCKET_LUT", "GYS_BK_BYTES", "GYS_SHIFT_SWITCH", "GYS_PROBE_XOR"
            "GYS_MB_PACKED", "GYS_MB_KERNARG", "GYS_MB_FUSE_OLD", "GYS_MB_COMPACT", "GYS_CONN_PREFETCH", "GYS_CONN_FLOOR", "GYS_HB_PIPE",
            "GYS_HB_STAGED", "GYS_HB_LUT", "GYS_KERNARG"]
 
+# run-time switches (getenv) that selected a variant the project's own tables rejected, or an A/B leg (EXPERIMENTS.md, "Retired run-time
+# switches"); the old round scripts under tools/ name them: those are records and are not scanned for these names
+RETIRED_RUNTIME = ["GYS_OLD_MERGE", "GYS_CLASS1_GENERAL", "GYS_CLASS2_HUGE", "GYS_OLD_HUGE", "GYS_TPT", "GYS_TBL_SPARSE", "GYS_RQ_ONE_STREAM",
+                   "GYS_NO_RESP_QUEUE", "GYS_NO_PRESPILL"]
+
+
+def _hits(names, files):
+    pat = re.compile(r"\b(" + "|".join(names) + r")\b")
+    hits = []
+    for path in files:
+        if not os.path.isfile(path) or os.path.abspath(path) == os.path.abspath(__file__):
+            continue
+        if path.endswith((".so", ".pyc", ".o")) or os.sep + "golden" + os.sep in path:
+            continue
+        for no, line in enumerate(open(path, errors="replace"), 1):
+            if pat.search(line):
+                hits.append("%s:%d" % (os.path.relpath(path, ROOT), no))
+    return hits
+
 
 def test_conditional_directives_name_listed_switches_only():
     seen = set()
@@ -35,16 +54,6 @@ def test_conditional_directives_name_listed_switches_only():
 
 def test_retired_switches_are_gone():
     files = [p for d in ("gyeeta_amd", "include", "tests") for p in glob.glob(os.path.join(ROOT, d, "**", "*"), recursive=True)]
-    files += glob.glob(os.path.join(ROOT, "tools", "*.sh"))
-    pat = re.compile(r"\b(" + "|".join(RETIRED) + r")\b")
-    hits = []
-    for path in files:
-        if not os.path.isfile(path) or os.path.abspath(path) == os.path.abspath(__file__):
-            continue
-        if path.endswith((".so", ".pyc", ".o")) or os.sep + "golden" + os.sep in path:
-            continue
-        for no, line in enumerate(open(path, errors="replace"), 1):
-            if pat.search(line):
-                hits.append("%s:%d" % (os.path.relpath(path, ROOT), no))
     assert len(files) > 50
+    hits = _hits(RETIRED, files + glob.glob(os.path.join(ROOT, "tools", "*.sh"))) + _hits(RETIRED_RUNTIME, files)
     assert not hits, hits
