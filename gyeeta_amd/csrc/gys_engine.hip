@@ -15,6 +15,7 @@
 #include <cstring>
 #include <deque>
 #include <map>
+#include <memory>
 #include <set>
 #include <string>
 #include <thread>
@@ -27,6 +28,7 @@
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 
+#include "gys_devmem.hpp"
 #include "gys_kernels.hpp"
 #include "gys_rollup.hpp"
 #include "gys_groups.hpp"
@@ -41,95 +43,6 @@
 using namespace gys;
 
 namespace {
-
-thread_local char g_err[512] = "";
-
-void set_err(const char *fmt, ...)
-{
-	va_list ap;
-	va_start(ap, fmt);
-	vsnprintf(g_err, sizeof(g_err), fmt, ap);
-	va_end(ap);
-}
-
-#define HIPCHK(expr)                                                                                       \
-	do {                                                                                               \
-		hipError_t e_ = (expr);                                                                    \
-		if (e_ != hipSuccess) {                                                                    \
-			set_err("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-			return GYS_ERR_HIP;                                                                \
-		}                                                                                          \
-	} while (0)
-
-// An owning, grow-only device buffer of `cap` elements.  grow() keeps a buffer that is large enough; otherwise it waits for the stream (a
-// kernel in flight may still read the old buffer), frees it and allocates anew: the contents are NOT kept.  The destructor frees.
-template <typename T>
-struct DevBuf {
-	T *p = nullptr;
-	size_t cap = 0;
-	DevBuf() = default;
-	DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
-	DevBuf &operator=(DevBuf &&o) noexcept
-	{
-		std::swap(p, o.p);
-		std::swap(cap, o.cap);
-		return *this;
-	}
-	~DevBuf() { release(); }
-	void release()
-	{
-		if (p) hipFree(p);
-		p = nullptr;
-		cap = 0;
-	}
-	int grow(size_t n, hipStream_t stream)
-	{
-		if (p && cap >= n) return GYS_OK;
-		if (p) HIPCHK(hipStreamSynchronize(stream));
-		release();
-		n = std::max<size_t>(n, 1);
-		HIPCHK(hipMalloc((void **)&p, n * sizeof(T)));
-		cap = n;
-		return GYS_OK;
-	}
-	int upload(const std::vector<T> &v, hipStream_t stream) // (asynchronous: v must outlive the copy)
-	{
-		const int rc = grow(v.size(), stream);
-		if (rc) return rc;
-		if (!v.empty()) HIPCHK(hipMemcpyAsync(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, stream));
-		return GYS_OK;
-	}
-};
-
-// A pinned host buffer and a device buffer of the same `cap` elements: filled on the host, copied per batch.  grow() keeps a pair that is
-// large enough; otherwise it frees both and allocates anew (at least `floor` elements): the contents are NOT kept, and the caller knows
-// that nothing in flight reads the old ones.  The destructor frees.
-template <typename T>
-struct PinnedPair {
-	T *host = nullptr, *dev = nullptr;
-	size_t cap = 0;
-	PinnedPair() = default;
-	PinnedPair(const PinnedPair &) = delete;
-	PinnedPair &operator=(const PinnedPair &) = delete;
-	~PinnedPair() { release(); }
-	void release()
-	{
-		if (host) hipHostFree(host);
-		if (dev) hipFree(dev);
-		host = dev = nullptr;
-		cap = 0;
-	}
-	int grow(size_t n, size_t floor)
-	{
-		if (n <= cap) return GYS_OK;
-		release();
-		n = std::max(n, floor);
-		HIPCHK(hipHostMalloc((void **)&host, n * sizeof(T), hipHostMallocDefault));
-		HIPCHK(hipMalloc((void **)&dev, n * sizeof(T)));
-		cap = n;
-		return GYS_OK;
-	}
-};
 
 // The member lists of one grouping (gys_groups.hpp) and their copy on the device, built at one generation of the registry
 // (gys_ctx::registry_gen); ensure_host_groups() / ensure_cluster_groups() rebuild them when the registry has moved on.
@@ -272,60 +185,58 @@ struct gys_ctx {
 	std::set<uint32_t> free_slots;
 	std::vector<uint32_t> svc_host_h;
 	std::vector<uint64_t> svc_key_h;
-	SvcClearSeg *clr_segs = nullptr;     // k_svc_clear's segment list (rebuilt per call: hist_win and lvl_last change places)
-	unsigned long long *stale_bits = nullptr; // gys_list_stale_listeners scratch (grows)
-	uint32_t *stale_tiles = nullptr;
-	uint64_t *stale_ids = nullptr;
-	uint64_t stale_tiles_cap = 0, stale_ids_cap = 0;
+	DevBuf<SvcClearSeg> clr_segs;     // k_svc_clear's segment list (rebuilt per call: hist_win and lvl_last change places)
+	DevBuf<unsigned long long> stale_bits; // gys_list_stale_listeners scratch (grows)
+	DevBuf<uint32_t> stale_tiles;
+	DevBuf<uint64_t> stale_ids;
 	std::vector<HostListeners> host_lst;
 	std::vector<uint32_t> host_seen; // batch stamp per host (duplicate-host detection in a multi-segment batch)
 	uint32_t batch_stamp = 0;
 	uint64_t n_batches_host_local = 0, n_batches_general = 0, n_batches_host_split = 0;
 	uint64_t htbl_used = 0, htbl_cap = 0, hlst_used = 0, hlst_cap = 0;
 	uint32_t resp_dyn_max = 0; // dynamic LDS a k_resp_host launch may use (160 KiB minus the kernel's static part)
-	uint64_t *htbl = nullptr; // pool of per-host sub-tables
-	uint32_t *hlst = nullptr; // pool of per-host local index -> slot lists
-	HostDesc *hdesc = nullptr; // [max_hosts] by host slot, then hdesc_ext_cap descriptors of the parts of many-listener hosts
-	ListenerCand *cand_pool = nullptr; // candidate records of the keys that need the server address (allocated on first use)
-	uint64_t cand_used = 0, cand_cap = 0;
+	DevBuf<uint64_t> htbl; // pool of per-host sub-tables
+	DevBuf<uint32_t> hlst; // pool of per-host local index -> slot lists
+	DevBuf<HostDesc> hdesc; // [max_hosts] by host slot, then hdesc_ext_cap descriptors of the parts of many-listener hosts
+	DevBuf<ListenerCand> cand_pool; // candidate records of the keys that need the server address (allocated on first use)
+	uint64_t cand_used = 0; // records handed out to the hosts' regions (cand_pool.cap: records allocated)
 	uint32_t hdesc_ext_used = 0, hdesc_ext_cap = 0;
 
 	// device state
-	DevTable lk_tbl{}, gid_tbl{};
-	uint64_t *svc_gid = nullptr;
-	gys_hist_rec *hist_win = nullptr, *hist_all = nullptr;
-	uint32_t *bitmap = nullptr;
-	int64_t *td_sum = nullptr;
-	uint32_t *td_cnt = nullptr;
-	TdMeta *td_meta = nullptr;
-	int2 *td_minmax = nullptr;
-	uint32_t *td_pend = nullptr;     // per service a buffer of pcap staged words ("per-key value buffers" in gys_kernels.hpp)
-	uint32_t *td_cur = nullptr;      // words in each buffer (== td_meta.npend between batches)
-	uint32_t *td_run = nullptr;      // spilled services: fill cursor of the run in `staged`
-	uint32_t *svc_host = nullptr;    // host slot of each service
-	uint32_t *host_spill = nullptr;  // per host: batch stamp of the last batch in which one of its services spilled
+	DevTable lk_tbl{}, gid_tbl{}; // (views, passed to the kernels by value: lk_ent / gid_ent own their entries)
+	DevBuf<TblEnt> lk_ent, gid_ent;
+	DevBuf<uint64_t> svc_gid;
+	DevBuf<gys_hist_rec> hist_win, hist_all;
+	DevBuf<uint32_t> bitmap;
+	DevBuf<int64_t> td_sum;
+	DevBuf<uint32_t> td_cnt;
+	DevBuf<TdMeta> td_meta;
+	DevBuf<int2> td_minmax;
+	DevBuf<uint32_t> td_pend;     // per service a buffer of pcap staged words ("per-key value buffers" in gys_kernels.hpp)
+	DevBuf<uint32_t> td_cur;      // words in each buffer (== td_meta.npend between batches)
+	DevBuf<uint32_t> td_run;      // spilled services: fill cursor of the run in `staged`
+	DevBuf<uint32_t> svc_host;    // host slot of each service
+	DevBuf<uint32_t> host_spill;  // per host: batch stamp of the last batch in which one of its services spilled
 	// predicted runs (k_prespill): start / end of a service's predicted run, the values its last batch brought, "worth predicting" flags of
 	// the previous / this batch, hosts of the running batch, keys whose run goes into the buffer after all
-	uint32_t *td_run0 = nullptr, *td_run1 = nullptr, *td_prevm = nullptr, *pre_hot = nullptr, *host_batch = nullptr;
-	MergeEnt *append_list = nullptr;
-	uint64_t append_cap = 0, staged_cap = 0;
+	DevBuf<uint32_t> td_run0, td_run1, td_prevm, pre_hot, host_batch;
+	DevBuf<MergeEnt> append_list;
 	uint32_t pre_seq = 0; // k_prespill launches so far (parity = which pre_hot word it reads)
 	bool prespill = false;
 	uint32_t spill_stamp = 0;
 	uint32_t pcap = 0;
 	uint32_t pend_cap = GYS_TD_PEND_CAP, merge_fast = GYS_TDIGEST_MERGE_FAST; // the t-digest rule's buffer size (gys_config.td_pend_cap) and its fast merge class
-	MergeEnt *merge_list = nullptr, *merge_list_slow = nullptr, *merge_list1 = nullptr, *merge_list2 = nullptr, *huge_list = nullptr, *query_list = nullptr;
-	uint32_t *merge_count = nullptr; // [FIN_*]: the words of the FIN_* enum (gys_kernels.hpp); [FIN_QUERY_ONE] = 1 (query list)
-	uint32_t *resp_win = nullptr;    // per service: response events of the open window (-> Count-Min rows at the window boundary)
-	uint32_t *cms_partial = nullptr; // [cms_nch][GYS_CMS_D][GYS_CMS_W] partial rows of k_cms_partial
+	DevBuf<MergeEnt> merge_list, merge_list_slow, merge_list1, merge_list2, huge_list, query_list;
+	DevBuf<uint32_t> merge_count; // [FIN_*]: the words of the FIN_* enum (gys_kernels.hpp); [FIN_QUERY_ONE] = 1 (query list)
+	DevBuf<uint32_t> resp_win;    // per service: response events of the open window (-> Count-Min rows at the window boundary)
+	DevBuf<uint32_t> cms_partial; // [cms_nch][GYS_CMS_D][GYS_CMS_W] partial rows of k_cms_partial
 	uint32_t cms_nch = 0;
 	bool resp_dirty = false;
-	int64_t *query_sum = nullptr;    // scratch of the non-destructive merge behind gys_query_quantiles
-	uint32_t *query_cnt = nullptr;
-	uint32_t *batch_cnt = nullptr, *batch_off = nullptr, *scan_block_sums = nullptr;
-	uint64_t *ev_kv = nullptr;       // general front end: (slot, staged word) per event
-	uint64_t ev_kv_cap = 0; // events
-	uint32_t *staged = nullptr;      // runs of the general front end / of spilled services
+	DevBuf<int64_t> query_sum;    // scratch of the non-destructive merge behind gys_query_quantiles
+	DevBuf<uint32_t> query_cnt;
+	DevBuf<uint32_t> batch_cnt, batch_off, scan_block_sums;
+	DevBuf<uint64_t> ev_kv;       // general front end: (slot, staged word) per event
+	DevBuf<uint32_t> staged;      // runs of the general front end / of spilled services
 	// the window boundary's fixed sequence of copies / clears, captured once per registry shape as a hipGraph and replayed
 	hipGraph_t win_graph = nullptr;
 	hipGraphExec_t win_graph_exec = nullptr;
@@ -333,29 +244,29 @@ struct gys_ctx {
 	int win_graph_state = 0;      // 0 not tried, 1 usable, -1 capture unavailable: plain launches
 	uint64_t win_graph_launches = 0;
 	int64_t i64min = INT64_MIN;   // stable host source of the graph's 8-byte copy
-	uint32_t *huge_scratch = nullptr;
+	DevBuf<uint32_t> huge_scratch;
 	// several-workgroups-per-key path (gys_huge.hpp): per-entry accumulators, chunk prefix, global tail list, fallback list
-	unsigned long long *huge_acc = nullptr, *huge_tail = nullptr;
-	uint32_t *huge_tb_list = nullptr;
-	uint32_t *huge_bm = nullptr, *huge_chunk_off = nullptr;
-	MergeEnt *huge_fb_list = nullptr;
+	DevBuf<unsigned long long> huge_acc, huge_tail;
+	DevBuf<uint32_t> huge_tb_list;
+	DevBuf<uint32_t> huge_bm, huge_chunk_off;
+	DevBuf<MergeEnt> huge_fb_list;
 	uint32_t huge_maxent = 0;
 	uint64_t huge_list_cap = 0;
 	int huge_blocks = 0;
-	uint32_t *hll32 = nullptr;
-	unsigned long long *svc_ctr = nullptr;
-	unsigned long long *svc_act = nullptr; // per listener: ACTIVE_CONN_STATS rows, bytes sent / received, active connections (cumulative)
-	unsigned long long *svc_win = nullptr; // per-service window accumulators of the connection path (k_conn_ingest / k_conn_fold)
+	DevBuf<uint32_t> hll32;
+	DevBuf<unsigned long long> svc_ctr;
+	DevBuf<unsigned long long> svc_act; // per listener: ACTIVE_CONN_STATS rows, bytes sent / received, active connections (cumulative)
+	DevBuf<unsigned long long> svc_win; // per-service window accumulators of the connection path (k_conn_ingest / k_conn_fold)
 	bool conn_dirty = false;
-	uint8_t *svc_state = nullptr;
-	unsigned long long *svc_claim = nullptr; // [S] k_lstate_ingest / k_lstate_keep: last record of a call per listener
+	DevBuf<uint8_t> svc_state;
+	DevBuf<unsigned long long> svc_claim; // [S] k_lstate_ingest / k_lstate_keep: last record of a call per listener
 	uint32_t lstate_launch = 0;
-	uint8_t *svc_hll = nullptr;
-	int32_t *host_summ_win = nullptr, *host_summ_last = nullptr;
-	gys_host_state *host_state = nullptr;
-	uint32_t *host_state_epoch = nullptr, *host_cluster = nullptr;
-	uint64_t *counters = nullptr;
-	uint32_t *misc = nullptr; // [0] table insert failures, [1] topn count
+	DevBuf<uint8_t> svc_hll;
+	DevBuf<int32_t> host_summ_win, host_summ_last;
+	DevBuf<gys_host_state> host_state;
+	DevBuf<uint32_t> host_state_epoch, host_cluster;
+	DevBuf<uint64_t> counters;
+	DevBuf<uint32_t> misc; // [0] table insert failures, [1] topn count
 	// segment descriptors of the batches in flight: a caller's segs array is only valid during the call and several batches may be
 	// queued on the stream, so each call copies it into one of GYS_SEG_RING pinned host buffers (+ its own device buffer); a slot is
 	// reused only after the kernels that read it have finished (event)
@@ -369,17 +280,17 @@ struct gys_ctx {
 	std::vector<RespPartView> resp_pv;
 
 	// reduce arena + last-window results
-	uint8_t *arena = nullptr;
-	bool own_arena = false;
+	uint8_t *arena = nullptr; // (a view: the caller's gys_config.reduce_arena, or arena_own)
+	DevBuf<uint8_t> arena_own;
 	ArenaLayout al{};
-	uint8_t *last = nullptr; // copy of the reduced arena of the last finished window (queries read this)
-	uint32_t *last_act32 = nullptr;           // ACTIVE_CONN_STATS Count-Min pair the queries read: per-cell maximum over the tables of the
-	unsigned long long *last_act64 = nullptr; // last GYS_ACT_RING windows (a partha reports every 15 s, a window is 5 s; k_act_latch)
-	uint32_t *ring_act32 = nullptr, *act_live = nullptr;
-	unsigned long long *ring_act64 = nullptr;
+	DevBuf<uint8_t> last; // copy of the reduced arena of the last finished window (queries read this)
+	DevBuf<uint32_t> last_act32;           // ACTIVE_CONN_STATS Count-Min pair the queries read: per-cell maximum over the tables of the
+	DevBuf<unsigned long long> last_act64; // last GYS_ACT_RING windows (a partha reports every 15 s, a window is 5 s; k_act_latch)
+	DevBuf<uint32_t> ring_act32, act_live;
+	DevBuf<unsigned long long> ring_act64;
 	uint32_t epoch = 1;      // current window number (0 = never)
 	bool prepared = false;
-	uint32_t *d_epoch = nullptr; // device copy of `epoch` for the captured window graph
+	DevBuf<uint32_t> d_epoch; // device copy of `epoch` for the captured window graph
 	// gys_window_close: the WHOLE single-rank window boundary as one hipGraph per (registry shape, which folds are due)
 	struct CloseGraph {
 		hipGraph_t g = nullptr;
@@ -398,8 +309,7 @@ struct gys_ctx {
 	// MAX_L2_MISC_THREADS = 16 L2 threads (server/gy_mconnhdlr.h:60) call concurrently: slots are handed out under stage_mu, the
 	// memcpy into pinned memory runs outside any lock, the enqueue (stream order, shared flags) under enq_mu.
 	struct Stage {
-		uint8_t *h = nullptr, *d = nullptr;
-		uint64_t cap = 0;
+		PinnedPair<uint8_t> buf;
 		hipEvent_t done = nullptr;
 		hipEvent_t copied = nullptr; // (record batches: the slot's H2D copy on the copy stream)
 	};
@@ -430,7 +340,7 @@ struct gys_ctx {
 	struct SubQ {
 		enum Kind { RESP, CONN, LSTATE } kind = RESP; // (also its index in gys_ctx::sq)
 		struct Batch {
-			uint8_t *h = nullptr, *d = nullptr; // RESP: events; else [records: cap][offset per record: u32 x cap_recs][host slot per record: u32 x cap_recs]
+			PinnedPair<uint8_t> buf;            // RESP: events; else [records: cap][offset per record: u32 x cap_recs][host slot per record: u32 x cap_recs]
 			uint64_t fill = 0;                  // RESP: events; else record bytes (8-byte aligned per call)
 			uint32_t nrec = 0;                  // records (not RESP)
 			std::vector<gys_resp_seg> segs;     // RESP: a segment per call
@@ -439,7 +349,7 @@ struct gys_ctx {
 			uint32_t writers = 0;
 		} b[6];
 		int nb = 0;                     // batches in use: 6 (RESP) / 4
-		uint64_t cap = 0, buf_bytes = 0; // per batch: `fill` it holds, size of h / d
+		uint64_t cap = 0, buf_bytes = 0; // per batch: `fill` it holds, size of buf
 		uint32_t cap_recs = 0;
 		std::mutex mu;
 		std::condition_variable cv;
@@ -456,41 +366,38 @@ struct gys_ctx {
 		bool flusher_on = false, stop = false;
 		const char *word() const { return kind == RESP ? "response" : "record"; } // (error texts)
 	} sq[3];
-	uint8_t *dev_staging = nullptr;
-	uint64_t dev_staging_bytes = 0;
-	uint32_t *dev_offsets = nullptr;
-	uint32_t dev_offsets_cap = 0;
+	DevBuf<uint8_t> dev_staging; // device-pointer record calls: the records and their offsets (grow)
+	DevBuf<uint32_t> dev_offsets;
 	// which service belongs to which host, which host to which cluster: counted up by every call that changes either (services added or
 	// deleted, a host registered or moved to another cluster, a cluster added).  The two cached groupings are rebuilt when it has moved:
 	// host -> services (ascending slot inside a host, the tie-break order of the top-N; roll-ups, all-hosts top-N) and cluster -> hosts
 	uint64_t registry_gen = 0;
 	DeviceGroups host_groups, cluster_groups;
 	std::vector<uint16_t> svc_port_h; // listener port per service slot (web_curr_top_listeners "port")
-	uint32_t *topn_slot = nullptr;
-	uint64_t *topn_metric = nullptr;
+	DevBuf<uint32_t> topn_slot;
+	DevBuf<uint64_t> topn_metric;
 	// filtered multi-host listener-state query (gys_svcquery.hpp): scratch, grow-only
 	DevBuf<unsigned long long> q_cand_key, q_out_keys, q_cnt;
 	DevBuf<uint32_t> q_cand_slot, q_misc, q_host_mask, q_slot_list;
 	DevBuf<int32_t> q_set;
 	DevBuf<uint8_t> q_out_rows;
 	DevBuf<long long> q_acc;
-	float *dev_pcts = nullptr;
-	float *zipf_cdf = nullptr;
+	DevBuf<float> dev_pcts;
+	DevBuf<float> zipf_cdf;
 	uint32_t zipf_n = 0, zipf_milli = 0;
 
 	// wire front-end scratch (grow-only)
-	uint64_t wire_slots_cap = 0;
-	uint32_t *wire_jump[2] = {nullptr, nullptr}, *wire_cnt = nullptr, *wire_rank = nullptr, *wire_bsums = nullptr, *wire_status = nullptr;
-	uint8_t *wire_mark = nullptr, *wire_flags = nullptr;
-	WireMsg *wire_msgs = nullptr;
-	uint32_t wire_msgs_cap = 0;
+	uint64_t wire_slots_cap = 0; // slots the per-slot arrays hold; kept apart from their .cap: wire_bsums holds a word per scan tile, not per slot
+	DevBuf<uint32_t> wire_jump[2], wire_cnt, wire_rank, wire_bsums, wire_status;
+	DevBuf<uint8_t> wire_mark, wire_flags;
+	DevBuf<WireMsg> wire_msgs;
 
 	// multi-level windows (cfg.enable_levels; kernels: "multi-level windows" in gys_kernels.hpp)
-	gys_hist_rec *lvl_snap = nullptr; // [2][GYS_LEVEL_RING][max_services] cumulative records at the last start of every ring bucket
-	gys_hist_rec *lvl_last = nullptr; // [max_services] the window closed last (level 0)
+	DevBuf<gys_hist_rec> lvl_snap; // [2][GYS_LEVEL_RING][max_services] cumulative records at the last start of every ring bucket
+	DevBuf<gys_hist_rec> lvl_last; // [max_services] the window closed last (level 0)
 	// lazily folded records (t-digest on): hist_win and lvl_last change places at every close instead of a copy; lvl_last[slot] then is the service's
 	// record of window lvl_last_tag[slot] (written by the close's fold pass) and counts only when that is lvl_last_epoch, the window closed last
-	uint32_t *lvl_last_tag = nullptr;
+	DevBuf<uint32_t> lvl_last_tag;
 	// roll-up digests (gys_rollup.hpp): the groups' value bins (GYS_RB_STRIDE words per group; grows)
 	DevBuf<unsigned long long> rb_bins;
 	// distinct counts (gys_hllroll.hpp): one scratch buffer (grows: a file per chunk, per host and per group -- first call / after a
@@ -499,12 +406,12 @@ struct gys_ctx {
 	// group histograms of the levels (gys_histroll.hpp): one scratch buffer (grows: a record per chunk and per host)
 	DevBuf<gys_hist_rec> hr_buf;
 	// distinct counts of the closed windows (cfg.svc_hll_levels; "levels" in gys_hllroll.hpp)
-	uint8_t *hl_lvl = nullptr;        // [GYS_HLL_LVL_FILES][max_services] files: last, the two rings, all
+	DevBuf<uint8_t> hl_lvl;        // [GYS_HLL_LVL_FILES][max_services] files: last, the two rings, all
 	DevBuf<uint8_t> hl_view;          // a level's files of every service, materialised for gys_hll_rollup_level_dev (nsvc files; grows)
 	// filtered roll-ups (gys_rollsel.hpp): the services' labels (gys_set_service_groups; allocated on first use, GYS_NO_GROUP everywhere)
 	// and the scratch of a selection (grows): the items' groups, the groups' counters / cursors, the members, the chunk lists,
 	// the rows with their offsets, the scan's tile sums and the totals
-	uint32_t *svc_label = nullptr;
+	DevBuf<uint32_t> svc_label;
 	uint32_t label_domain = 0; // every label set so far is below this
 	DevBuf<uint32_t> rs_item_group, rs_counts, rs_members, rs_tiles, rs_tot;
 	DevBuf<RollupChunk> rs_chunks, rs_gchunks;
@@ -513,10 +420,10 @@ struct gys_ctx {
 	int64_t hl_t_last = -1;           // close time (s) of the last window rolled into hl_lvl, -1: none yet
 	uint32_t hl_roll_epoch = 0xFFFFFFFEu; // the window rolled last (a finish step that is retried after a failure further down must not roll twice)
 	int64_t hl_close_t = 0;           // close time (s) the prepared window was given (gys_window_prepare; the roll runs in gys_window_finish)
-	uint8_t *svc_bithist = nullptr; // [max_services][2] TCP_LISTENER::issue_bit_hist_ / high_resp_bit_hist_ (gys_decide_listener_state_dev; allocated on first use)
+	DevBuf<uint8_t> svc_bithist; // [max_services][2] TCP_LISTENER::issue_bit_hist_ / high_resp_bit_hist_ (gys_decide_listener_state_dev; allocated on first use)
 	uint32_t lvl_last_epoch = 0;
-	int64_t *lvl_first = nullptr;     // [max_services] time (s) of the service's first window close (firstTime_ of its series), 0: none yet
-	gys_hist_rec *qps_hist = nullptr, *act_hist = nullptr; // per-service QPS_HISTOGRAM / ACTIVE_CONN_HISTOGRAM
+	DevBuf<int64_t> lvl_first;     // [max_services] time (s) of the service's first window close (firstTime_ of its series), 0: none yet
+	DevBuf<gys_hist_rec> qps_hist, act_hist; // per-service QPS_HISTOGRAM / ACTIVE_CONN_HISTOGRAM
 	int64_t lvl_t_last = -1;          // close time (s) of the last window, -1: none yet
 
 	bool profile = false;
@@ -572,15 +479,6 @@ inline uint32_t grid_for(uint64_t n, uint32_t block, uint32_t cap)
 	return (uint32_t)g;
 }
 
-template <typename T>
-int dev_alloc(T **p, uint64_t count, bool zero = true)
-{
-	if (count == 0) count = 1;
-	HIPCHK(hipMalloc((void **)p, count * sizeof(T)));
-	if (zero) HIPCHK(hipMemset(*p, 0, count * sizeof(T)));
-	return GYS_OK;
-}
-
 // ---- staging ring of the host-pointer boundary (gys_ctx::Stage)
 int stage_acquire(gys_ctx *c, uint64_t bytes, int *idx)
 {
@@ -600,21 +498,18 @@ int stage_acquire(gys_ctx *c, uint64_t bytes, int *idx)
 	if (e == hipSuccess && hipEventQuery(st.done) == hipErrorNotReady) c->stage_waits++;
 	(void)hipGetLastError();
 	if (e == hipSuccess) e = hipEventSynchronize(st.done); // the kernels that read this slot last time are done (no-op unless the ring wrapped)
-	if (e == hipSuccess && bytes > st.cap) {
-		if (st.h) (void)hipHostFree(st.h);
-		if (st.d) (void)hipFree(st.d);
-		st.h = st.d = nullptr;
-		st.cap = align_up(std::max<uint64_t>(bytes, 1u << 20), 4096);
-		e = hipHostMalloc((void **)&st.h, st.cap, hipHostMallocDefault);
-		if (e == hipSuccess) e = hipMalloc((void **)&st.d, st.cap);
-		if (e != hipSuccess) st.cap = 0;
-	}
+	int rc = GYS_OK;
 	if (e != hipSuccess) {
 		set_err("staging slot: %s", hipGetErrorString(e));
+		rc = GYS_ERR_HIP;
+	} else if (bytes > st.buf.cap) {
+		rc = st.buf.grow(align_up(bytes, 4096), 1u << 20);
+	}
+	if (rc) {
 		std::lock_guard<std::mutex> lk(c->stage_mu);
 		c->stage_free.push_back(i);
 		c->stage_cv.notify_one();
-		return GYS_ERR_HIP;
+		return rc;
 	}
 	*idx = i;
 	return GYS_OK;
@@ -629,23 +524,10 @@ void stage_release(gys_ctx *c, int idx)
 
 int ensure_staging(gys_ctx *c, uint64_t bytes, uint32_t nrec)
 {
-	if (bytes > c->dev_staging_bytes) {
-		if (c->dev_staging) {
-			HIPCHK(hipStreamSynchronize(c->stream));
-			HIPCHK(hipFree(c->dev_staging));
-		}
-		c->dev_staging_bytes = align_up(std::max<uint64_t>(bytes, 1u << 20), 4096);
-		HIPCHK(hipMalloc((void **)&c->dev_staging, c->dev_staging_bytes));
-	}
-	if (nrec > c->dev_offsets_cap) {
-		if (c->dev_offsets) {
-			HIPCHK(hipStreamSynchronize(c->stream));
-			HIPCHK(hipFree(c->dev_offsets));
-		}
-		c->dev_offsets_cap = std::max<uint32_t>(nrec, 4096);
-		HIPCHK(hipMalloc((void **)&c->dev_offsets, (uint64_t)c->dev_offsets_cap * 4));
-	}
-	return GYS_OK;
+	int rc = GYS_OK;
+	if (bytes > c->dev_staging.cap) rc = c->dev_staging.grow(align_up(std::max<uint64_t>(bytes, 1u << 20), 4096), c->stream);
+	if (!rc && nrec > c->dev_offsets.cap) rc = c->dev_offsets.grow(std::max<uint32_t>(nrec, 4096), c->stream);
+	return rc;
 }
 
 int lookup_host(gys_ctx *c, const uint8_t machine_id[16], uint32_t *slot)
@@ -753,19 +635,11 @@ int host_cands_upload(gys_ctx *c, HostListeners &hl)
 			set_err("listener candidate pool exhausted");
 			return GYS_ERR_NOMEM;
 		}
-		if (c->cand_used + want > c->cand_cap) {
-			uint64_t ncap = std::max<uint64_t>(c->cand_cap * 2, 4096);
+		if (c->cand_used + want > c->cand_pool.cap) {
+			uint64_t ncap = std::max<uint64_t>(c->cand_pool.cap * 2, 4096);
 			while (ncap < c->cand_used + want) ncap *= 2;
-			ncap = std::min(ncap, bound);
-			ListenerCand *np = nullptr;
-			HIPCHK(hipMalloc((void **)&np, ncap * sizeof(ListenerCand)));
-			if (c->cand_pool) {
-				HIPCHK(hipMemcpyAsync(np, c->cand_pool, c->cand_used * sizeof(ListenerCand), hipMemcpyDeviceToDevice, c->stream));
-				HIPCHK(hipStreamSynchronize(c->stream)); // (every launch that reads the old pool is behind us on this stream)
-				HIPCHK(hipFree(c->cand_pool));
-			}
-			c->cand_pool = np;
-			c->cand_cap = ncap;
+			const int rc = c->cand_pool.grow_keep(std::min(ncap, bound), c->cand_used, c->stream);
+			if (rc) return rc;
 		}
 		hl.cand_off = (uint32_t)c->cand_used;
 		hl.cand_cap = (uint32_t)want;
@@ -941,7 +815,7 @@ int host_lst_flush(gys_ctx *c, uint32_t host)
 			const int rs = ensure_staging(c, kv.size() * 8, 0);
 			if (rs) return rs;
 			HIPCHK(hipMemcpyAsync(c->dev_staging, kv.data(), kv.size() * 8, hipMemcpyHostToDevice, c->stream));
-			hipLaunchKernelGGL(k_table_set, dim3((nk + 255) / 256), dim3(256), 0, c->stream, c->lk_tbl, (const uint64_t *)c->dev_staging, nk);
+			hipLaunchKernelGGL(k_table_set, dim3((nk + 255) / 256), dim3(256), 0, c->stream, c->lk_tbl, (const uint64_t *)c->dev_staging.p, nk);
 			HIPCHK(hipStreamSynchronize(c->stream));
 		}
 	}
@@ -1233,7 +1107,7 @@ int resp_fill_params(gys_ctx *c, RespBatch &b)
 		fin.svc_host = c->svc_host;
 		fin.host_spill = c->host_spill;
 		fin.counters = c->counters;
-		fin.staged_cap = (uint32_t)std::min<uint64_t>(c->staged_cap, 0xFFFFFFFFull);
+		fin.staged_cap = (uint32_t)std::min<uint64_t>(c->staged.cap, 0xFFFFFFFFull);
 	}
 	if (b.td && c->prespill) {
 		fin.td_run0 = c->td_run0;
@@ -1242,7 +1116,7 @@ int resp_fill_params(gys_ctx *c, RespBatch &b)
 		fin.hot = c->pre_hot;
 		fin.hot_wr = b.pre ? ((c->pre_seq & 1u) ^ 1u) : (c->pre_seq & 1u); // the word the NEXT k_prespill reads (this batch's own one, if any, reads the other)
 		fin.append_list = c->append_list;
-		fin.append_cap = (uint32_t)c->append_cap;
+		fin.append_cap = (uint32_t)c->append_list.cap;
 		fin.td_pend = c->td_pend;
 		fin.staged = c->staged;
 		HIPCHK(hipMemsetAsync(c->merge_count + FIN_APPEND, 0, (FIN_NWORDS - FIN_APPEND) * 4, c->stream)); // (the append list's length; the predicted runs' reservation counter)
@@ -1263,7 +1137,7 @@ int resp_fill_params(gys_ctx *c, RespBatch &b)
 	hp.pcap = c->pcap;
 	hp.td_run = c->td_run;
 	hp.td_run1 = c->td_run1;
-	hp.run_delta = (long long)(((intptr_t)c->staged - (intptr_t)c->td_pend) / 4);
+	hp.run_delta = (long long)(((intptr_t)c->staged.p - (intptr_t)c->td_pend.p) / 4);
 	hp.staged = c->staged;
 	hp.host_spill = c->host_spill;
 	hp.spill_stamp = ++c->spill_stamp;
@@ -1325,7 +1199,7 @@ int resp_launch_host_local(gys_ctx *c, RespBatch &b)
 		pp.pcap = c->pcap;
 		pp.pend_cap = c->pend_cap;
 		pp.resv = (unsigned long long *)(c->merge_count + FIN_PRE_RESV); // (cleared at the start of the batch)
-		pp.run_limit = (uint32_t)std::min<uint64_t>(c->staged_cap - std::min<uint64_t>(b.n, c->staged_cap), 0xFFFFFFFFull); // the exact runs of the fall-back (<= n words) keep their room
+		pp.run_limit = (uint32_t)std::min<uint64_t>(c->staged.cap - std::min<uint64_t>(b.n, c->staged.cap), 0xFFFFFFFFull); // the exact runs of the fall-back (<= n words) keep their room
 		++c->pre_seq;
 		hipLaunchKernelGGL(k_mark_hosts, dim3((b.nsegs + 255) / 256), dim3(256), 0, c->stream, b.slot->segs.dev, b.nsegs, c->host_batch, c->batch_stamp);
 		hipLaunchKernelGGL(k_prespill, dim3((c->nsvc + 255) / 256), dim3(256), 0, c->stream, pp);
@@ -1579,7 +1453,7 @@ int hll_level_roll(gys_ctx *c)
 			if (((mask[li] >> j) & 1u) && j != cur[li])
 				HIPCHK(hipMemsetAsync(hll_level_array(c, GYS_HLL_LVL_RING + (uint32_t)li * GYS_LEVEL_RING + j), 0, (uint64_t)c->nsvc << p, c->stream));
 	HllLevelRollP q{};
-	q.open = (uint4 *)c->svc_hll;
+	q.open = (uint4 *)c->svc_hll.p;
 	q.last = (uint4 *)hll_level_array(c, GYS_HLL_LVL_LAST);
 	q.ring1 = (uint4 *)hll_level_array(c, GYS_HLL_LVL_RING + cur[0]);
 	q.ring2 = (uint4 *)hll_level_array(c, GYS_HLL_LVL_RING + GYS_LEVEL_RING + cur[1]);
@@ -1925,18 +1799,18 @@ int ingest_staged_records(gys_ctx *c, uint32_t host, const void *batch, uint64_t
 	int rc = stage_acquire(c, total, &si);
 	if (rc) return rc;
 	gys_ctx::Stage &st = c->stage[si];
-	memcpy(st.h, batch, bytes);
-	memcpy(st.h + off_at, offs.data(), offs.size() * 4);
+	memcpy(st.buf.host, batch, bytes);
+	memcpy(st.buf.host + off_at, offs.data(), offs.size() * 4);
 	{
 		std::lock_guard<std::mutex> g(c->enq_mu);
 		// (copy on the copy stream, kernels on the engine stream behind an event -- as for the response submissions: the copy of one
 		// message runs under the kernels of the message before it)
-		hipError_t e = hipMemcpyAsync(st.d, st.h, total, hipMemcpyHostToDevice, c->copy_stream);
+		hipError_t e = hipMemcpyAsync(st.buf.dev, st.buf.host, total, hipMemcpyHostToDevice, c->copy_stream);
 		if (e == hipSuccess) e = hipEventRecord(st.copied, c->copy_stream);
 		if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, st.copied, 0);
 		if (e == hipSuccess) {
-			rc = conn ? run_conn(c, st.d, (const uint32_t *)(st.d + off_at), (uint32_t)offs.size())
-				  : run_lstate(c, st.d, (const uint32_t *)(st.d + off_at), nullptr, host, (uint32_t)offs.size());
+			rc = conn ? run_conn(c, st.buf.dev, (const uint32_t *)(st.buf.dev + off_at), (uint32_t)offs.size())
+				  : run_lstate(c, st.buf.dev, (const uint32_t *)(st.buf.dev + off_at), nullptr, host, (uint32_t)offs.size());
 			e = hipEventRecord(st.done, c->stream);
 		}
 		if (e != hipSuccess) {
@@ -1982,15 +1856,15 @@ int subq_submit_one(gys_ctx *c, SubQ &q, SubQ::Batch &b)
 	// submission (0.85 ms at 57 GB/s) and its kernels alternate; the batch's buffers are not reused before `done` has fired
 	hipStream_t cs = c->copy_stream;
 	const uint64_t off_at = q.cap, host_at = q.cap + (uint64_t)q.cap_recs * 4;
-	hipError_t e = hipMemcpyAsync(b.d, b.h, resp ? b.fill * 24 : b.fill, hipMemcpyHostToDevice, cs);
-	if (e == hipSuccess && !resp) e = hipMemcpyAsync(b.d + off_at, b.h + off_at, (uint64_t)b.nrec * 4, hipMemcpyHostToDevice, cs);
-	if (e == hipSuccess && q.kind == SubQ::LSTATE) e = hipMemcpyAsync(b.d + host_at, b.h + host_at, (uint64_t)b.nrec * 4, hipMemcpyHostToDevice, cs);
+	hipError_t e = hipMemcpyAsync(b.buf.dev, b.buf.host, resp ? b.fill * 24 : b.fill, hipMemcpyHostToDevice, cs);
+	if (e == hipSuccess && !resp) e = hipMemcpyAsync(b.buf.dev + off_at, b.buf.host + off_at, (uint64_t)b.nrec * 4, hipMemcpyHostToDevice, cs);
+	if (e == hipSuccess && q.kind == SubQ::LSTATE) e = hipMemcpyAsync(b.buf.dev + host_at, b.buf.host + host_at, (uint64_t)b.nrec * 4, hipMemcpyHostToDevice, cs);
 	if (e == hipSuccess) e = hipEventRecord(b.copied, cs);
 	if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, b.copied, 0);
 	if (e == hipSuccess) {
-		if (resp) rc = run_resp_batch(c, b.segs.data(), (uint32_t)b.segs.size(), b.d, b.fill);
-		else if (q.kind == SubQ::CONN) rc = run_conn(c, b.d, (const uint32_t *)(b.d + off_at), b.nrec);
-		else rc = run_lstate(c, b.d, (const uint32_t *)(b.d + off_at), (const uint32_t *)(b.d + host_at), 0, b.nrec);
+		if (resp) rc = run_resp_batch(c, b.segs.data(), (uint32_t)b.segs.size(), b.buf.dev, b.fill);
+		else if (q.kind == SubQ::CONN) rc = run_conn(c, b.buf.dev, (const uint32_t *)(b.buf.dev + off_at), b.nrec);
+		else rc = run_lstate(c, b.buf.dev, (const uint32_t *)(b.buf.dev + off_at), (const uint32_t *)(b.buf.dev + host_at), 0, b.nrec);
 		e = hipEventRecord(b.done, c->stream);
 	}
 	if (e != hipSuccess) {
@@ -2145,27 +2019,20 @@ int subq_ingest(gys_ctx *c, SubQ &q, uint32_t host, const void *data, uint64_t b
 			q.free.pop_front();
 			SubQ::Batch &nb = q.b[bi];
 			lk.unlock(); // (first-use allocation: outside the lock; the batch is not visible yet)
+			// the buffers (both or none: PinnedPair) and the two events; what a failure leaves built, the next caller of this batch completes
+			int arc = nb.buf.cap ? GYS_OK : nb.buf.grow(q.buf_bytes, 0);
 			hipError_t e = hipSuccess;
-			if (!nb.h || !nb.d || !nb.done || !nb.copied) {
-				if (!nb.h) e = hipHostMalloc((void **)&nb.h, q.buf_bytes, hipHostMallocDefault);
-				if (e == hipSuccess && !nb.d) e = hipMalloc((void **)&nb.d, q.buf_bytes);
-				if (e == hipSuccess && !nb.done) e = hipEventCreateWithFlags(&nb.done, hipEventDisableTiming);
-				if (e == hipSuccess && !nb.copied) e = hipEventCreateWithFlags(&nb.copied, hipEventDisableTiming);
-				if (e != hipSuccess) { // all four or none: a half-built batch must not look usable to the next caller
-					if (nb.h) (void)hipHostFree(nb.h);
-					if (nb.d) (void)hipFree(nb.d);
-					if (nb.done) (void)hipEventDestroy(nb.done);
-					if (nb.copied) (void)hipEventDestroy(nb.copied);
-					nb.h = nb.d = nullptr;
-					nb.done = nb.copied = nullptr;
-				}
+			if (!arc && !nb.done) e = hipEventCreateWithFlags(&nb.done, hipEventDisableTiming);
+			if (!arc && e == hipSuccess && !nb.copied) e = hipEventCreateWithFlags(&nb.copied, hipEventDisableTiming);
+			if (e != hipSuccess) {
+				set_err("%s batch events: %s", q.word(), hipGetErrorString(e));
+				arc = GYS_ERR_HIP;
 			}
 			lk.lock();
-			if (e != hipSuccess) {
+			if (arc) {
 				q.free.push_back(bi);
 				q.cv.notify_all();
-				set_err("%s batch buffers: %s", q.word(), hipGetErrorString(e));
-				return GYS_ERR_HIP;
+				return arc;
 			}
 			if (q.open >= 0) { // another caller opened one meanwhile
 				q.free.push_front(bi);
@@ -2196,10 +2063,10 @@ int subq_ingest(gys_ctx *c, SubQ &q, uint32_t host, const void *data, uint64_t b
 	b.writers++;
 	lk.unlock();
 	if (resp) {
-		memcpy(b.h + at * 24, data, (uint64_t)n * 24);
+		memcpy(b.buf.host + at * 24, data, (uint64_t)n * 24);
 	} else {
-		memcpy(b.h + at, data, bytes);
-		uint32_t *o = (uint32_t *)(b.h + q.cap) + r0;
+		memcpy(b.buf.host + at, data, bytes);
+		uint32_t *o = (uint32_t *)(b.buf.host + q.cap) + r0;
 		for (uint32_t i = 0; i < n; ++i) o[i] = offs[i] + (uint32_t)at;
 		if (q.kind == SubQ::LSTATE) std::fill_n(o + q.cap_recs, n, host);
 	} // the caller's buffer is free from here on
@@ -2234,13 +2101,13 @@ int ingest_staged_resp(gys_ctx *c, uint32_t host, const void *ev, uint32_t neven
 	rc = stage_acquire(c, bytes, &si);
 	if (rc) return rc;
 	gys_ctx::Stage &st = c->stage[si];
-	memcpy(st.h, ev, bytes); // the caller's buffer is free from here on
+	memcpy(st.buf.host, ev, bytes); // the caller's buffer is free from here on
 	{
 		std::lock_guard<std::mutex> g(c->enq_mu);
-		hipError_t e = hipMemcpyAsync(st.d, st.h, bytes, hipMemcpyHostToDevice, c->stream);
+		hipError_t e = hipMemcpyAsync(st.buf.dev, st.buf.host, bytes, hipMemcpyHostToDevice, c->stream);
 		if (e == hipSuccess) {
 			gys_resp_seg seg{host, 0, 0};
-			rc = run_resp_batch(c, &seg, 1, st.d, nevents, v6);
+			rc = run_resp_batch(c, &seg, 1, st.buf.dev, nevents, v6);
 			e = hipEventRecord(st.done, c->stream);
 		}
 		if (e != hipSuccess) {
@@ -2325,7 +2192,14 @@ try {
 		set_err("no HIP device");
 		return GYS_ERR_HIP;
 	}
-	gys_ctx *c = new gys_ctx();
+	// the context is destroyed on every early return below; released at `*out = c`.  A failed create also takes the runtime's "last error"
+	// with it (an invalid device ordinal, say): the caller has the code and the text, and the thread's next HIP user -- whose launch
+	// check reads hipGetLastError -- must not find this one
+	std::unique_ptr<gys_ctx, void (*)(gys_ctx *)> guard(new gys_ctx(), [](gys_ctx *dead) {
+		gys_destroy(dead);
+		(void)hipGetLastError();
+	});
+	gys_ctx *c = guard.get();
 	for (int i = 0; i < gys_ctx::NSTAGE; ++i) c->stage_free.push_back(i);
 	c->cfg = *cfg;
 	for (SubQ::Kind k : {SubQ::RESP, SubQ::CONN, SubQ::LSTATE}) subq_init(c, k);
@@ -2348,13 +2222,12 @@ try {
 	const uint64_t S = cfg->max_services, H = cfg->max_hosts;
 	const uint32_t cap = next_pow2(S * 2);
 	int rc;
-#define ALLOC(ptr, count)                        \
-	if ((rc = dev_alloc(&ptr, (count))) != GYS_OK) { \
-		gys_destroy(c);                          \
-		return rc;                               \
-	}
-	ALLOC(c->lk_tbl.ent, cap);
-	ALLOC(c->gid_tbl.ent, cap);
+#define ALLOC(buf, count) \
+	if ((rc = buf.alloc(count)) != GYS_OK) return rc;
+	ALLOC(c->lk_ent, cap);
+	ALLOC(c->gid_ent, cap);
+	c->lk_tbl.ent = c->lk_ent;
+	c->gid_tbl.ent = c->gid_ent;
 	c->lk_tbl.mask = c->gid_tbl.mask = cap - 1;
 	HIPCHK(hipMemset(c->lk_tbl.ent, 0xFF, (uint64_t)cap * sizeof(TblEnt)));
 	HIPCHK(hipMemset(c->gid_tbl.ent, 0xFF, (uint64_t)cap * sizeof(TblEnt)));
@@ -2445,10 +2318,7 @@ try {
 		ALLOC(c->td_minmax, S);
 		ALLOC(c->td_cur, align_up(S, 64));
 		ALLOC(c->td_run, S);
-		if ((rc = dev_alloc(&c->td_pend, S * c->pcap, false)) != GYS_OK) { // never read before written: no clear of (up to) tens of GB
-			gys_destroy(c);
-			return rc;
-		}
+		if ((rc = c->td_pend.alloc(S * c->pcap, false)) != GYS_OK) return rc; // never read before written: no clear of (up to) tens of GB
 		ALLOC(c->merge_list, std::min<uint64_t>(S, B) + 1);
 		ALLOC(c->merge_list_slow, S + 1); // (the all-service scan may list any service)
 		// a key lands in a larger merge size class only when the batch itself brought it more than CLASS0 - PEND_CAP values
@@ -2469,23 +2339,18 @@ try {
 		ALLOC(c->batch_off, align_up(S, 16));
 		ALLOC(c->scan_block_sums, (S + GYS_SCAN_TILE - 1) / GYS_SCAN_TILE + 1);
 		ALLOC(c->ev_kv, B);
-		c->ev_kv_cap = B;
 		// `staged`: the runs of one batch.  With predicted runs (k_prespill) a batch may need the predicted runs (the last batch's counts
 		// plus a quarter, + 64 per key) AND the exact runs of the keys the prediction missed (<= B): 5/2 B + slack, while indices stay 32-bit
 		c->prespill = B * 5 / 2 + (1u << 24) < (1ull << 32);
-		c->staged_cap = c->prespill ? B * 5 / 2 + (1u << 24) : B;
-		if ((rc = dev_alloc(&c->staged, c->staged_cap, false)) != GYS_OK) { // (runs are written before they are read)
-			gys_destroy(c);
-			return rc;
-		}
+		if ((rc = c->staged.alloc(c->prespill ? B * 5 / 2 + (1u << 24) : B, false)) != GYS_OK) return rc; // (runs are written before they are read)
 		if (c->prespill) {
 			ALLOC(c->td_run0, S);
 			ALLOC(c->td_run1, S);
 			ALLOC(c->td_prevm, S);
 			ALLOC(c->pre_hot, 2);
 			ALLOC(c->host_batch, H);
-			c->append_cap = S + 1; // (a key has at most one entry per batch; the keys of a batch are not bounded by its size: predictions come from EARLIER batches)
-			ALLOC(c->append_list, c->append_cap);
+			// S + 1 entries (a key has at most one entry per batch; the keys of a batch are not bounded by its size: predictions come from EARLIER batches)
+			ALLOC(c->append_list, S + 1);
 		}
 		c->huge_blocks = (int)std::min<uint64_t>(64, std::min<uint64_t>(S, B / GYS_MERGE_LDS_MAX + 1));
 		if (c->huge_blocks < 1) c->huge_blocks = 1;
@@ -2537,22 +2402,21 @@ try {
 	if (cfg->reduce_arena) {
 		if (cfg->reduce_arena_bytes < c->al.total) {
 			set_err("reduce_arena too small: %llu < %llu", (unsigned long long)cfg->reduce_arena_bytes, (unsigned long long)c->al.total);
-			gys_destroy(c);
 			return GYS_ERR_INVAL;
 		}
 		c->arena = (uint8_t *)cfg->reduce_arena;
 	} else {
-		HIPCHK(hipMalloc((void **)&c->arena, c->al.total));
-		c->own_arena = true;
+		if ((rc = c->arena_own.alloc(c->al.total, false)) != GYS_OK) return rc;
+		c->arena = c->arena_own;
 	}
-	HIPCHK(hipMalloc((void **)&c->last, c->al.total));
+	if ((rc = c->last.alloc(c->al.total, false)) != GYS_OK) return rc;
 	HIPCHK(hipMemsetAsync(c->arena, 0, c->al.total, c->stream));
 	HIPCHK(hipMemsetAsync(c->last, 0, c->al.total, c->stream));
 	{
 		HIPCHK(hipMemcpyAsync(c->arena + c->al.off_i64max, &c->i64min, 8, hipMemcpyHostToDevice, c->stream));
 	}
 	HIPCHK(hipStreamSynchronize(c->stream));
-	*out = c;
+	*out = guard.release();
 	return GYS_OK;
 } GYS_CATCH_ALL
 
@@ -2582,29 +2446,17 @@ void gys_destroy(gys_ctx *c)
 	}
 	for (auto &q : c->sq)
 		for (auto &b : q.b) {
-			if (b.h) hipHostFree(b.h);
-			if (b.d) hipFree(b.d);
 			if (b.done) hipEventDestroy(b.done);
 			if (b.copied) hipEventDestroy(b.copied);
 		}
 	if (c->copy_stream) hipStreamDestroy(c->copy_stream);
 	for (auto &st : c->stage) {
-		if (st.h) hipHostFree(st.h);
-		if (st.d) hipFree(st.d);
 		if (st.done) hipEventDestroy(st.done);
 		if (st.copied) hipEventDestroy(st.copied);
 	}
 	prof_resolve(c);
-	void *ptrs[] = {c->lk_tbl.ent, c->gid_tbl.ent, c->svc_gid, c->hist_win, c->hist_all, c->bitmap, c->td_sum,
-			c->td_cnt, c->td_meta, c->td_minmax, c->td_pend, c->td_cur, c->td_run, c->td_run0, c->td_run1, c->td_prevm, c->pre_hot, c->host_batch, c->append_list, c->svc_host, c->host_spill, c->merge_list, c->merge_list_slow, c->merge_list1, c->merge_list2, c->resp_win, c->cms_partial, c->huge_list, c->query_list, c->merge_count, c->query_sum, c->query_cnt,
-			c->batch_cnt, c->batch_off, c->scan_block_sums, c->ev_kv, c->staged, c->huge_scratch, c->huge_acc, c->huge_tail, c->huge_tb_list, c->huge_bm, c->huge_chunk_off, c->huge_fb_list, c->hll32, c->svc_ctr, c->svc_win, c->svc_state, c->svc_claim, c->svc_hll, c->host_summ_win, c->host_summ_last, c->host_state,
-			c->host_state_epoch, c->host_cluster, c->counters, c->misc, c->htbl, c->hlst, c->hdesc, c->wire_jump[0], c->wire_jump[1], c->wire_cnt,
-			c->wire_rank, c->wire_bsums, c->wire_status, c->wire_mark, c->wire_flags, c->wire_msgs, c->last, c->last_act32, c->last_act64, c->ring_act32, c->ring_act64, c->act_live, c->dev_staging, c->dev_offsets, c->svc_act, c->d_epoch, c->topn_slot,
-			c->topn_metric, c->dev_pcts, c->zipf_cdf, c->lvl_snap, c->lvl_last, c->lvl_last_tag, c->svc_bithist, c->hl_lvl, c->svc_label, c->lvl_first, c->qps_hist, c->act_hist, c->cand_pool, c->clr_segs, c->stale_bits, c->stale_tiles, c->stale_ids, c->own_arena ? c->arena : nullptr};
-	for (void *p : ptrs)
-		if (p) hipFree(p);
 	if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
-	delete c;
+	delete c; // (frees all device and pinned memory: the members' destructors)
 }
 
 int gys_sync(gys_ctx *c)
@@ -2718,8 +2570,8 @@ try {
 	HIPCHK(hipMemcpyAsync(c->dev_staging, keys.data(), keys.size() * 8, hipMemcpyHostToDevice, c->stream));
 	HIPCHK(hipMemcpyAsync(c->svc_gid + c->nsvc, c->dev_staging, (size_t)n * 8, hipMemcpyDeviceToDevice, c->stream));
 	HIPCHK(hipMemsetAsync(c->misc, 0, 4, c->stream));
-	hipLaunchKernelGGL(k_table_insert, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->gid_tbl, (const uint64_t *)c->dev_staging, c->nsvc, n, c->misc);
-	hipLaunchKernelGGL(k_table_insert, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->lk_tbl, (const uint64_t *)c->dev_staging + n, c->nsvc, n,
+	hipLaunchKernelGGL(k_table_insert, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->gid_tbl, (const uint64_t *)c->dev_staging.p, c->nsvc, n, c->misc);
+	hipLaunchKernelGGL(k_table_insert, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->lk_tbl, (const uint64_t *)c->dev_staging.p + n, c->nsvc, n,
 			   c->misc);
 	uint32_t nfail = 0;
 	HIPCHK(hipMemcpyAsync(&nfail, c->misc, 4, hipMemcpyDeviceToHost, c->stream));
@@ -2809,8 +2661,8 @@ static int svc_clear_prepare(gys_ctx *c, std::vector<SvcClearSeg> &segs, uint64_
 		set_err("internal error: %zu clear segments", segs.size());
 		return GYS_ERR_INTERNAL;
 	}
-	if (!c->clr_segs) HIPCHK(hipMalloc((void **)&c->clr_segs, GYS_SVCCLEAR_MAXSEG * sizeof(SvcClearSeg)));
-	return ensure_staging(c, staging_bytes, 0);
+	const int rc = c->clr_segs.p ? GYS_OK : c->clr_segs.alloc(GYS_SVCCLEAR_MAXSEG, false);
+	return rc ? rc : ensure_staging(c, staging_bytes, 0);
 }
 // d_slots: nslots slot numbers on the device.  segs has to stay alive until the stream has been synchronised.
 static int svc_clear_launch(gys_ctx *c, const std::vector<SvcClearSeg> &segs, const uint32_t *d_slots, uint32_t nslots)
@@ -2911,8 +2763,8 @@ try {
 	HIPCHK(hipMemcpyAsync(c->dev_staging + keys_bytes, del.data(), (size_t)nd * 4, hipMemcpyHostToDevice, c->stream));
 	{
 		ProfScope ps(c, "table_erase");
-		hipLaunchKernelGGL(k_table_erase, dim3(1), dim3(64), 0, c->stream, c->gid_tbl, (const uint64_t *)c->dev_staging, nd, (uint32_t *)nullptr);
-		if (nlk) hipLaunchKernelGGL(k_table_erase, dim3(1), dim3(64), 0, c->stream, c->lk_tbl, (const uint64_t *)c->dev_staging + nd, nlk, (uint32_t *)nullptr);
+		hipLaunchKernelGGL(k_table_erase, dim3(1), dim3(64), 0, c->stream, c->gid_tbl, (const uint64_t *)c->dev_staging.p, nd, (uint32_t *)nullptr);
+		if (nlk) hipLaunchKernelGGL(k_table_erase, dim3(1), dim3(64), 0, c->stream, c->lk_tbl, (const uint64_t *)c->dev_staging.p + nd, nlk, (uint32_t *)nullptr);
 	}
 	rc = svc_clear_launch(c, segs, (const uint32_t *)(c->dev_staging + keys_bytes), nd);
 	if (rc) return rc;
@@ -2986,7 +2838,7 @@ try {
 		std::vector<SvcClearSeg> segs;
 		rc = nfree ? svc_clear_prepare(c, segs, keys_bytes + (uint64_t)n * 4) : ensure_staging(c, keys_bytes + (uint64_t)n * 4, 0);
 		if (rc) return rc;
-		const uint64_t *d_keys = (const uint64_t *)c->dev_staging;
+		const uint64_t *d_keys = (const uint64_t *)c->dev_staging.p;
 		const uint32_t *d_sl = (const uint32_t *)(c->dev_staging + keys_bytes);
 		HIPCHK(hipMemcpyAsync(c->dev_staging, keys.data(), keys_bytes, hipMemcpyHostToDevice, c->stream));
 		HIPCHK(hipMemcpyAsync(c->dev_staging + keys_bytes, sl.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
@@ -3064,26 +2916,14 @@ try {
 	p.max_age = max_age_windows;
 	cap = std::min(cap, c->nsvc); // (there are no more hits than services: a caller's "everything" does not size the id buffer)
 	p.cap = cap;
-	if (c->stale_tiles_cap < p.ntiles) {
-		HIPCHK(hipStreamSynchronize(c->stream));
-		if (c->stale_bits) HIPCHK(hipFree(c->stale_bits));
-		if (c->stale_tiles) HIPCHK(hipFree(c->stale_tiles));
-		c->stale_bits = nullptr;
-		c->stale_tiles = nullptr;
-		c->stale_tiles_cap = 0;
+	int rc = GYS_OK;
+	if (c->stale_tiles.cap < p.ntiles + 1u || c->stale_bits.cap < p.ntiles * 16ull) { // (16 words and a count per tile, + the total)
 		const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(2ull * p.ntiles, 64), ((uint64_t)c->cfg.max_services + GYS_STALE_TILE - 1u) / GYS_STALE_TILE);
-		HIPCHK(hipMalloc((void **)&c->stale_bits, want * 16 * 8));
-		HIPCHK(hipMalloc((void **)&c->stale_tiles, (want + 1) * 4));
-		c->stale_tiles_cap = want;
+		rc = c->stale_bits.grow(want * 16, c->stream);
+		if (!rc) rc = c->stale_tiles.grow(want + 1, c->stream);
 	}
-	if (c->stale_ids_cap < cap) {
-		HIPCHK(hipStreamSynchronize(c->stream));
-		if (c->stale_ids) HIPCHK(hipFree(c->stale_ids));
-		c->stale_ids = nullptr;
-		c->stale_ids_cap = 0;
-		HIPCHK(hipMalloc((void **)&c->stale_ids, (uint64_t)cap * 8));
-		c->stale_ids_cap = cap;
-	}
+	if (!rc && c->stale_ids.cap < cap) rc = c->stale_ids.grow(cap, c->stream);
+	if (rc) return rc;
 	p.bits = c->stale_bits;
 	p.tile_cnt = c->stale_tiles;
 	p.ids = c->stale_ids;
@@ -3200,12 +3040,12 @@ try {
 	rc = stage_acquire(c, bytes, &si);
 	if (rc) return rc;
 	gys_ctx::Stage &st = c->stage[si];
-	memcpy(st.h, batch, bytes);
+	memcpy(st.buf.host, batch, bytes);
 	{
 		std::lock_guard<std::mutex> g(c->enq_mu);
-		hipError_t e = hipMemcpyAsync(st.d, st.h, bytes, hipMemcpyHostToDevice, c->stream);
+		hipError_t e = hipMemcpyAsync(st.buf.dev, st.buf.host, bytes, hipMemcpyHostToDevice, c->stream);
 		if (e == hipSuccess) {
-			rc = run_actconn(c, st.d, n);
+			rc = run_actconn(c, st.buf.dev, n);
 			e = hipEventRecord(st.done, c->stream);
 		}
 		if (e != hipSuccess) {
@@ -3248,32 +3088,20 @@ constexpr uint32_t MAX_NUM_CONNS_T = 2048, MAX_NUM_LISTENERS_T = 512;          /
 int wire_reserve(gys_ctx *c, uint64_t nslots, uint32_t nmsgs)
 {
 	if (nslots + 1 > c->wire_slots_cap) {
-		HIPCHK(hipStreamSynchronize(c->stream));
-		void *old[] = {c->wire_jump[0], c->wire_jump[1], c->wire_cnt, c->wire_rank, c->wire_bsums, c->wire_mark, c->wire_flags};
-		for (void *p : old)
-			if (p) hipFree(p);
-		c->wire_jump[0] = c->wire_jump[1] = c->wire_cnt = c->wire_rank = c->wire_bsums = nullptr;
-		c->wire_mark = c->wire_flags = nullptr;
 		const uint64_t cap = align_up(std::max<uint64_t>(nslots + 1, 1u << 16), 4096);
-		HIPCHK(hipMalloc((void **)&c->wire_jump[0], cap * 4));
-		HIPCHK(hipMalloc((void **)&c->wire_jump[1], cap * 4));
-		HIPCHK(hipMalloc((void **)&c->wire_cnt, cap * 4));
-		HIPCHK(hipMalloc((void **)&c->wire_rank, cap * 4));
-		HIPCHK(hipMalloc((void **)&c->wire_bsums, (cap / GYS_SCAN_TILE + 2) * 4));
-		HIPCHK(hipMalloc((void **)&c->wire_mark, cap));
-		HIPCHK(hipMalloc((void **)&c->wire_flags, cap));
+		c->wire_slots_cap = 0; // (a grow that fails leaves its array empty: no slot counts as reserved until all seven stand)
+		int rc = GYS_OK;
+		for (DevBuf<uint32_t> *b : {&c->wire_jump[0], &c->wire_jump[1], &c->wire_cnt, &c->wire_rank})
+			if (!rc) rc = b->grow(cap, c->stream);
+		if (!rc) rc = c->wire_bsums.grow(cap / GYS_SCAN_TILE + 2, c->stream);
+		if (!rc) rc = c->wire_mark.grow(cap, c->stream);
+		if (!rc) rc = c->wire_flags.grow(cap, c->stream);
+		if (rc) return rc;
 		c->wire_slots_cap = cap;
 	}
-	if (!c->wire_status) HIPCHK(hipMalloc((void **)&c->wire_status, 16));
-	if (nmsgs > c->wire_msgs_cap) {
-		if (c->wire_msgs) {
-			HIPCHK(hipStreamSynchronize(c->stream));
-			HIPCHK(hipFree(c->wire_msgs));
-		}
-		c->wire_msgs_cap = std::max<uint32_t>(nmsgs, 1024);
-		HIPCHK(hipMalloc((void **)&c->wire_msgs, (uint64_t)c->wire_msgs_cap * sizeof(WireMsg)));
-	}
-	return GYS_OK;
+	int rc = c->wire_status.p ? GYS_OK : c->wire_status.alloc(4, false);
+	if (!rc && nmsgs > c->wire_msgs.cap) rc = c->wire_msgs.grow(std::max<uint32_t>(nmsgs, 1024), c->stream);
+	return rc;
 }
 
 // d_buf: device copy of the stream (8-byte aligned); msgs: accepted messages of ONE record kind, sorted by position; fills
@@ -3525,13 +3353,13 @@ static hipError_t enqueue_finish(gys_ctx *c, hipStream_t st)
 	if (((uintptr_t)c->arena & 15u) == 0) { // (a caller's reduce_arena is torch / hipMalloc memory: always; the plain sequence below otherwise)
 		WinFinishP p{};
 		p.arena = (uint4 *)c->arena;
-		p.last = (uint4 *)c->last;
+		p.last = (uint4 *)c->last.p;
 		p.n16 = c->al.total / 16;
 		p.i64max_at = c->al.off_i64max;
-		p.hll32 = (uint4 *)c->hll32;
+		p.hll32 = (uint4 *)c->hll32.p;
 		p.hll16 = ((uint64_t)4 << GYS_HLL_P) / 16;
-		p.hs_win = (uint4 *)c->host_summ_win;
-		p.hs_last = (uint4 *)c->host_summ_last;
+		p.hs_win = (uint4 *)c->host_summ_win.p;
+		p.hs_last = (uint4 *)c->host_summ_last.p;
 		p.hs16 = hb / 16;
 		p.d_epoch = c->d_epoch; // the device copy of the window number follows the host's
 		hipLaunchKernelGGL(k_window_finish, dim3(grid_for(std::max<uint64_t>(p.n16, p.hs16), 256, (uint32_t)c->ncu * 4)), dim3(256), 0, st, p);
@@ -4118,8 +3946,9 @@ try {
 	if (!c || !q || !d_out || nq == 0 || nq > 16) return GYS_ERR_INVAL;
 	TDIGEST_CHECK();
 	if (!c->nsvc) return GYS_OK;
-	double *d_q = nullptr;
-	HIPCHK(hipMalloc((void **)&d_q, sizeof(double) * nq));
+	DevBuf<double> d_q;
+	int rc = d_q.alloc(nq, false);
+	if (rc) return rc;
 	HIPCHK(hipMemcpyAsync(d_q, q, sizeof(double) * nq, hipMemcpyHostToDevice, c->stream));
 	HIPCHK(hipMemsetAsync(c->merge_count + FIN_SLOW, 0, 4, c->stream));
 	MergeBP bp{};
@@ -4139,7 +3968,6 @@ try {
 	uint32_t nslow = 0;
 	HIPCHK(hipMemcpyAsync(&nslow, c->merge_count + FIN_SLOW, 4, hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(hipStreamSynchronize(c->stream));
-	HIPCHK(hipFree(d_q));
 	if (nslow) { // services whose digest weighs 2^31 or more (64-bit weights) or whose buffer holds more than GYS_MB_BIG_CAP values of a second or longer: one at a time through the general merge
 		std::vector<MergeEnt> slow(nslow);
 		HIPCHK(hipMemcpy(slow.data(), c->merge_list_slow, sizeof(MergeEnt) * nslow, hipMemcpyDeviceToHost));
@@ -4626,14 +4454,15 @@ try {
 		const int rcf = fold_range(c, first_slot, nslots);
 		if (rcf) return rcf;
 	}
-	gys_hist_rec *tmp = nullptr; // window / all-time VIEW of the records (hist_view in gys_kernels.hpp)
-	HIPCHK(hipMalloc((void **)&tmp, (size_t)nslots * sizeof(gys_hist_rec)));
+	DevBuf<gys_hist_rec> tmp; // window / all-time VIEW of the records (hist_view in gys_kernels.hpp)
+	{
+		const int rct = tmp.alloc(nslots, false);
+		if (rct) return rct;
+	}
 	hipLaunchKernelGGL(k_hist_view, dim3((nslots + 255) / 256), dim3(256), 0, c->stream, window_records(c), c->hist_all,
 			   c->cfg.enable_tdigest ? c->td_meta : nullptr, c->epoch, which, first_slot, nslots, tmp);
-	hipError_t e = hipMemcpyAsync(out, tmp, (size_t)nslots * sizeof(gys_hist_rec), hipMemcpyDeviceToHost, c->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-	hipFree(tmp);
-	HIPCHK(e);
+	HIPCHK(hipMemcpyAsync(out, tmp, (size_t)nslots * sizeof(gys_hist_rec), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
 	return GYS_OK;
 } GYS_CATCH_ALL
 
@@ -4946,30 +4775,19 @@ try {
 	RANGE_CHECK(first_slot, nslots);
 	LEVELS_CHECK();
 	if (!nslots) return GYS_OK;
-	gys_hist_rec *lv = nullptr;
-	gys_listener_day_stats *d_out = nullptr;
-	HIPCHK(hipMalloc((void **)&lv, (size_t)nslots * sizeof(gys_hist_rec)));
-	hipError_t e = hipMalloc((void **)&d_out, (size_t)nslots * sizeof(gys_listener_day_stats));
-	if (e != hipSuccess) {
-		hipFree(lv);
-		HIPCHK(e);
-	}
-	int rc = level_view(c, 2, tusec, first_slot, nslots, lv);
-	if (rc == GYS_OK) {
-		ProfScope ps(c, "day_stats");
-		hipLaunchKernelGGL(k_day_stats, dim3((nslots + 255) / 256), dim3(256), 0, c->stream, lv, c->qps_hist, c->act_hist, c->svc_gid, first_slot, nslots,
-				   d_out);
-		e = hipGetLastError();
-		if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)nslots * sizeof(gys_listener_day_stats), hipMemcpyDeviceToHost, c->stream);
-		if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-		if (e != hipSuccess) {
-			set_err("day stats: %s", hipGetErrorString(e));
-			rc = GYS_ERR_HIP;
-		}
-	}
-	hipFree(lv);
-	hipFree(d_out);
-	return rc;
+	DevBuf<gys_hist_rec> lv;
+	DevBuf<gys_listener_day_stats> d_out;
+	int rc = lv.alloc(nslots, false);
+	if (!rc) rc = d_out.alloc(nslots, false);
+	if (!rc) rc = level_view(c, 2, tusec, first_slot, nslots, lv);
+	if (rc) return rc;
+	ProfScope ps(c, "day_stats");
+	hipLaunchKernelGGL(k_day_stats, dim3((nslots + 255) / 256), dim3(256), 0, c->stream, lv, c->qps_hist, c->act_hist, c->svc_gid, first_slot, nslots,
+			   d_out);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(out, d_out, (size_t)nslots * sizeof(gys_listener_day_stats), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	return GYS_OK;
 } GYS_CATCH_ALL
 
 int gys_scan_listener_state_dev(gys_ctx *c, uint64_t tusec, float qps_multiple, uint32_t diffsec, void *d_notify, gys_listener_scan *d_scan)
@@ -5011,9 +4829,14 @@ try {
 	GYS_ENTER(c);
 	if (!c || !d_scan) return GYS_ERR_INVAL;
 	if (!c->nsvc) return GYS_OK;
-	if (!c->svc_bithist) { // the listeners' two history bytes: engine state from the first decision on
-		HIPCHK(hipMalloc((void **)&c->svc_bithist, (size_t)c->cfg.max_services * 2));
-		HIPCHK(hipMemsetAsync(c->svc_bithist, 0, (size_t)c->cfg.max_services * 2, c->stream));
+	if (!c->svc_bithist.p) { // the listeners' two history bytes: engine state from the first decision on
+		const int rc = c->svc_bithist.alloc((size_t)c->cfg.max_services * 2, false);
+		if (rc) return rc;
+		const hipError_t e = hipMemsetAsync(c->svc_bithist, 0, (size_t)c->cfg.max_services * 2, c->stream);
+		if (e != hipSuccess) {
+			c->svc_bithist.release(); // (an array that was not cleared must not pass for the history)
+			HIPCHK(e);
+		}
 	}
 	ListenerDecideP p{};
 	p.scan = d_scan;
@@ -5172,12 +4995,10 @@ try {
 			cdf[k] = (float)run;
 		}
 		cdf[svcs_per_host - 1] = 1.0f;
-		if (c->zipf_cdf) {
-			HIPCHK(hipStreamSynchronize(c->stream));
-			HIPCHK(hipFree(c->zipf_cdf));
-			c->zipf_cdf = nullptr;
-		}
-		HIPCHK(hipMalloc((void **)&c->zipf_cdf, (size_t)svcs_per_host * 4));
+		c->zipf_n = 0; // (no table until the new one has landed)
+		if (c->zipf_cdf.p) HIPCHK(hipStreamSynchronize(c->stream)); // a generator launch in flight reads the old table
+		const int rc = c->zipf_cdf.grow(svcs_per_host, c->stream);
+		if (rc) return rc;
 		HIPCHK(hipMemcpy(c->zipf_cdf, cdf.data(), (size_t)svcs_per_host * 4, hipMemcpyHostToDevice));
 		c->zipf_n = svcs_per_host;
 		c->zipf_milli = zipf_milli;

@@ -24,11 +24,11 @@ try {
 		}
 		slots[i] = it->second;
 	}
-	if (!c->svc_label) {
-		HIPCHK(hipMalloc((void **)&c->svc_label, std::max<size_t>(c->cfg.max_services, 1) * 4));
-		if (hipMemsetAsync(c->svc_label, 0xFF, std::max<size_t>(c->cfg.max_services, 1) * 4, c->stream) != hipSuccess) {
-			hipFree(c->svc_label);
-			c->svc_label = nullptr;
+	if (!c->svc_label.p) {
+		const int rc = c->svc_label.alloc(c->cfg.max_services, false);
+		if (rc) return rc;
+		if (hipMemsetAsync(c->svc_label, 0xFF, c->svc_label.cap * 4, c->stream) != hipSuccess) {
+			c->svc_label.release();
 			set_err("gys_set_service_groups: could not clear the label array");
 			return GYS_ERR_HIP;
 		}
