@@ -237,6 +237,12 @@ SIGNATURES = {
     "gys_rollup_filtered_dev": (C.c_int, [vp, C.POINTER(SvcFilter), C.c_uint32, C.c_int, C.c_int, C.c_uint64, C.POINTER(RollupRow), C.c_uint32, u32p, vp, vp, vp]),
     "gys_hist_rollup_level_dev": (C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, vp]),
     "gys_hist_rollup_filtered_dev": (C.c_int, [vp, C.POINTER(SvcFilter), C.c_uint32, C.c_int, C.c_int, C.c_uint64, C.POINTER(RollupRow), C.c_uint32, u32p, vp]),
+    "gys_hist_rollup_period_dev": (C.c_int, [vp, C.c_int, C.c_int64, C.c_int64, C.c_uint64, vp, C.POINTER(C.c_int)]),
+    "gys_hist_rollup_period_filtered_dev": (C.c_int, [vp, C.POINTER(SvcFilter), C.c_uint32, C.c_int, C.c_int64, C.c_int64, C.c_uint64, C.POINTER(RollupRow), C.c_uint32, u32p, vp, C.POINTER(C.c_int)]),
+    "gys_svc_hist_rollup_dev": (C.c_int, [vp, C.c_int, C.c_int, vp]),
+    "gys_svc_hist_rollup_filtered_dev": (C.c_int, [vp, C.POINTER(SvcFilter), C.c_uint32, C.c_int, C.c_int, C.POINTER(RollupRow), C.c_uint32, u32p, vp]),
+    "gys_day_stats_rollup_dev": (C.c_int, [vp, C.c_int, C.c_uint64, vp]),
+    "gys_day_stats_rollup_filtered_dev": (C.c_int, [vp, C.POINTER(SvcFilter), C.c_uint32, C.c_int, C.c_uint64, C.POINTER(RollupRow), C.c_uint32, u32p, vp]),
     "gys_svc_aggr_value": (C.c_int, [C.POINTER(SvcAggrRow), C.c_uint32, C.c_int, f64p]),
     "gys_query_svcstate_percentiles": (C.c_int, [vp, C.POINTER(SvcFilter), C.c_int, f64p, C.c_uint32, i64p, u64p]),
     "gys_svc_ids_by_name": (C.c_int, [vp, C.c_int, C.POINTER(C.c_char_p), C.c_uint32, u64p, C.c_uint32, u32p]),

@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <map>
 #include <memory>
 #include <set>
@@ -1580,24 +1581,19 @@ int level_view(gys_ctx *c, int level, uint64_t tusec, uint32_t first, uint32_t n
 	return GYS_OK;
 }
 
-// TIME_HISTOGRAM::get_stats_for_period_with_flush (common/gy_statistics.h:1378-1413) for slots [first, first + n): the interval's
-// {count, sum} per histogram bucket into d_out.  start / end are the reference's starttime / endtime + 1 (:1383).
-int level_period(gys_ctx *c, int64_t start, int64_t end, uint64_t tusec, uint32_t first, uint32_t n, gys_hist_rec *d_out, int *plevel)
+// The plan of TIME_HISTOGRAM::get_stats_for_period_with_flush (common/gy_statistics.h:1378-1413) at tusec: the level that answers, its
+// overlapping ring buckets with their scales and boundary snapshots, and the sources of the records -- everything that is the same for every
+// service (first / n / out stay the caller's).  start / end are the reference's starttime / endtime + 1 (:1383).  Shared by level_period and
+// the group records of a period (gys_rollup_host.hpp); the caller folds the services it reads first (fold_range).
+void period_plan(gys_ctx *c, int64_t start, int64_t end, uint64_t tusec, LevelPeriodP &p, int *plevel)
 {
 	int64_t tq = (int64_t)(tusec / 1000000ull);
 	if (tq < c->lvl_t_last) tq = c->lvl_t_last; // the flush: latestTime_ of every level
-	{
-		const int rcf = fold_range(c, first, n);
-		if (rcf) return rcf;
-	}
-	LevelPeriodP p{};
+	p = LevelPeriodP{};
 	p.win = c->hist_win;
 	p.all = c->hist_all;
 	p.meta = c->cfg.enable_tdigest ? c->td_meta : nullptr;
 	p.epoch_open = c->epoch + (c->prepared ? 1u : 0u);
-	p.first = first;
-	p.n = n;
-	p.out = d_out;
 	int level = GYS_NLEVELS - 1; // MultiLevelTimeSeries::getLevel(start): the first level that reaches back to start
 	for (int l = c->cfg.enable_levels == 1 ? 0 : 1; l < GYS_NLEVELS - 1; ++l) // (enable_levels = 2: no 5-s level, the 300-s ring answers)
 		if (tq - LEVEL_SECS[l] <= start) {
@@ -1646,6 +1642,20 @@ int level_period(gys_ctx *c, int64_t start, int64_t end, uint64_t tusec, uint32_
 		}
 		if (!p.nrb) p.mode = 1;
 	}
+}
+
+// the interval's {count, sum} per histogram bucket for slots [first, first + n) into d_out
+int level_period(gys_ctx *c, int64_t start, int64_t end, uint64_t tusec, uint32_t first, uint32_t n, gys_hist_rec *d_out, int *plevel)
+{
+	{
+		const int rcf = fold_range(c, first, n);
+		if (rcf) return rcf;
+	}
+	LevelPeriodP p;
+	period_plan(c, start, end, tusec, p, plevel);
+	p.first = first;
+	p.n = n;
+	p.out = d_out;
 	hipLaunchKernelGGL(k_level_period, dim3((uint32_t)(((uint64_t)n * 16 + 255) / 256)), dim3(256), 0, c->stream, p);
 	HIPCHK(hipGetLastError());
 	return GYS_OK;

@@ -101,4 +101,78 @@ __global__ __launch_bounds__(GYS_HR_NT) void k_hist_level_union(HistUnionP q)
 	}
 }
 
+// ---------------------------------------------------------------------------------------------------- group records of a PERIOD
+// The record of a group for the seconds [start, end) (gys_hist_rollup_period_dev): the sum of the members' records as k_level_period stores
+// them.  A partly covered ring bucket is scaled in float and truncated per member and per ring bucket BEFORE anything is added (range_adjust),
+// so the group record is not a function of the group's level records: the members are walked here, by the one period rule period_pair_load /
+// period_pair_value (gys_kernels.hpp).  Shape, join and determinism are those of k_hist_level_union above: 16 lane groups of 16, lane k owns pair
+// k, one workgroup per RollupChunk (grid-stride), the 4 KB LDS join, no atomics, no __shfl, no pre-zeroed output.  Pair 15's .x (total_count)
+// costs nothing in the member loop: period_pair_value brings 0 there, and after the join it is the sum of the 15 joined counts -- the sum over
+// the members of their totals, mod 2^64 the same value -- read back by thread 15 from the 15 joined pairs through LDS.
+// The mode, nrb, whole_mask, the scales and the boundary pointers are kernel arguments: every branch on them is wave-uniform, and the
+// boundary walk is unrolled under those scalar guards (no register array is indexed at run time).  All loads of GYS_HP_INFLIGHT members are
+// requested before the first is used; in mode 0 a member asks for up to 13 sixteen-byte loads per lane (11 boundaries, cumulative, window).
+// MEMBERS IN FLIGHT, from the register counts of the gfx950 code object (hipcc -O3; .vgpr_count of the kernel's metadata; the ~50 SGPRs of plan
+// that do not fit the 102 are kept in VGPR lanes, no scratch either way): GYS_HP_INFLIGHT = 1 -> 78 VGPRs (allocated 80), 6 waves / SIMD;
+// GYS_HP_INFLIGHT = 2 -> 134 VGPRs (allocated 136), 3 waves / SIMD.  Either way a SIMD has the same 6 x 13 = 3 x 26 = 78 sixteen-byte loads in
+// flight in mode 0 (registers are allocated for the 11 boundaries whatever nrb is), so one member per lane group is kept: twice the waves to
+// cover the dependent member index -> TdMeta -> window-record loads, half the live state.  (Two in flight would pay below 128 VGPRs, 4 waves.)
+// Bytes per member service: 4 (member index) + 16 (TdMeta, lazily folded records) + 256 x (boundaries + cumulative [+ window, a member whose
+// open window is partly folded]); modes 1 and 2 read pair 15 of the cumulative record only, mode 2 the last-window record, mode 3 first_sec.
+#define GYS_HP_INFLIGHT 1u // members per lane group whose loads are requested together (see above)
+
+struct HistPeriodUnionP {
+	LevelPeriodP v;            // the period's sources and plan (first / n / out are not used)
+	gys_hist_rec *dst;         // one record per CHUNK: dst[chunk index]
+	const RollupChunk *chunks;
+	const uint32_t *members;   // service slot of a member
+	uint32_t nchunks;
+};
+
+__global__ __launch_bounds__(GYS_HR_NT) void k_hist_period_union(HistPeriodUnionP q)
+{
+	__shared__ ulonglong2 red[GYS_HR_NT]; // 4 KB
+	const uint32_t t = threadIdx.x, k = t & 15u, row = t >> 4;
+	constexpr uint32_t rows = GYS_HR_NT / 16u;
+	ulonglong2 ident;
+	ident.x = 0ull;
+	ident.y = k < 15u ? 0ull : (unsigned long long)INT64_MIN;
+	for (uint32_t ch = blockIdx.x; ch < q.nchunks; ch += gridDim.x) {
+		const uint32_t m0 = q.chunks[ch].m0, m1 = q.chunks[ch].m1;
+		ulonglong2 acc = ident;
+		uint32_t j = m0 + row;
+		for (; j < m1 && m1 - j > (GYS_HP_INFLIGHT - 1u) * rows; j += GYS_HP_INFLIGHT * rows) { // the members' indices, then every load of theirs, then the adds
+			uint32_t s[GYS_HP_INFLIGHT];
+#pragma unroll
+			for (uint32_t i = 0; i < GYS_HP_INFLIGHT; ++i) s[i] = q.members[j + i * rows];
+			PeriodPair in[GYS_HP_INFLIGHT];
+#pragma unroll
+			for (uint32_t i = 0; i < GYS_HP_INFLIGHT; ++i) in[i] = period_pair_load<true>(q.v, s[i], k);
+#pragma unroll
+			for (uint32_t i = 0; i < GYS_HP_INFLIGHT; ++i) acc = pair_add(acc, period_pair_value(q.v, in[i], k), k);
+		}
+		for (; j < m1; j += rows) {
+			const PeriodPair in = period_pair_load<true>(q.v, q.members[j], k);
+			acc = pair_add(acc, period_pair_value(q.v, in, k), k);
+		}
+		red[t] = acc;
+		__syncthreads();
+		ulonglong2 r = ident;
+		if (t < 16u) {
+			r = red[t];
+#pragma unroll
+			for (uint32_t g = 1; g < rows; ++g) r = pair_add(r, red[g * 16u + t], k);
+		}
+		__syncthreads(); // (every column is read: red takes the joined pairs)
+		if (t < 15u) red[t] = r;
+		__syncthreads();
+		if (t == 15u) { // total_count = the sum of the 15 joined counts
+#pragma unroll
+			for (uint32_t b = 0; b < 15u; ++b) r.x += red[b].x;
+		}
+		if (t < 16u) ((ulonglong2 *)q.dst)[(uint64_t)ch * 16ull + t] = r;
+		__syncthreads(); // (red is written again in the next turn)
+	}
+}
+
 } // namespace gys

@@ -3931,47 +3931,87 @@ struct LevelPeriodP {
 
 __device__ __forceinline__ long long range_adjust(long long v, float scale) { return (long long)((float)v * scale); }
 
-__global__ __launch_bounds__(256) void k_level_period(LevelPeriodP p)
+// THE period rule for pair k of service `slot`, in two halves like level_pair_load / level_pair_value above (k_level_period stores from them,
+// k_hist_period_union, gys_histroll.hpp, adds them up): period_pair_load issues every load of the pair, period_pair_value is pure arithmetic.
+// The boundaries are walked by loops unrolled to GYS_PERIOD_MAXB + 1 whose guards (nrb, bnd[i], whole_mask) are kernel arguments, the same in
+// every lane: b[] is only ever indexed by constants and stays in registers.  SPARSE = false loads what k_level_period always loaded; SPARSE =
+// true leaves out the loads whose value the rule does not look at (the window record of a service whose open window holds nothing folded, the
+// cumulative pairs 0..14 of modes 1 and 2).
+struct PeriodPair {
+	ulonglong2 cum, w;
+	ulonglong2 b[GYS_PERIOD_MAXB + 1]; // mode 0: the boundary records; mode 2: b[0] = the last-window record
+	uint32_t hw, tag;
+	int64_t first; // mode 3
+};
+
+template <bool SPARSE>
+__device__ __forceinline__ PeriodPair period_pair_load(const LevelPeriodP &p, uint32_t slot, uint32_t k)
 {
-	const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	const bool live = t < (uint64_t)p.n * 16ull;
-	const uint64_t tt = live ? t : 0; // every lane stays for the 16-lane sums below
-	const uint32_t slot = p.first + (uint32_t)(tt >> 4), k = (uint32_t)(tt & 15u);
 	const uint64_t g = (uint64_t)slot * 16ull + k;
-	ulonglong2 cum = ((const ulonglong2 *)p.all)[g];
-	const ulonglong2 w = ((const ulonglong2 *)p.win)[g];
-	if (p.meta) {
-		if (p.meta[slot].hw_epoch == p.epoch_open) { // the folded part of the OPEN window is not in any level yet
-			cum.x -= w.x;
-			if (k < 15u) cum.y -= w.y;
+	PeriodPair in;
+	in.cum = in.w = ulonglong2{0ull, 0ull};
+#pragma unroll
+	for (uint32_t i = 0; i <= GYS_PERIOD_MAXB; ++i) in.b[i] = ulonglong2{0ull, 0ull};
+	in.hw = p.epoch_open + 1u; // (not the open epoch)
+	in.tag = p.last_epoch;
+	in.first = 0;
+	const bool body = p.mode == 0 || p.mode == 3; // the cumulative pairs 0..14 are looked at
+	if (!SPARSE || body || k == 15u) in.cum = ((const ulonglong2 *)p.all)[g];
+	if (p.meta && (!SPARSE || body)) in.hw = p.meta[slot].hw_epoch;
+	if (!SPARSE || (p.meta ? in.hw == p.epoch_open : k == 15u)) in.w = ((const ulonglong2 *)p.win)[g];
+	if (k < 15u) {
+		if (p.mode == 0) {
+#pragma unroll
+			for (uint32_t i = 0; i <= GYS_PERIOD_MAXB; ++i)
+				if (i <= p.nrb && p.bnd[i]) in.b[i] = ((const ulonglong2 *)p.bnd[i])[g];
+		} else if (p.mode == 2) {
+			if (p.last_tag) in.tag = p.last_tag[slot];
+			if (in.tag == p.last_epoch) in.b[0] = ((const ulonglong2 *)p.last)[g];
+		} else if (p.mode == 3) {
+			in.first = p.first_sec[slot];
 		}
-	} else if (k == 15u && (long long)cum.y < (long long)w.y) {
-		cum.y = w.y;
+	}
+	return in;
+}
+
+// pairs 0..14: the interval's {count, sum}; pair 15: {0, the all-time maximum} -- its .x, the sum of the 15 counts, is the caller's
+__device__ __forceinline__ ulonglong2 period_pair_value(const LevelPeriodP &p, const PeriodPair &in, uint32_t k)
+{
+	ulonglong2 cum = in.cum;
+	if (p.meta) {
+		if (in.hw == p.epoch_open) { // the folded part of the OPEN window is not in any level yet
+			cum.x -= in.w.x;
+			if (k < 15u) cum.y -= in.w.y;
+		}
+	} else if (k == 15u && (long long)cum.y < (long long)in.w.y) {
+		cum.y = in.w.y;
 	}
 	long long ac = 0, as = 0;
 	if (k < 15u) {
 		if (p.mode == 0) {
-			ulonglong2 lo = p.bnd[0] ? ((const ulonglong2 *)p.bnd[0])[g] : cum;
-			for (uint32_t i = 0; i < p.nrb; ++i) {
-				const ulonglong2 hi = p.bnd[i + 1] ? ((const ulonglong2 *)p.bnd[i + 1])[g] : cum;
-				const long long c = (long long)(hi.x - lo.x), sm = (long long)(hi.y - lo.y);
-				if ((p.whole_mask >> i) & 1u) {
-					ac += c;
-					as += sm;
-				} else {
-					ac += range_adjust(c, p.scale[i]);
-					as += range_adjust(sm, p.scale[i]);
+			ulonglong2 lo = p.bnd[0] ? in.b[0] : cum;
+#pragma unroll
+			for (uint32_t i = 0; i < GYS_PERIOD_MAXB; ++i) {
+				if (i < p.nrb) {
+					const ulonglong2 hi = p.bnd[i + 1] ? in.b[i + 1] : cum;
+					const long long c = (long long)(hi.x - lo.x), sm = (long long)(hi.y - lo.y);
+					if ((p.whole_mask >> i) & 1u) {
+						ac += c;
+						as += sm;
+					} else {
+						ac += range_adjust(c, p.scale[i]);
+						as += range_adjust(sm, p.scale[i]);
+					}
+					lo = hi;
 				}
-				lo = hi;
 			}
 		} else if (p.mode == 2) {
-			if (!p.last_tag || p.last_tag[slot] == p.last_epoch) {
-				const ulonglong2 r = ((const ulonglong2 *)p.last)[g];
-				ac = (long long)r.x;
-				as = (long long)r.y;
+			if (in.tag == p.last_epoch) {
+				ac = (long long)in.b[0].x;
+				as = (long long)in.b[0].y;
 			}
 		} else if (p.mode == 3) {
-			const int64_t bs = p.first_sec[slot];
+			const int64_t bs = in.first;
 			int64_t bn = p.latest + 1;
 			if (bs != 0 && !(p.start >= bn) && !(p.end <= bs)) {
 				if (p.start <= bs && p.end >= bn) {
@@ -3986,31 +4026,39 @@ __global__ __launch_bounds__(256) void k_level_period(LevelPeriodP p)
 			}
 		}
 	}
-	long long tot = ac;
-	for (int o = 1; o < 16; o <<= 1) tot += __shfl_xor(tot, o, 16);
-	if (!live) return;
 	ulonglong2 r;
 	if (k < 15u) {
 		r.x = (unsigned long long)ac;
 		r.y = (unsigned long long)as;
 	} else {
-		r.x = (unsigned long long)tot;
+		r.x = 0ull;
 		r.y = cum.y;
 	}
+	return r;
+}
+
+__global__ __launch_bounds__(256) void k_level_period(LevelPeriodP p)
+{
+	const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	const bool live = t < (uint64_t)p.n * 16ull;
+	const uint64_t tt = live ? t : 0; // every lane stays for the 16-lane sums below
+	const uint32_t slot = p.first + (uint32_t)(tt >> 4), k = (uint32_t)(tt & 15u);
+	const PeriodPair in = period_pair_load<false>(p, slot, k);
+	ulonglong2 r = period_pair_value(p, in, k);
+	long long tot = (long long)r.x; // (pair 15 brings 0)
+	for (int o = 1; o < 16; o <<= 1) tot += __shfl_xor(tot, o, 16);
+	if (!live) return;
+	if (k == 15u) r.x = (unsigned long long)tot;
 	((ulonglong2 *)p.out)[t] = r;
 }
 
 // comm::LISTENER_DAY_STATS (common/gy_comm_proto.h:1620-1632) the way TCP_LISTENER::get_curr_state fills it
 // (common/gy_socket_stat.cc:2053-2112): 5-day level count / sum / p95 / p25 of the response histogram (TIME_HISTOGRAM::get_stats),
 // p95 / p25 of the QPS and active-connection histograms (GY_HISTOGRAM::get_percentiles, HIST_DATA {95, 25}).
-__global__ __launch_bounds__(256) void k_day_stats(const gys_hist_rec *lvl5d, const gys_hist_rec *qps, const gys_hist_rec *act, const uint64_t *svc_gid,
-						   uint32_t first, uint32_t n, gys_listener_day_stats *out)
+__device__ __forceinline__ gys_listener_day_stats day_stats_of(uint64_t glob_id, const gys_hist_rec &r, const gys_hist_rec &q, const gys_hist_rec &a)
 {
-	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n) return;
-	const gys_hist_rec r = lvl5d[i];
 	gys_listener_day_stats o;
-	o.glob_id = svc_gid[first + i];
+	o.glob_id = glob_id;
 	int64_t ts = 0;
 	for (int b = 0; b < 15; ++b) ts += r.stats[b].sum;
 	o.tcount_5d = (int64_t)r.total_count;
@@ -4020,17 +4068,43 @@ __global__ __launch_bounds__(256) void k_day_stats(const gys_hist_rec *lvl5d, co
 	o.p25_5d_respms = (uint32_t)level_percentile(dr, r, 25.0f);
 	int64_t dv, sum;
 	uint64_t cnt;
-	const gys_hist_rec q = qps[first + i];
 	hist_percentile(hash_def(GYS_SEMI_LOG_HASH_LO), q, 95.0f, &dv, &sum, &cnt);
 	o.p95_qps = (uint32_t)dv;
 	hist_percentile(hash_def(GYS_SEMI_LOG_HASH_LO), q, 25.0f, &dv, &sum, &cnt);
 	o.p25_qps = (uint32_t)dv;
-	const gys_hist_rec a = act[first + i];
 	hist_percentile(hash_def(GYS_HASH_1_3000), a, 95.0f, &dv, &sum, &cnt);
 	o.p95_nactive = (uint32_t)dv;
 	hist_percentile(hash_def(GYS_HASH_1_3000), a, 25.0f, &dv, &sum, &cnt);
 	o.p25_nactive = (uint32_t)dv;
-	out[i] = o;
+	return o;
+}
+
+__global__ __launch_bounds__(256) void k_day_stats(const gys_hist_rec *lvl5d, const gys_hist_rec *qps, const gys_hist_rec *act, const uint64_t *svc_gid,
+						   uint32_t first, uint32_t n, gys_listener_day_stats *out)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	out[i] = day_stats_of(svc_gid[first + i], lvl5d[i], qps[first + i], act[first + i]);
+}
+
+// the same rule on the records of GROUPS (gys_day_stats_rollup_dev): group i's 5-day response record, QPS record and active-connection record;
+// glob_id = the group index -- i, or the group of row i of a filtered selection.  A group WITHOUT members has zero statistics (the rule on empty
+// records would report the lowest bucket's threshold): it is the group whose QPS record still carries max_val_seen = INT64_MIN, the record of
+// no member -- a member that never reported brings the INT32_MIN gys_create leaves.
+__global__ __launch_bounds__(256) void k_day_stats_groups(const gys_hist_rec *lvl5d, const gys_hist_rec *qps, const gys_hist_rec *act, const gys_rollup_row *rows,
+							  uint32_t n, gys_listener_day_stats *out)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const uint64_t gid = rows ? rows[i].group : i;
+	if (qps[i].max_val_seen == INT64_MIN) {
+		gys_listener_day_stats o;
+		memset(&o, 0, sizeof(o));
+		o.glob_id = gid;
+		out[i] = o;
+		return;
+	}
+	out[i] = day_stats_of(gid, lvl5d[i], qps[i], act[i]);
 }
 
 

@@ -229,12 +229,27 @@ public:
 			       : -1;
 	}
 
+	// the same question asked of every host / cluster / this madhava (scope: GYS_ROLLUP_*): the sum of the listeners' period records, one
+	// record per group on the device (percentiles through gys_hist_percentiles_dev); *level_used = the level that answered (may be nullptr)
+	bool aggr_resp_period_hist(int scope, time_t starttime, time_t endtime, gys_hist_rec *d_out, int *level_used = nullptr, time_t tnow = time(nullptr)) noexcept
+	{
+		std::unique_lock<std::shared_mutex> g(mu_); // (a query: not concurrent with ingest calls)
+		return gys_hist_rollup_period_dev(ctx_, scope, (int64_t)starttime, (int64_t)endtime, (uint64_t)tnow * 1000000ull, d_out, level_used) == GYS_OK;
+	}
+
 	// the NOTIFY_LISTENER_DAY_STATS payload (comm::LISTENER_DAY_STATS[], MAX_NUM_LISTENERS = 2048 per message) for service slots
 	// [first_slot, first_slot + nslots), as TCP_LISTENER::get_curr_state fills it (common/gy_socket_stat.cc:2098-2112)
 	bool listener_day_stats(time_t tnow, uint32_t first_slot, uint32_t nslots, gys_listener_day_stats *pout) noexcept
 	{
 		std::unique_lock<std::shared_mutex> g(mu_);
 		return gys_export_day_stats(ctx_, (uint64_t)tnow * 1000000ull, first_slot, nslots, pout) == GYS_OK;
+	}
+
+	// LISTENER_DAY_STATS of every host / cluster / this madhava (scope: GYS_ROLLUP_*), glob_id_ = the group index; records on the device
+	bool aggr_day_stats(int scope, time_t tnow, gys_listener_day_stats *d_out) noexcept
+	{
+		std::unique_lock<std::shared_mutex> g(mu_);
+		return gys_day_stats_rollup_dev(ctx_, scope, (uint64_t)tnow * 1000000ull, d_out) == GYS_OK;
 	}
 
 	// the same answers as the reference's web JSON (web_curr_listener_summ / web_curr_listener_state / web_curr_clusterstate)

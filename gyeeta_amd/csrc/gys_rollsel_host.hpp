@@ -199,11 +199,24 @@ try {
 	return GYS_OK;
 } GYS_CATCH_ALL
 
+// the argument rules the filtered group-histogram calls share
+#define HIST_FILTERED_ARGS_OK(f, rows, nrows, out, flags, group_by) \
+	((f) && (rows) && (nrows) && (out) && !((flags) & ~GYS_RF_ANY_STATE) && (group_by) >= GYS_GROUP_NONE && (group_by) <= GYS_GROUP_LABEL)
+
+// the members' records `src` of a selection (rollsel_select: nr rows, nchunks chunks) -> one record per chunk -> one per row (d_recs)
+static int hist_rollup_selected(gys_ctx *c, const HistMemberSrc &src, uint32_t nr, uint32_t nchunks, gys_hist_rec *d_recs)
+{
+	gys_hist_rec *parts = nullptr;
+	const int rc = hist_union_scratch(c, nchunks, 0, &parts, nullptr);
+	if (rc) return rc;
+	return hist_union_rows(c, src, c->rs_chunks.p, nchunks, c->rs_members.p, c->rs_gchunks.p, nr, parts, d_recs);
+}
+
 int gys_hist_rollup_filtered_dev(gys_ctx *c, const gys_svc_filter *f, uint32_t flags, int group_by, int level, uint64_t tusec, gys_rollup_row *rows, uint32_t maxrows,
 				 uint32_t *nrows, gys_hist_rec *d_recs)
 try {
 	GYS_ENTER(c);
-	if (!c || !f || !rows || !nrows || !d_recs || (flags & ~GYS_RF_ANY_STATE) || group_by < GYS_GROUP_NONE || group_by > GYS_GROUP_LABEL || level < 0 || level >= GYS_NLEVELS) {
+	if (!c || !HIST_FILTERED_ARGS_OK(f, rows, nrows, d_recs, flags, group_by) || level < 0 || level >= GYS_NLEVELS) {
 		set_err("gys_hist_rollup_filtered_dev: null filter / rows / nrows / d_recs, unknown flags or group_by, or a level outside 0 .. %d", GYS_NLEVELS - 1);
 		return GYS_ERR_INVAL;
 	}
@@ -211,12 +224,62 @@ try {
 	LEVELS_CHECK();
 	LEVEL0_CHECK(level);
 	uint32_t nr, nchunks;
-	int rc = rollsel_select(c, f, flags, group_by, rows, maxrows, nrows, &nr, &nchunks);
+	const int rc = rollsel_select(c, f, flags, group_by, rows, maxrows, nrows, &nr, &nchunks);
 	if (rc != GYS_OK || !nr) return rc;
-	gys_hist_rec *parts = nullptr;
-	if ((rc = hist_union_scratch(c, nchunks, 0, &parts, nullptr)) != GYS_OK) return rc;
-	// the members' level records -> one record per chunk -> one per row
-	return hist_union_rows(c, level, tusec, c->rs_chunks.p, nchunks, c->rs_members.p, c->rs_gchunks.p, nr, parts, d_recs);
+	return hist_rollup_selected(c, hist_src_level(level, tusec), nr, nchunks, d_recs);
+} GYS_CATCH_ALL
+
+int gys_hist_rollup_period_filtered_dev(gys_ctx *c, const gys_svc_filter *f, uint32_t flags, int group_by, int64_t starttime, int64_t endtime, uint64_t tusec,
+					gys_rollup_row *rows, uint32_t maxrows, uint32_t *nrows, gys_hist_rec *d_recs, int *level_used)
+try {
+	GYS_ENTER(c);
+	if (!c || !HIST_FILTERED_ARGS_OK(f, rows, nrows, d_recs, flags, group_by)) {
+		set_err("gys_hist_rollup_period_filtered_dev: null filter / rows / nrows / d_recs, unknown flags or group_by");
+		return GYS_ERR_INVAL;
+	}
+	*nrows = 0;
+	LEVELS_CHECK();
+	LevelPeriodP plan;
+	period_plan(c, starttime, endtime + 1, tusec, plan, level_used);
+	uint32_t nr, nchunks;
+	const int rc = rollsel_select(c, f, flags, group_by, rows, maxrows, nrows, &nr, &nchunks);
+	if (rc != GYS_OK || !nr) return rc;
+	return hist_rollup_selected(c, hist_src_period(&plan), nr, nchunks, d_recs);
+} GYS_CATCH_ALL
+
+int gys_svc_hist_rollup_filtered_dev(gys_ctx *c, const gys_svc_filter *f, uint32_t flags, int group_by, int which, gys_rollup_row *rows, uint32_t maxrows, uint32_t *nrows,
+				     gys_hist_rec *d_recs)
+try {
+	GYS_ENTER(c);
+	if (!c || !HIST_FILTERED_ARGS_OK(f, rows, nrows, d_recs, flags, group_by) || which < 0 || which > 1) {
+		set_err("gys_svc_hist_rollup_filtered_dev: null filter / rows / nrows / d_recs, unknown flags or group_by, or which outside 0 .. 1");
+		return GYS_ERR_INVAL;
+	}
+	*nrows = 0;
+	LEVELS_CHECK();
+	uint32_t nr, nchunks;
+	const int rc = rollsel_select(c, f, flags, group_by, rows, maxrows, nrows, &nr, &nchunks);
+	if (rc != GYS_OK || !nr) return rc;
+	return hist_rollup_selected(c, hist_src_plain(which ? c->act_hist : c->qps_hist), nr, nchunks, d_recs);
+} GYS_CATCH_ALL
+
+int gys_day_stats_rollup_filtered_dev(gys_ctx *c, const gys_svc_filter *f, uint32_t flags, int group_by, uint64_t tusec, gys_rollup_row *rows, uint32_t maxrows,
+				      uint32_t *nrows, gys_listener_day_stats *d_out)
+try {
+	GYS_ENTER(c);
+	if (!c || !HIST_FILTERED_ARGS_OK(f, rows, nrows, d_out, flags, group_by)) {
+		set_err("gys_day_stats_rollup_filtered_dev: null filter / rows / nrows / d_out, unknown flags or group_by");
+		return GYS_ERR_INVAL;
+	}
+	*nrows = 0;
+	LEVELS_CHECK();
+	uint32_t nr, nchunks;
+	const int rc = rollsel_select(c, f, flags, group_by, rows, maxrows, nrows, &nr, &nchunks);
+	if (rc != GYS_OK || !nr) return rc;
+	// one selection, three families over it; glob_id = the row's group (the device's copy of the rows)
+	return day_stats_groups(c, nr, std::max<size_t>(nchunks, 1), c->rs_rows.p, d_out, [&](int fam, gys_hist_rec *recs) {
+		return hist_rollup_selected(c, fam == 0 ? hist_src_level(2, tusec) : hist_src_plain(fam == 1 ? c->qps_hist : c->act_hist), nr, nchunks, recs);
+	});
 } GYS_CATCH_ALL
 
 } // extern "C"

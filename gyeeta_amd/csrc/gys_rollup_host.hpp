@@ -238,16 +238,25 @@ static void hist_union_launch(gys_ctx *c, const HistUnionP &q)
 	if (q.nchunks) hipLaunchKernelGGL(k_hist_level_union, dim3(std::min<uint32_t>(q.nchunks, (uint32_t)c->ncu * 8)), dim3(GYS_HR_NT), 0, c->stream, q);
 }
 
-// the sources of `level` at tusec for every service, exactly as level_view() reads them: the fold of the buffered values first, then
+// where the members' records of a group histogram come from: a level at tusec, a planned period, or a per-service array as it stands
+// (the QPS / active-connection histograms).  One descriptor, so that the fixed scopes and the filtered selection share one path per family.
+struct HistMemberSrc {
+	enum Kind { LEVEL, PERIOD, PLAIN } kind;
+	int level;                 // LEVEL
+	uint64_t tusec;            // LEVEL
+	const LevelPeriodP *plan;  // PERIOD: period_plan()'s result
+	const gys_hist_rec *recs;  // PLAIN: [nsvc]
+};
+static HistMemberSrc hist_src_level(int level, uint64_t tusec) { return HistMemberSrc{HistMemberSrc::LEVEL, level, tusec, nullptr, nullptr}; }
+static HistMemberSrc hist_src_period(const LevelPeriodP *plan) { return HistMemberSrc{HistMemberSrc::PERIOD, 0, 0, plan, nullptr}; }
+static HistMemberSrc hist_src_plain(const gys_hist_rec *recs) { return HistMemberSrc{HistMemberSrc::PLAIN, 0, 0, nullptr, recs}; }
+
+// the sources of `level` at tusec for every service, exactly as level_view() reads them:
 // tq = max(tusec / 10^6, the last close) -- never the open window
-static int hist_union_level(gys_ctx *c, int level, uint64_t tusec, HistUnionP &q)
+static void hist_union_level(gys_ctx *c, int level, uint64_t tusec, HistUnionP &q)
 {
 	int64_t tq = (int64_t)(tusec / 1000000ull);
 	if (tq < c->lvl_t_last) tq = c->lvl_t_last;
-	{
-		const int rcf = fold_range(c, 0, c->nsvc);
-		if (rcf) return rcf;
-	}
 	q = HistUnionP{};
 	q.v.win = c->hist_win;
 	q.v.all = c->hist_all;
@@ -256,22 +265,40 @@ static int hist_union_level(gys_ctx *c, int level, uint64_t tusec, HistUnionP &q
 	level_source(c, level, tq, &q.v.mode, &q.v.sub);
 	q.v.last_tag = c->cfg.enable_tdigest ? c->lvl_last_tag : nullptr;
 	q.v.last_epoch = c->lvl_last_epoch;
-	return GYS_OK;
 }
 
-// the members' level records -> one record per chunk (parts) -> one per row (d_rows)
-static int hist_union_rows(gys_ctx *c, int level, uint64_t tusec, const RollupChunk *d_chunks, uint32_t nchunks, const uint32_t *d_members, const RollupChunk *d_gchunks,
+// the members' records -> one record per chunk (parts) -> one per row (d_rows).  Levels and periods: the fold of the buffered values first
+// (the members' open windows, as level_view() / level_period() fold the slots they read)
+static int hist_union_rows(gys_ctx *c, const HistMemberSrc &src, const RollupChunk *d_chunks, uint32_t nchunks, const uint32_t *d_members, const RollupChunk *d_gchunks,
 			   uint32_t nrows, gys_hist_rec *parts, gys_hist_rec *d_rows)
 {
-	HistUnionP q;
-	const int rc = hist_union_level(c, level, tusec, q);
-	if (rc) return rc;
+	if (src.kind != HistMemberSrc::PLAIN) {
+		const int rcf = fold_range(c, 0, c->nsvc);
+		if (rcf) return rcf;
+	}
 	ProfScope ps(c, "hist_rollup_union");
-	q.dst = parts;
-	q.chunks = d_chunks;
-	q.members = d_members;
-	q.nchunks = nchunks;
-	hist_union_launch(c, q);
+	if (src.kind == HistMemberSrc::PERIOD) {
+		HistPeriodUnionP q{};
+		q.v = *src.plan;
+		q.dst = parts;
+		q.chunks = d_chunks;
+		q.members = d_members;
+		q.nchunks = nchunks;
+		if (nchunks) hipLaunchKernelGGL(k_hist_period_union, dim3(std::min<uint32_t>(nchunks, (uint32_t)c->ncu * 8)), dim3(GYS_HR_NT), 0, c->stream, q);
+	} else {
+		HistUnionP q{};
+		if (src.kind == HistMemberSrc::LEVEL) {
+			hist_union_level(c, src.level, src.tusec, q);
+		} else {
+			q.plain = 1;
+			q.src = src.recs;
+		}
+		q.dst = parts;
+		q.chunks = d_chunks;
+		q.members = d_members;
+		q.nchunks = nchunks;
+		hist_union_launch(c, q);
+	}
 	HistUnionP g{};
 	g.plain = 1;
 	g.src = parts;
@@ -283,15 +310,9 @@ static int hist_union_rows(gys_ctx *c, int level, uint64_t tusec, const RollupCh
 	return GYS_OK;
 }
 
-int gys_hist_rollup_level_dev(gys_ctx *c, int scope, int level, uint64_t tusec, gys_hist_rec *d_out)
-try {
-	GYS_ENTER(c);
-	if (!c || !d_out || scope < GYS_ROLLUP_HOST || scope > GYS_ROLLUP_GLOBAL || level < 0 || level >= GYS_NLEVELS) {
-		set_err("gys_hist_rollup_level_dev: null output, an unknown scope or a level outside 0 .. %d", GYS_NLEVELS - 1);
-		return GYS_ERR_INVAL;
-	}
-	LEVELS_CHECK();
-	LEVEL0_CHECK(level);
+// one record per host slot / registered cluster / one of the members' records `src` into d_out (DEVICE): the fixed scopes of every family
+static int hist_rollup_scope(gys_ctx *c, int scope, const HistMemberSrc &src, gys_hist_rec *d_out)
+{
 	const uint32_t nh = (uint32_t)c->hosts.size();
 	uint32_t ngroups, nparts;
 	int rc = rollup_scope(c, scope, &ngroups, &nparts);
@@ -300,7 +321,7 @@ try {
 	gys_hist_rec *parts = nullptr, *hostrecs = nullptr;
 	if ((rc = hist_union_scratch(c, nparts, scope == GYS_ROLLUP_HOST ? 0 : nh, &parts, &hostrecs)) != GYS_OK) return rc;
 	if (scope == GYS_ROLLUP_HOST) hostrecs = d_out;
-	if ((rc = hist_union_rows(c, level, tusec, hg.chunks.p, hg.nchunks, hg.members.p, hg.gchunks.p, nh, parts, hostrecs)) != GYS_OK) return rc;
+	if ((rc = hist_union_rows(c, src, hg.chunks.p, hg.nchunks, hg.members.p, hg.gchunks.p, nh, parts, hostrecs)) != GYS_OK) return rc;
 	if (scope == GYS_ROLLUP_HOST) return GYS_OK;
 	ProfScope ps(c, "hist_rollup_groups"); // host records -> cluster records / the rank's record (plain)
 	HistUnionP g{};
@@ -332,6 +353,79 @@ try {
 	hist_union_launch(c, f);
 	HIPCHK(hipGetLastError());
 	return GYS_OK;
+}
+
+#define HIST_SCOPE_OK(scope) ((scope) >= GYS_ROLLUP_HOST && (scope) <= GYS_ROLLUP_GLOBAL)
+
+int gys_hist_rollup_level_dev(gys_ctx *c, int scope, int level, uint64_t tusec, gys_hist_rec *d_out)
+try {
+	GYS_ENTER(c);
+	if (!c || !d_out || !HIST_SCOPE_OK(scope) || level < 0 || level >= GYS_NLEVELS) {
+		set_err("gys_hist_rollup_level_dev: null output, an unknown scope or a level outside 0 .. %d", GYS_NLEVELS - 1);
+		return GYS_ERR_INVAL;
+	}
+	LEVELS_CHECK();
+	LEVEL0_CHECK(level);
+	return hist_rollup_scope(c, scope, hist_src_level(level, tusec), d_out);
+} GYS_CATCH_ALL
+
+// the group record of the seconds [starttime, endtime] at tusec: the plan of gys_export_hist_period once, the members through k_hist_period_union
+int gys_hist_rollup_period_dev(gys_ctx *c, int scope, int64_t starttime, int64_t endtime, uint64_t tusec, gys_hist_rec *d_out, int *level_used)
+try {
+	GYS_ENTER(c);
+	if (!c || !d_out || !HIST_SCOPE_OK(scope)) {
+		set_err("gys_hist_rollup_period_dev: null output or an unknown scope");
+		return GYS_ERR_INVAL;
+	}
+	LEVELS_CHECK();
+	LevelPeriodP plan;
+	period_plan(c, starttime, endtime + 1, tusec, plan, level_used);
+	return hist_rollup_scope(c, scope, hist_src_period(&plan), d_out);
+} GYS_CATCH_ALL
+
+int gys_svc_hist_rollup_dev(gys_ctx *c, int scope, int which, gys_hist_rec *d_out)
+try {
+	GYS_ENTER(c);
+	if (!c || !d_out || !HIST_SCOPE_OK(scope) || which < 0 || which > 1) {
+		set_err("gys_svc_hist_rollup_dev: null output, an unknown scope or which outside 0 .. 1");
+		return GYS_ERR_INVAL;
+	}
+	LEVELS_CHECK();
+	return hist_rollup_scope(c, scope, hist_src_plain(which ? c->act_hist : c->qps_hist), d_out);
+} GYS_CATCH_ALL
+
+// the day statistics of ngroups groups: their 5-day response records, QPS records and active-connection records into three record arrays of
+// the scratch buffer (behind the `used` records a roll-up itself takes), then k_day_stats' rule on them.  `one` runs one family into its array.
+static int day_stats_groups(gys_ctx *c, uint32_t ngroups, size_t used, const gys_rollup_row *d_rows, gys_listener_day_stats *d_out,
+			    const std::function<int(int, gys_hist_rec *)> &one)
+{
+	// (grown to its full size before the first pointer into it is taken: a later grow would move the records)
+	int rc = c->hr_buf.grow(used + 3ull * ngroups, c->stream);
+	if (rc) return rc;
+	for (int fam = 0; fam < 3; ++fam)
+		if ((rc = one(fam, c->hr_buf.p + used + (size_t)fam * ngroups)) != GYS_OK) return rc;
+	ProfScope ps(c, "day_stats_groups");
+	const gys_hist_rec *r = c->hr_buf.p + used;
+	hipLaunchKernelGGL(k_day_stats_groups, dim3((ngroups + 255) / 256), dim3(256), 0, c->stream, r, r + ngroups, r + 2ull * ngroups, d_rows, ngroups, d_out);
+	HIPCHK(hipGetLastError());
+	return GYS_OK;
+}
+
+int gys_day_stats_rollup_dev(gys_ctx *c, int scope, uint64_t tusec, gys_listener_day_stats *d_out)
+try {
+	GYS_ENTER(c);
+	if (!c || !d_out || !HIST_SCOPE_OK(scope)) {
+		set_err("gys_day_stats_rollup_dev: null output or an unknown scope");
+		return GYS_ERR_INVAL;
+	}
+	LEVELS_CHECK();
+	uint32_t ngroups, nparts;
+	const int rc = rollup_scope(c, scope, &ngroups, &nparts);
+	if (rc || !ngroups) return rc;
+	const size_t used = std::max<size_t>(nparts, 1) + (size_t)c->hosts.size(); // what hist_rollup_scope takes of the scratch buffer
+	return day_stats_groups(c, ngroups, used, nullptr, d_out, [&](int fam, gys_hist_rec *recs) {
+		return hist_rollup_scope(c, scope, fam == 0 ? hist_src_level(2, tusec) : hist_src_plain(fam == 1 ? c->qps_hist : c->act_hist), recs);
+	});
 } GYS_CATCH_ALL
 
 } // extern "C"

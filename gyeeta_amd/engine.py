@@ -723,6 +723,102 @@ class SketchEngine:
         res = ([(rows[i].group, rows[i].nmembers) for i in range(nr)], n.value, recs[:nr].cpu().numpy())
         return res if pcts is None else res + (self._group_percentiles(recs, nr, pcts),)
 
+    # ---------------------------------------------------------------- group records of any period, group QPS / active-connection histograms, day statistics per group
+    def _filtered_call(self, fn, group_by, filt, any_state, maxrows, out_of, *mid):
+        """the rows / maxrows / nrows part the filtered group calls share: fn(h, filter, flags, group_by, *mid, rows, maxrows, &nrows, out, ...);
+        out_of(cap) -> (device tensor, trailing arguments).  Returns (rows, nrows there are, rows written, tensor)"""
+        f, keep = self._svc_filter(*filt)
+        if maxrows is None:
+            maxrows = {capi.GROUP_NONE: 1, capi.GROUP_HOST: self.L.gys_num_hosts(self.h), capi.GROUP_CLUSTER: self.L.gys_num_clusters(self.h)}.get(
+                group_by, min(getattr(self, "_label_domain", 0), self.num_services()))
+        cap = max(maxrows, 1)
+        out, trail = out_of(cap)
+        rows = (capi.RollupRow * cap)()
+        n = C.c_uint32()
+        self.order()
+        capi.check(fn(self.h, C.byref(f), capi.RF_ANY_STATE if any_state else 0, group_by, *mid, rows, maxrows, C.byref(n), C.c_void_p(out.data_ptr()), *trail))
+        self.sync()
+        nr = min(n.value, maxrows)
+        return [(rows[i].group, rows[i].nmembers) for i in range(nr)], n.value, nr, out
+
+    def _recs(self, cap):
+        return self.torch.zeros((cap, 16, 2), dtype=self.torch.int64, device=self.device)
+
+    def _pcts_of(self, dev_recs, n, pcts, kind):
+        out = self.torch.zeros(max(n * len(pcts), 1), dtype=self.torch.int64, device=self.device)
+        pa = (C.c_float * len(pcts))(*pcts)
+        capi.check(self.L.gys_hist_percentiles_dev(self.h, kind, C.c_void_p(dev_recs.data_ptr()), n, pa, len(pcts), C.c_void_p(out.data_ptr())))
+        self.sync()
+        return out[:n * len(pcts)].cpu().numpy().reshape(n, len(pcts))
+
+    def hist_rollup_period(self, scope, starttime, endtime, tusec, pcts=None):
+        """gys_hist_rollup_period_dev: the hosts' / clusters' / the rank's records of the seconds [starttime, endtime] as of tusec ->
+        (records [groups][16][2] int64 like export_hist_period, level that answered); with pcts=(...) a third element: their percentiles
+        (groups, len(pcts)) int64 of gys_hist_percentiles_dev on the device records"""
+        n = self._hll_groups(scope)
+        recs = self._recs(max(n, 1))
+        lv = C.c_int(-1)
+        self.order()
+        capi.check(self.L.gys_hist_rollup_period_dev(self.h, scope, int(starttime), int(endtime), int(tusec), C.c_void_p(recs.data_ptr()), C.byref(lv)))
+        self.sync()
+        res = (recs[:n].cpu().numpy(), lv.value)
+        return res if pcts is None else res + (self._pcts_of(recs, n, pcts, 0),)
+
+    def hist_rollup_period_filtered(self, group_by, starttime, endtime, tusec, terms=None, group_oper=(), top_oper="and", machine_ids=None, svcids=None,
+                                    clusters=None, any_state=False, maxrows=None, pcts=None):
+        """gys_hist_rollup_period_filtered_dev -> (rows [(group, nmembers)], nrows there are, records [rows][16][2] int64, level that answered);
+        with pcts=(...) a fifth element: the rows' percentiles"""
+        lv = C.c_int(-1)
+        rows, n, nr, recs = self._filtered_call(self.L.gys_hist_rollup_period_filtered_dev, group_by, (terms, group_oper, top_oper, machine_ids, svcids, clusters),
+                                                any_state, maxrows, lambda cap: (self._recs(cap), (C.byref(lv),)), int(starttime), int(endtime), int(tusec))
+        res = (rows, n, recs[:nr].cpu().numpy(), lv.value)
+        return res if pcts is None else res + (self._pcts_of(recs, nr, pcts, 0),)
+
+    @staticmethod
+    def _svc_hist_kind(which):
+        return capi.KINDS["HASH_1_3000" if which else "SEMI_LOG_HASH_LO"]
+
+    def svc_hist_rollup(self, scope, which, pcts=None):
+        """gys_svc_hist_rollup_dev: the groups' QPS (which = 0) / active-connection (1) histograms, [groups][16][2] int64 like export_svc_hist;
+        with pcts=(...) -> (records, percentiles by the matching hash kind)"""
+        n = self._hll_groups(scope)
+        recs = self._recs(max(n, 1))
+        self.order()
+        capi.check(self.L.gys_svc_hist_rollup_dev(self.h, scope, which, C.c_void_p(recs.data_ptr())))
+        self.sync()
+        out = recs[:n].cpu().numpy()
+        return out if pcts is None else (out, self._pcts_of(recs, n, pcts, self._svc_hist_kind(which)))
+
+    def svc_hist_rollup_filtered(self, group_by, which, terms=None, group_oper=(), top_oper="and", machine_ids=None, svcids=None, clusters=None, any_state=False,
+                                 maxrows=None, pcts=None):
+        """gys_svc_hist_rollup_filtered_dev -> (rows, nrows there are, records [rows][16][2] int64); with pcts=(...) a fourth element"""
+        rows, n, nr, recs = self._filtered_call(self.L.gys_svc_hist_rollup_filtered_dev, group_by, (terms, group_oper, top_oper, machine_ids, svcids, clusters),
+                                                any_state, maxrows, lambda cap: (self._recs(cap), ()), which)
+        res = (rows, n, recs[:nr].cpu().numpy())
+        return res if pcts is None else res + (self._pcts_of(recs, nr, pcts, self._svc_hist_kind(which)),)
+
+    DAY_STATS_DT = np.dtype([("glob_id", "<u8"), ("tcount_5d", "<i8"), ("tsum_5d", "<i8"), ("p95_5d_respms", "<u4"), ("p25_5d_respms", "<u4"), ("p95_qps", "<u4"),
+                             ("p25_qps", "<u4"), ("p95_nactive", "<u4"), ("p25_nactive", "<u4")])  # == capi.ListenerDayStats
+
+    def _day_stats(self, cap):
+        return self.torch.zeros(cap * self.DAY_STATS_DT.itemsize, dtype=self.torch.uint8, device=self.device)
+
+    def day_stats_rollup(self, scope, tusec):
+        """gys_day_stats_rollup_dev: one LISTENER_DAY_STATS per host slot / cluster / the rank as a numpy record array (DAY_STATS_DT)"""
+        n = self._hll_groups(scope)
+        out = self._day_stats(max(n, 1))
+        self.order()
+        capi.check(self.L.gys_day_stats_rollup_dev(self.h, scope, int(tusec), C.c_void_p(out.data_ptr())))
+        self.sync()
+        return np.frombuffer(out.cpu().numpy().tobytes(), dtype=self.DAY_STATS_DT)[:n]
+
+    def day_stats_rollup_filtered(self, group_by, tusec, terms=None, group_oper=(), top_oper="and", machine_ids=None, svcids=None, clusters=None, any_state=False,
+                                  maxrows=None):
+        """gys_day_stats_rollup_filtered_dev -> (rows, nrows there are, DAY_STATS_DT records of the rows)"""
+        rows, n, nr, out = self._filtered_call(self.L.gys_day_stats_rollup_filtered_dev, group_by, (terms, group_oper, top_oper, machine_ids, svcids, clusters),
+                                               any_state, maxrows, lambda cap: (self._day_stats(cap), ()), int(tusec))
+        return rows, n, np.frombuffer(out.cpu().numpy().tobytes(), dtype=self.DAY_STATS_DT)[:nr]
+
     def json_clusterstate(self, shyamaid="0" * 16, timestr=""):
         return self._json(self.L.gys_json_clusterstate, shyamaid.encode(), timestr.encode())
 

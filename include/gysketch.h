@@ -787,6 +787,49 @@ int gys_hist_rollup_level_dev(gys_ctx *ctx, int scope, int level, uint64_t tusec
 int gys_hist_rollup_filtered_dev(gys_ctx *ctx, const gys_svc_filter *filter, uint32_t flags, int group_by, int level, uint64_t tusec,
 				 gys_rollup_row *rows, uint32_t maxrows, uint32_t *nrows, gys_hist_rec *d_recs);
 
+/* -------------------------------------------------------------------------------------------------------------------
+ * Group response-time histograms for ANY PERIOD, group QPS / active-connection histograms, day statistics per group: the per-service
+ * questions gys_export_hist_period, gys_export_svc_hist and gys_export_day_stats asked of a host, a cluster, the rank or the rows of a filtered
+ * selection.  The roll-up digests are since-start only (a t-digest cannot be subtracted), so the group record of a period IS the windowed
+ * percentile of a group: "p95 of this cluster between 14:00 and 14:30" = get_stats_for_period_with_flush asked of a group.
+ *   GROUP PERIOD RECORD at (starttime, endtime, tusec) = GY_HISTOGRAM::add_histogram (common/gy_statistics.h:625-660) of the members' records
+ *   exactly as gys_export_hist_period returns them for the same three arguments: per bucket b < 15 count and sum are the 64-bit sums of the
+ *   members' values -- the scaling and truncation of a partly covered ring bucket (float, BucketedTimeSeries::rangeAdjust) happen per MEMBER and
+ *   per RING BUCKET, before the add, the since-start level's per-service bucket [first close, tq + 1) included; the group record is therefore
+ *   NOT a function of the group's level records and is computed by a pass over the members on the device.  total_count = the sum of the
+ *   members' total_count = the sum of the group's 15 counts; max_val_seen = the largest of the members' all-time maxima; no member: all zero,
+ *   max_val_seen = INT64_MIN.  The answering level depends on starttime, tq and enable_levels only: the same for every member, returned once
+ *   through level_used (may be NULL; set whether or not there is a group).  Argument rules, tq = max(tusec / 10^6, the last close), "never the
+ *   open window" and the enable_levels = 0 (GYS_ERR_STATE) / 2 (no 5-s level: the 300-s ring answers) behaviour are those of
+ *   gys_export_hist_period; no interval is rejected there, none is here.
+ *   GROUP QPS / ACTIVE-CONNECTION HISTOGRAMS: which = 0 QPS (SEMI_LOG_HASH_LO), 1 active connections (HASH_1_3000); the group record is the same
+ *   sum over the members' records as gys_export_svc_hist returns them; no member: all zero with INT64_MIN.  A member that never reported
+ *   carries max_val_seen = INT32_MIN, the value gys_create leaves in these per-service records, so a group whose members never reported shows
+ *   INT32_MIN, not INT64_MIN.  The definition is this library's: the distribution of the 5-s samples of the group's listeners (the reference
+ *   keeps these histograms per listener only).  Percentiles: gys_hist_percentiles_dev with GYS_SEMI_LOG_HASH_LO / GYS_HASH_1_3000.
+ *   GROUP DAY STATISTICS: one gys_listener_day_stats per group; glob_id = the group index (host slot, cluster index, 0, the row's group);
+ *   tcount_5d / tsum_5d / p95 / p25 from the group's level-2 record at tusec, p95 / p25 of QPS and active connections from the two group
+ *   histograms, all by the rule gys_export_day_stats applies to a service's records.  A group without members (a host slot without services,
+ *   a cluster without hosts) has glob_id and zeros.
+ *   BIT-EXACT and order-free, as the level records above: everything after the per-member rule is 64-bit integer addition and a maximum, so
+ *   services -> hosts -> cluster equals services -> cluster directly, and an all-selecting filtered call grouped by host or cluster equals the
+ *   fixed scopes.  Scopes, outputs per host slot / cluster / one, rows, maxrows, *nrows, GYS_RF_ANY_STATE, labels and "no services: GYS_OK,
+ *   *nrows = 0" are those of gys_hist_rollup_level_dev / gys_hist_rollup_filtered_dev.  Scratch kept by the context (one record per chunk of
+ *   1024 members, one per host, three per group for the day statistics); nothing is kept per service.  No engine state a query can see is
+ *   modified; asynchronous on the context stream (gys_sync).  GYS_ERR_STATE without enable_levels; GYS_ERR_INVAL for an unknown scope, which,
+ *   group_by or flags and for NULL outputs, filter, rows or nrows.
+ *   ACROSS RANKS there is no collective of its own: the caller all-gathers the group records and adds the records of one group with
+ *   gys_hist_merge_dev, as for the levels (day statistics across ranks: from the merged records). */
+int gys_hist_rollup_period_dev(gys_ctx *ctx, int scope, int64_t starttime, int64_t endtime, uint64_t tusec, gys_hist_rec *d_out, int *level_used);
+int gys_hist_rollup_period_filtered_dev(gys_ctx *ctx, const gys_svc_filter *filter, uint32_t flags, int group_by, int64_t starttime, int64_t endtime,
+					uint64_t tusec, gys_rollup_row *rows, uint32_t maxrows, uint32_t *nrows, gys_hist_rec *d_recs, int *level_used);
+int gys_svc_hist_rollup_dev(gys_ctx *ctx, int scope, int which, gys_hist_rec *d_out);
+int gys_svc_hist_rollup_filtered_dev(gys_ctx *ctx, const gys_svc_filter *filter, uint32_t flags, int group_by, int which, gys_rollup_row *rows,
+				     uint32_t maxrows, uint32_t *nrows, gys_hist_rec *d_recs);
+int gys_day_stats_rollup_dev(gys_ctx *ctx, int scope, uint64_t tusec, gys_listener_day_stats *d_out);
+int gys_day_stats_rollup_filtered_dev(gys_ctx *ctx, const gys_svc_filter *filter, uint32_t flags, int group_by, uint64_t tusec, gys_rollup_row *rows,
+				      uint32_t maxrows, uint32_t *nrows, gys_listener_day_stats *d_out);
+
 /* The per-listener 5-second scan from the engine's OWN state (needs gys_config.enable_levels): replaces the loop of
  * TCP_SOCK_HANDLER::listener_stats_update (common/gy_socket_stat.cc:4044-4365) that turns every listener's counters and histograms into
  * one comm::LISTENER_STATE_NOTIFY (common/gy_comm_proto.h:2183-2254), and the data-parallel part of TCP_LISTENER::get_curr_state
