@@ -190,6 +190,9 @@ SIGNATURES = {
     "gys_query_topn": (C.c_int, [vp, mid, C.c_int, C.POINTER(TopnEntry), u32p]),
     "gys_scan_percentiles_dev": (C.c_int, [vp, C.c_int, f32p, C.c_uint32, vp]),
     "gys_scan_quantiles_dev": (C.c_int, [vp, f64p, C.c_uint32, vp]),
+    "gys_query_ranks": (C.c_int, [vp, C.c_uint64, C.POINTER(C.c_int64), C.c_uint32, f64p, C.POINTER(C.c_uint64)]),
+    "gys_scan_ranks_dev": (C.c_int, [vp, C.POINTER(C.c_int64), C.c_uint32, vp, vp]),
+    "gys_tdigest_slab_ranks_dev": (C.c_int, [vp, vp, C.c_uint32, C.POINTER(C.c_int64), C.c_uint32, vp, vp]),
     "gys_scan_listener_state_dev": (C.c_int, [vp, C.c_uint64, C.c_float, C.c_uint32, vp, vp]),
     "gys_decide_listener_state_dev": (C.c_int, [vp, vp, vp, vp, vp]),
     "gys_tdigest_rollup_dev": (C.c_int, [vp, C.c_int, vp]),

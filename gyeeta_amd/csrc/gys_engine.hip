@@ -40,6 +40,7 @@
 #include "gys_svcquery.hpp"
 #include "gys_rollsel.hpp"
 #include "gys_svcdel.hpp"
+#include "gys_tdrank.hpp"
 
 using namespace gys;
 
@@ -213,6 +214,7 @@ struct gys_ctx {
 	DevBuf<uint32_t> td_cnt;
 	DevBuf<TdMeta> td_meta;
 	DevBuf<int2> td_minmax;
+	DevBuf<double> rank_row;      // gys_query_ranks: the one row k_td_ranks writes (GYS_TR_MAXT doubles, then the total); kept between calls
 	DevBuf<uint32_t> td_pend;     // per service a buffer of pcap staged words ("per-key value buffers" in gys_kernels.hpp)
 	DevBuf<uint32_t> td_cur;      // words in each buffer (== td_meta.npend between batches)
 	DevBuf<uint32_t> td_run;      // spilled services: fill cursor of the run in `staged`
@@ -3993,6 +3995,78 @@ try {
 		}
 	}
 	return GYS_OK;
+} GYS_CATCH_ALL
+
+// ------------------------------------------------------------------------------------------------ ranks (gys_tdrank.hpp)
+// k_td_ranks over members [first, first + n): service slots (d_in == nullptr) or the slabs at d_in.  Asynchronous on the context stream.
+static int td_ranks_launch(gys_ctx *c, const gys_tdigest_slab *d_in, uint32_t first, uint32_t n, const int64_t *thr, uint32_t nt, double *d_below, uint64_t *d_total)
+{
+	if (!n) return GYS_OK;
+	TdRankP rp{};
+	rp.d = digest_params(c);
+	rp.in = d_in;
+	rp.first = first;
+	rp.n = n;
+	rp.nt = nt;
+	for (uint32_t i = 0; i < nt; ++i) rp.thr[i] = thr[i];
+	rp.below = d_below;
+	rp.total = (unsigned long long *)d_total;
+	// a wave per member, four to a workgroup.  Up to 16 workgroups per CU: with 1 - 4 thresholds eight of them are resident at a time (8 waves per
+	// SIMD; 5 - 8 thresholds: six, 9 - 16: five), the rest follow as those finish and even out the tail
+	const dim3 grid(std::max(1u, std::min<uint32_t>((n + 3u) / 4u, (uint32_t)c->ncu * 16u))), block(GYS_TR_NT);
+	ProfScope ps(c, d_in ? "slab_ranks" : "scan_ranks");
+	if (d_in) hipLaunchKernelGGL((k_td_ranks<1, 1u>), grid, block, 0, c->stream, rp);
+	else if (nt <= 2u) hipLaunchKernelGGL((k_td_ranks<0, 1u>), grid, block, 0, c->stream, rp);
+	else if (nt <= 4u) hipLaunchKernelGGL((k_td_ranks<0, 2u>), grid, block, 0, c->stream, rp);
+	else if (nt <= 8u) hipLaunchKernelGGL((k_td_ranks<0, 4u>), grid, block, 0, c->stream, rp);
+	else hipLaunchKernelGGL((k_td_ranks<0, 8u>), grid, block, 0, c->stream, rp);
+	HIPCHK(hipGetLastError());
+	return GYS_OK;
+}
+
+#define RANKS_NT_CHECK(name)                                                             \
+	if (nt == 0 || nt > GYS_TR_MAXT) {                                               \
+		set_err(name ": 1 .. %u thresholds per call", (unsigned)GYS_TR_MAXT);    \
+		return GYS_ERR_INVAL;                                                    \
+	}
+
+int gys_scan_ranks_dev(gys_ctx *c, const int64_t *thr, uint32_t nt, double *d_below, uint64_t *d_total)
+try {
+	GYS_ENTER(c);
+	if (!c || !thr || !d_below) return GYS_ERR_INVAL;
+	TDIGEST_CHECK();
+	RANKS_NT_CHECK("gys_scan_ranks_dev");
+	return td_ranks_launch(c, nullptr, 0u, c->nsvc, thr, nt, d_below, d_total);
+} GYS_CATCH_ALL
+
+int gys_query_ranks(gys_ctx *c, uint64_t glob_id, const int64_t *thr, uint32_t nt, double *below, uint64_t *total)
+try {
+	GYS_ENTER(c);
+	if (!c || !thr || !below) return GYS_ERR_INVAL;
+	TDIGEST_CHECK();
+	RANKS_NT_CHECK("gys_query_ranks");
+	uint32_t slot;
+	int rc = gys_lookup_service(c, glob_id, &slot);
+	if (rc) return rc;
+	// the scan's kernel on this one slot: nt doubles, then the total, in a row the context keeps
+	if ((rc = c->rank_row.grow(GYS_TR_MAXT + 1u, c->stream)) != GYS_OK) return rc;
+	double *const d_row = c->rank_row.p;
+	if ((rc = td_ranks_launch(c, nullptr, slot, 1u, thr, nt, d_row, (uint64_t *)(d_row + nt))) != GYS_OK) return rc;
+	double row[GYS_TR_MAXT + 1u];
+	HIPCHK(hipMemcpyAsync(row, d_row, ((size_t)nt + 1u) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	memcpy(below, row, (size_t)nt * sizeof(double));
+	if (total) memcpy(total, row + nt, sizeof(uint64_t));
+	return GYS_OK;
+} GYS_CATCH_ALL
+
+int gys_tdigest_slab_ranks_dev(gys_ctx *c, const gys_tdigest_slab *d_slabs, uint32_t nslabs, const int64_t *thr, uint32_t nt, double *d_below, uint64_t *d_total)
+try {
+	GYS_ENTER(c);
+	if (!c || !d_slabs || !thr || !d_below) return GYS_ERR_INVAL;
+	TDIGEST_CHECK();
+	RANKS_NT_CHECK("gys_tdigest_slab_ranks_dev");
+	return td_ranks_launch(c, d_slabs, 0u, nslabs, thr, nt, d_below, d_total);
 } GYS_CATCH_ALL
 
 // ------------------------------------------------------------------------------------------------ the cached groupings

@@ -323,6 +323,41 @@ class SketchEngine:
         capi.check(self.L.gys_scan_quantiles_dev(self.h, qa, len(qs), C.c_void_p(out.data_ptr())))
         return out[:n].cpu().numpy()
 
+    # ---------------------------------------------------------------- ranks: how many responses finished within x ms ("Ranks" in gysketch.h)
+    @staticmethod
+    def _thresholds(thr):
+        thr = [int(x) for x in thr]
+        return (C.c_int64 * max(len(thr), 1))(*thr), len(thr)
+
+    def ranks(self, glob_id, thr):
+        """one service (gys_query_ranks): (below [len(thr)] float64, total) -- the same bits as scan_ranks(thr)[0][slot]"""
+        ta, nt = self._thresholds(thr)
+        below, total = np.zeros(max(nt, 1), dtype=np.float64), C.c_uint64()
+        capi.check(self.L.gys_query_ranks(self.h, int(glob_id), ta, nt, below.ctypes.data_as(C.POINTER(C.c_double)), C.byref(total)))
+        return below[:nt], total.value
+
+    def scan_ranks(self, thr):
+        """EVERY service slot in one device pass (gys_scan_ranks_dev): (below [nsvc][len(thr)] float64, total [nsvc] uint64)"""
+        ta, nt = self._thresholds(thr)
+        n = self.num_services()
+        below = self.torch.empty((max(n, 1), max(nt, 1)), dtype=self.torch.float64, device=self.device)
+        total = self.torch.empty(max(n, 1), dtype=self.torch.int64, device=self.device)
+        self.order()
+        capi.check(self.L.gys_scan_ranks_dev(self.h, ta, nt, C.c_void_p(below.data_ptr()), C.c_void_p(total.data_ptr())))
+        self.sync()
+        return below[:n].cpu().numpy(), total[:n].cpu().numpy().view(np.uint64)
+
+    def slab_ranks(self, dev_slabs, n, thr):
+        """the same for n slabs on the device (gys_tdigest_slab_ranks_dev): roll-ups of any scope, rows of rollup_filtered, a cross-rank
+        merge -- (below [n][len(thr)] float64, total [n] uint64)"""
+        ta, nt = self._thresholds(thr)
+        below = self.torch.empty((max(n, 1), max(nt, 1)), dtype=self.torch.float64, device=self.device)
+        total = self.torch.empty(max(n, 1), dtype=self.torch.int64, device=self.device)
+        self.order()
+        capi.check(self.L.gys_tdigest_slab_ranks_dev(self.h, C.c_void_p(dev_slabs.data_ptr()), n, ta, nt, C.c_void_p(below.data_ptr()), C.c_void_p(total.data_ptr())))
+        self.sync()
+        return below[:n].cpu().numpy(), total[:n].cpu().numpy().view(np.uint64)
+
     LSCAN_DT = np.dtype([("glob_id", "<u8"), ("tcount", "<i8", 4), ("tsum", "<i8", 4), ("p95_ms", "<i4", 4), ("p99_ms", "<i4", 4), ("p25_ms", "<i4", 4),
                          ("last_qps", "<i4"), ("curr_qps", "<i4"), ("qps_p95", "<i4"), ("qps_p25", "<i4"), ("act_p95", "<i4"), ("act_p25", "<i4"),
                          ("b5", "u1"), ("b300", "u1"), ("b5day", "u1"), ("nconn_active", "u1"), ("nactive_conn_arr", "u1", 15), ("reserved", "u1", 5)])

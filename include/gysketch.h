@@ -421,6 +421,38 @@ int gys_scan_percentiles_dev(gys_ctx *ctx, int which, const float *pcts, uint32_
 int gys_scan_quantiles_dev(gys_ctx *ctx, const double *q, uint32_t nq, double *d_out);
 
 /* -------------------------------------------------------------------------------------------------------------------
+ * Ranks: how many responses finished within x ms -- the inverse of the quantile calls, for the share of requests inside a latency
+ * objective (below / total), an error budget or an Apdex figure, per service and per group.  Builder-defined, PARITY UNPINNED like the
+ * t-digest itself.  The definition is FROZEN.  For a digest with clusters {sum[k], cnt[k]} (k < GYS_TD_NB), extremes vmin / vmax, a
+ * multiset P of buffered values (a service's; empty for a slab) and an integer threshold x (milliseconds, any int64_t), below(x) is a
+ * double that estimates the number of recorded values <= x:
+ *   1. nb = the number of values of P that are <= x: exact.
+ *   2. N = sum of cnt; total = N + |P|.  N = 0: below = (double)nb.
+ *   3. lo = min(vmin, min P), hi = max(vmax, max P).  x < lo: the clusters' part r = 0.  x >= hi: r = (double)N.
+ *   4. Otherwise the clusters are read at y = (double)x + 0.5: the values are whole milliseconds, and a value v stands for the interval
+ *      [v - 1/2, v + 1/2] -- the inverse of the quantile calls, which round the interpolated latency half-up to whole milliseconds.  Over the
+ *      non-empty clusters in index order, W_k = the exact integer weight before cluster k, c_k = (double)W_k + (double)cnt_k * 0.5,
+ *      m_k = (double)sum_k / (double)cnt_k; j = the greatest non-empty index whose mean is at most x + 1/2, decided in exact integers:
+ *      sum_j - floor(cnt_j / 2) <= x * cnt_j (128-bit product); n = the next non-empty index after j, f = the first non-empty index:
+ *        no such j:     r = c_f * ((y - ((double)lo - 0.5)) / (m_f - ((double)lo - 0.5)))
+ *        j is the last: r = c_j + ((double)N - c_j) * ((y - m_j) / (((double)hi + 0.5) - m_j))
+ *        otherwise:     r = c_j + (c_n - c_j) * ((y - m_j) / (m_n - m_j))
+ *      Every denominator is positive by construction.  Only + - * / on doubles, in exactly this order (the library is built with
+ *      -ffp-contract=off: a restatement in another language gives the same bits).
+ *   5. below = r + (double)nb.
+ * The buffered values are counted exactly, not merged virtually.  below is monotone in x, 0 for x below every value and == total at and
+ * above the largest.  Why x + 1/2 and not x: read at x itself, a cluster whose mean is exactly x counts with half its weight (its centre)
+ * although all of its values are <= x; wherever one millisecond value carries a hundredth of the weight (a service answering in 1 500 +- 3 ms,
+ * the small latencies of a lognormal) that alone was 1.0 - 1.5 % of the total, above the project's 1 % rank-error tolerance.  Measured rank
+ * error |below - exact| / total against the exact sort: DESIGN.md section 4.
+ * thr is a HOST array of nt = 1 .. 16 thresholds (GYS_ERR_INVAL otherwise); GYS_ERR_STATE when enable_tdigest is 0.  No state is modified. */
+/* one service: below[nt] and *total (may be NULL) on the HOST */
+int gys_query_ranks(gys_ctx *ctx, uint64_t glob_id, const int64_t *thr, uint32_t nt, double *below, uint64_t *total);
+/* EVERY service slot in one streaming pass: d_below[slot * nt + i], d_total[slot] (DEVICE; d_total may be NULL).  A slot without data and
+ * a free slot give 0 and 0.  Row `slot` equals gys_query_ranks of that service bit for bit.  Asynchronous on the context stream (gys_sync). */
+int gys_scan_ranks_dev(gys_ctx *ctx, const int64_t *thr, uint32_t nt, double *d_below /* [nsvc * nt] */, uint64_t *d_total /* [nsvc] */);
+
+/* -------------------------------------------------------------------------------------------------------------------
  * Roll-up digests: the response-time digest of a GROUP of services -- a host, a cluster, all hosts of this rank ("global") -- and the
  * merge of such digests across ranks.  Replaces the aggregated percentile Postgres computes over a set of listeners' rows,
  * public.tdigest_percentile(col, 100, p) (common/gy_query_common.cc:1818-1855), and feeds the fan-in of
@@ -447,6 +479,11 @@ int gys_tdigest_rollup_dev(gys_ctx *ctx, int scope, gys_tdigest_slab *d_out);
 int gys_tdigest_merge_slabs_dev(gys_ctx *ctx, const gys_tdigest_slab *d_in, uint32_t n, gys_tdigest_slab *d_out);
 /* quantiles q[i] (0..1) of one DEVICE slab into the HOST array out (same interpolation and rounding as gys_query_quantiles) */
 int gys_tdigest_slab_quantiles(gys_ctx *ctx, const gys_tdigest_slab *d_slab, const double *q, uint32_t nq, double *out);
+/* below(x) ("Ranks" above; P is empty, the extremes are the slab's) of nslabs DEVICE slabs -- the host, cluster and global roll-ups, the rows
+ * of gys_rollup_filtered_dev, a cross-rank merge: d_below[i * nt + t], d_total[i] = the slab's weight (DEVICE; d_total may be NULL).
+ * Asynchronous on the context stream. */
+int gys_tdigest_slab_ranks_dev(gys_ctx *ctx, const gys_tdigest_slab *d_slabs, uint32_t nslabs, const int64_t *thr, uint32_t nt, double *d_below,
+			       uint64_t *d_total);
 uint32_t gys_num_clusters(gys_ctx *ctx);
 
 /* -------------------------------------------------------------------------------------------------------------------
