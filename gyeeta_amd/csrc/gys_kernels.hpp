@@ -824,22 +824,6 @@ __global__ __launch_bounds__(256) void k_cms_reduce(const uint32_t *partial, uin
 //   SPILL:  second pass over the hosts that have spilled keys: only those keys' events, into their runs in `staged`.
 // RESP_TIME_HASH bucket of a response time through a 1 KiB LDS table: values below 1024 -- eleven of the thirteen thresholds -- take one LDS
 // byte read (ds_read_u8 at t & 1023), the rest two compares; resp_bucket() costs 13 compare + add pairs
-#ifndef GYS_EV_DMA
-#define GYS_EV_DMA 0 // (r6h / r6i: bit-exact and SLOWER -- 5.85 ms without, 6.22 ms with the requests one group ahead, against 5.24 - 5.39 ms; left off) (16 384-event tiles) a wave's events come in through LDS: six global_load_lds_dwordx4 per group of four event slots -- every 128-byte line of the wave's span requested ONCE, no destination registers -- into the wave's 6 KB of the (idle) tile-image area, then three 8-byte LDS reads per event.  r6g's counters: the vector-memory path stalls on pending lines half the time (TCP_PENDING_STALL_CYCLES 51 %, TD_TC_STALL 52 % of the kernel's cycles) with the strided 16 + 8-byte loads, which ask for every line twice
-#endif
-#ifndef GYS_EV_DMA_AHEAD
-#define GYS_EV_DMA_AHEAD 1 // the requests of group g + 1 are issued as soon as group g's words have been read out of the wave's area (they run under group g's work)
-#endif
-#if defined(__HIP_DEVICE_COMPILE__)
-#ifndef GYS_EV_DMA_CPOL
-#define GYS_EV_DMA_CPOL 0 // cache policy bits of the requests (2 = nt: the event lines pass through the L2 without displacing the partly written buffer lines of the flush)
-#endif
-#define GYS_DMA16(gptr, ldsptr) __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gptr), (__attribute__((address_space(3))) void *)(ldsptr), 16, 0, GYS_EV_DMA_CPOL) // lane l's 16 bytes land at ldsptr + 16 l (ldsptr: wave-uniform)
-#define GYS_DMA_WAIT() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-#else
-#define GYS_DMA16(gptr, ldsptr) memcpy((char *)(ldsptr) + 16u * (threadIdx.x & 63u), (const void *)(gptr), 16)
-#define GYS_DMA_WAIT() ((void)0)
-#endif
 #ifndef GYS_PARK_INDEX
 #define GYS_PARK_INDEX 1 // the rank atomic of a place that kept nothing goes to s_ts[Lc_park + lane]: one select for the index, no select between two addresses
 #endif
@@ -939,6 +923,16 @@ __host__ __device__ __forceinline__ size_t resp_host_lds_bytes(uint32_t tbl_entr
 #define GYS_OPAQUE_LOADED4(a) asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]))
 #endif
 #define GYS_MEM_FENCE() asm volatile("" ::: "memory") // compiler-only: memory operations are not moved across it (keeps a batch of LDS reads in front of the stores / the next batch)
+
+// slot stride of a group of four event slots with r > 0 events left in the tile (T threads): T while the group is full; in the tile's partly
+// filled last group the r events are packed into the four slots of the lowest threads -- a quarter of them per slot, rounded up to whole
+// waves, so that the waves from thread S on have no event in any slot and leave the group loop (53 687 events: the last tile's second
+// group has 439 events left -- 2 waves run it, not 16)
+template <uint32_t T>
+__host__ __device__ __forceinline__ uint32_t resp_slot_stride(uint32_t r)
+{
+	return r >= 4u * T ? T : (((r + 3u) / 4u + 63u) & ~63u);
+}
 
 // MODE 0: IPv4 events, every listener of the batch's hosts alone on its (netns, port) key and bound to the any-address (the instance of the
 // measured configurations: nothing below costs it an instruction); 1: IPv4 events, keys with candidates (bound-address listeners) are
@@ -1058,19 +1052,8 @@ __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), 4) void k_resp_host(RespHost
 	unsigned long long t_prev__ = (unsigned long long)clock64();
 #endif
 	const uint32_t tid24 = 24u * tid;
+	const uint32_t wbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid & ~63u)); // the wave's first thread (uniform)
 	int32_t tmax = INT32_MIN, wmax = -1;
-	// events through LDS (GYS_EV_DMA): the tile image of 6 bytes per event is 6 KB per wave with 16 events per thread -- room for the 4 x 1536 bytes of a
-	// group's four event slots.  Layout of a wave's area: the first KB of slot u at 1024 u, its last 512 bytes at 4096 + 512 u (the tails of two slots
-	// are one full-width request).  The 8-byte piece k of lane l's event (byte 24 l + 8 k of the slot) never straddles the KB boundary.
-	constexpr bool DMA = GYS_EV_DMA && TPT == 16 && !SPILL && MODE != 2;
-	char *const dma_ws = (char *)s_val + wave * 6144u;
-	uint32_t dma_a[3], dma_s[3]; // address of piece k in slot 0 and its stride from slot to slot
-#pragma unroll
-	for (uint32_t k = 0; k < 3u; ++k) {
-		const uint32_t byte = 24u * lane + 8u * k;
-		dma_a[k] = byte < 1024u ? byte : 4096u + (byte - 1024u);
-		dma_s[k] = byte < 1024u ? 1024u : 512u;
-	}
 	GYS_TICK(10); // prologue: tables, floor
 	for (uint64_t t0 = e0; t0 < e1; t0 += TILE, ++tile_no) {
 		GYS_RESP_P_RELOAD();
@@ -1078,7 +1061,6 @@ __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), 4) void k_resp_host(RespHost
 		// double-buffered and were cleared two phases ago, the floor and the candidate queue were settled behind barriers of the
 		// previous tile; a wave that is done flushing starts on its next events while the others still flush)
 		uint32_t *const s_ts = s_ts2 + (tile_no & 1u) * Lc;
-		if (DMA) __syncthreads(); // (the waves stage their events in the tile-image area: the previous tile's flush must be over)
 #if GYS_PARK_INDEX
 #if defined(__HIP_DEVICE_COMPILE__)
 		typedef uint32_t park_ix_t; // (LDS addresses are 32 bits: wrap-around arithmetic on word indices, s_ts[park_ix] is s_park[lane])
@@ -1096,7 +1078,7 @@ __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), 4) void k_resp_host(RespHost
 		// instruction cache two CUs share); the per-event results live in registers all the same: wd / lr are shifted down by 4 per
 		// group, so that every index stays a compile-time constant and after TPT / 4 groups event g sits at wd[g].
 		const uint64_t left = e1 - t0;
-		const uint32_t rem = left < (uint64_t)TILE ? (uint32_t)left : TILE; // events of this tile (> 0)
+		const uint32_t rem = (uint32_t)__builtin_amdgcn_readfirstlane((int)(left < (uint64_t)TILE ? (uint32_t)left : TILE)); // events of this tile (> 0; uniform)
 		const uint64_t *const tb = p.ev + (uint64_t)SW * t0;
 		uint32_t wd[TPT], lr[TPT]; // staged word (GYS_EV_DROPPED: not kept) / local index | rank inside the key's tile run << 12
 #pragma unroll
@@ -1107,74 +1089,33 @@ __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), 4) void k_resp_host(RespHost
 #pragma unroll 1
 		for (int g = 0; g < TPT; g += 4) {
 			if ((uint32_t)g * T >= rem) break; // the segment's last tile is usually short (C3: 53 687 events = 3.28 tiles): no empty groups
+			// slot u of the group holds the events g T + u S + tid of the tile (tid < S): S = T, except in the tile's partly filled last group,
+			// whose events are packed into the four slots of the lowest threads -- the waves from thread S on hold nothing in any slot and
+			// leave the loop (resp_slot_stride).  Which thread takes an event does not matter to any result
+			const uint32_t S = resp_slot_stride<T>(rem - (uint32_t)g * T);
+			if (wbase >= S) break;
 			uint64_t w0[4], w1[4], w2[4];
 			bool in[4];
 #pragma unroll
 			for (int u = 0; u < 4; ++u) {
-				const uint32_t o = (uint32_t)(g + u) * T + tid;
-				in[u] = o < rem;
-				const uint32_t oo = in[u] ? o : 0u; // (lanes past the end read the tile's first event and ignore it: no branch around the loads)
+				// the tile's base is uniform and an event's byte offset inside the tile fits 32 bits: written so, the three loads share ONE
+				// 32-bit offset register (scalar base + offset + immediate) instead of a 64-bit address each.  Round 6: the offset is
+				// 24 tid (kept) + 24 (g T + u S) (scalar) -- no 32-bit multiply (a quarter-rate instruction) per event
+				const uint32_t first = (uint32_t)g * T + (uint32_t)u * S, last = min(rem, first + S); // the slot's events [first, last) (uniform)
+				const uint32_t ob_raw = tid24 + 24u * first;
+				in[u] = ob_raw < 24u * last;
+				const uint32_t ob = in[u] ? ob_raw : 0u; // (lanes without an event read the tile's first event and ignore it: no branch around the loads)
 				if (V6) { // the name space / ports word and the times word; the addresses are read where they are needed (candidates, flow hash)
+					static_assert(GYS_EV6_WORDS == 6, "ob = 24 o: word 6 o of the tile is ob / 4");
 					w0[u] = 0;
-					w1[u] = tb[GYS_EV6_WORDS * oo + 4u];
-					w2[u] = tb[GYS_EV6_WORDS * oo + 5u];
-				} else if (DMA) {
-					in[u] = (uint32_t)(g + u) * T + tid < rem; // (the words are read from the wave's LDS area below, behind the requests of all four slots)
-					w0[u] = w1[u] = w2[u] = 0;
+					w1[u] = tb[ob / 4u + 4u];
+					w2[u] = tb[ob / 4u + 5u];
 				} else {
-					// the tile's base is uniform and an event's byte offset inside the tile fits 32 bits: written so, the three loads share ONE
-					// 32-bit offset register (scalar base + offset + immediate) instead of a 64-bit address each.  Round 6: the offset is
-					// 24 tid (kept) + 24 T (g + u) (scalar) -- no 32-bit multiply (a quarter-rate instruction) per event
-					const uint32_t ob_raw = tid24 + (uint32_t)(g + u) * (24u * T);
-					in[u] = ob_raw < 24u * rem; // (== o < rem)
-					const uint32_t ob = in[u] ? ob_raw : 0u;
 					const char *const tbb = (const char *)tb;
 					w0[u] = *(const uint64_t *)(tbb + ob);
 					w1[u] = *(const uint64_t *)(tbb + ob + 8u);
 					w2[u] = *(const uint64_t *)(tbb + ob + 16u);
 				}
-			}
-			if (DMA) {
-				// the requests of a group: six full-width 16-byte-per-lane transfers into the wave's area.  A 16-byte piece may reach 8 bytes past the
-				// tile's last event (into the next tile's or segment's events): it is requested as long as it lies inside the batch; the batch's
-				// very last event (its last piece would pass the buffer's end when n is odd) is re-read below
-				auto dma_issue = [&](uint32_t gg) {
-					const char *const tbb = (const char *)tb;
-					const uint64_t left_b = (p.n - t0) * 24ull;
-					const uint32_t lim = left_b > 0xFFFFFFF0ull ? 0xFFFFFFF0u : (uint32_t)left_b;
-#pragma unroll
-					for (uint32_t u = 0; u < 4u; ++u) { // the first KB of each slot: lane l asks for bytes [16 l, 16 l + 16) of the wave's 1536
-						const uint32_t bo = 24u * ((gg + u) * T + (tid & ~63u)) + 16u * lane;
-						GYS_DMA16(tbb + (bo + 16u <= lim ? bo : 0u), dma_ws + 1024u * u);
-					}
-#pragma unroll
-					for (uint32_t t2 = 0; t2 < 2u; ++t2) { // the last 512 bytes of two slots: lanes 0..31 slot 2 t2, lanes 32..63 slot 2 t2 + 1
-						const uint32_t u = 2u * t2 + (lane >> 5);
-						const uint32_t bo = 24u * ((gg + u) * T + (tid & ~63u)) + 1024u + 16u * (lane & 31u);
-						GYS_DMA16(tbb + (bo + 16u <= lim ? bo : 0u), dma_ws + 4096u + 1024u * t2);
-					}
-				};
-				if (!GYS_EV_DMA_AHEAD || g == 0) dma_issue((uint32_t)g); // (the tile's first group: behind the tile-top barrier)
-				GYS_DMA_WAIT();
-				__builtin_amdgcn_wave_barrier();
-#pragma unroll
-				for (uint32_t u = 0; u < 4u; ++u) {
-					w0[u] = *(const uint64_t *)(dma_ws + dma_a[0] + u * dma_s[0]);
-					w1[u] = *(const uint64_t *)(dma_ws + dma_a[1] + u * dma_s[1]);
-					w2[u] = *(const uint64_t *)(dma_ws + dma_a[2] + u * dma_s[2]);
-					const uint32_t o = (uint32_t)(g + u) * T + tid;
-					if (t0 + o + 1u == p.n) { // (one lane of one workgroup per batch)
-						w0[u] = tb[3u * o];
-						w1[u] = tb[3u * o + 1u];
-						w2[u] = tb[3u * o + 2u];
-					}
-				}
-				GYS_OPAQUE_LOADED4(w0); // (the words are in registers: the area is free again)
-				GYS_OPAQUE_LOADED4(w1);
-				GYS_OPAQUE_LOADED4(w2);
-				__builtin_amdgcn_wave_barrier();
-				// the NEXT group's requests go out now and run under this group's work: software pipelining with one buffer and no registers
-				if (GYS_EV_DMA_AHEAD && g + 4 < TPT && (uint32_t)(g + 4) * T < rem) dma_issue((uint32_t)g + 4u);
 			}
 			// (all twelve words pass through one opaque statement: the four events' loads are issued before the first word is used -- the
 			// scheduler otherwise waits for event 0 and starts on its fields before the loads of events 1..3 are even issued.  Requesting
@@ -1253,7 +1194,7 @@ __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), 4) void k_resp_host(RespHost
 					if (ok[u] && local[u] != GYS_NOSLOT && (local[u] & GYS_LOCAL_GROUP)) {
 						uint32_t e32, e128[4] = {0u, 0u, 0u, 0u}, lc = 0, sl = 0;
 						if (V6) {
-							const uint32_t o = (uint32_t)(g + u) * T + tid;
+							const uint32_t o = (uint32_t)g * T + (uint32_t)u * S + tid;
 							const uint64_t x0 = tb[GYS_EV6_WORDS * o], x1 = tb[GYS_EV6_WORDS * o + 1u];
 							e128[0] = (uint32_t)x0; e128[1] = (uint32_t)(x0 >> 32); e128[2] = (uint32_t)x1; e128[3] = (uint32_t)(x1 >> 32);
 							e32 = ip6_embedded_v4(e128);
@@ -1357,7 +1298,7 @@ __global__ __launch_bounds__(GYS_RESP_THREADS(TPT), 4) void k_resp_host(RespHost
 				for (uint32_t u = 0; u < 4u; ++u) {
 					if (!((rare >> u) & 1u)) continue;
 					// (the event this lane holds in place u of the group: see the load above)
-					const uint32_t o = ((uint32_t)g + u) * T + tid;
+					const uint32_t o = (uint32_t)g * T + u * S + tid;
 					uint32_t idx, rank;
 					if (V6) {
 						const uint64_t a0 = tb[GYS_EV6_WORDS * o], a1 = tb[GYS_EV6_WORDS * o + 1u], d0 = tb[GYS_EV6_WORDS * o + 2u], d1 = tb[GYS_EV6_WORDS * o + 3u],
