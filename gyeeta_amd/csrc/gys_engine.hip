@@ -1360,7 +1360,7 @@ void resp_launch_huge(gys_ctx *c, const RespBatch &b)
 	q.chunk_off = c->huge_chunk_off;
 	q.tail = c->huge_tail;
 	q.tail_count = c->merge_count + FIN_HUGE_TAIL;
-	q.tail_cap = 1u << 20;
+	q.tail_cap = GYS_HB_TAIL_CAP;
 	q.maxent = c->huge_maxent;
 	q.fb_list = c->huge_fb_list;
 	q.fb_count = c->merge_count + FIN_HUGE_FB;
@@ -2378,7 +2378,7 @@ try {
 		ALLOC(c->huge_acc, (uint64_t)c->huge_maxent * GYS_HB_ACC);
 		ALLOC(c->huge_bm, (uint64_t)c->huge_maxent * GYS_BM_WORDS);
 		ALLOC(c->huge_chunk_off, (uint64_t)c->huge_maxent + 1);
-		ALLOC(c->huge_tail, (uint64_t)1 << 20);
+		ALLOC(c->huge_tail, (uint64_t)GYS_HB_TAIL_CAP);
 		ALLOC(c->huge_tb_list, (uint64_t)c->huge_maxent);
 		ALLOC(c->huge_fb_list, std::min<uint64_t>(S, B / (GYS_MERGE_CLASS1 - c->pend_cap) + 1) + 1);
 		HIPCHK(hipFuncSetAttribute((const void *)k_huge_count, hipFuncAttributeMaxDynamicSharedMemorySize, GYS_HB_BINS * 4));
@@ -5058,6 +5058,24 @@ try {
 	hipLaunchKernelGGL(k_read_events, dim3((uint32_t)((nevents + per_wg - 1) / per_wg)), dim3(1024), 0, c->stream, (const uint64_t *)d_ev24, nevents, per_wg,
 			   (uint64_t *)c->counters + 31);
 	HIPCHK(hipGetLastError());
+	return GYS_OK;
+} GYS_CATCH_ALL
+
+// the large-key path's list lengths as the last response batch left them (tests: which route did the entries take)
+int gys_debug_huge_counts(gys_ctx *c, uint32_t out[8])
+try {
+	GYS_ENTER(c);
+	if (!c || !out) return GYS_ERR_INVAL;
+	memset(out, 0, 8 * sizeof(uint32_t));
+	if (!c->merge_count.p) return GYS_OK; // (no t-digests: no merge lists)
+	uint32_t w[FIN_NWORDS];
+	HIPCHK(hipMemcpyAsync(w, c->merge_count, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	out[0] = w[FIN_HUGE];
+	out[1] = w[FIN_HUGE_FB];
+	out[2] = w[FIN_HUGE_NENT];
+	out[3] = w[FIN_HUGE_TAIL];
+	out[4] = w[FIN_HUGE_TB];
 	return GYS_OK;
 } GYS_CATCH_ALL
 

@@ -24,6 +24,7 @@ namespace gys {
 #endif                          // whatever its size: the C5 window paid 5 x 10^7 of them, 4.8 ms; eight times the values per chunk, an eighth of the adds)
 #define GYS_HB_TAIL_LDS 16384u  // tail values (>= GYS_HB_BINS) one entry may carry on this path (sorted in LDS): tier B of k_huge_merge
 #define GYS_HB_TAIL_A 512u      // ... tier A (two workgroups per CU)
+#define GYS_HB_TAIL_CAP (1u << 20) // places of the global tail list (all entries of a pool round together); more tail values than that in one round: every entry of the round takes the fallback
 #define GYS_HB_VEC 2u           // k_huge_count: 16-byte pieces a thread requests before it takes their values
 #ifndef GYS_HB_WAVES
 #define GYS_HB_WAVES 8            // waves per SIMD k_huge_count is compiled for

@@ -997,6 +997,14 @@ class SketchEngine:
         capi.check(self.L.gys_get_counters(self.h, C.byref(out)))
         return {n: getattr(out, n) for n, _ in out._fields_}
 
+    def huge_counts(self):
+        """which way the large keys (more than 16 384 values in one call) of the last response batch went: 'huge' of them in the batch,
+        'fallback' of those merged by the one-workgroup kernel; of the batch's last pool round: 'pool_entries', 'tail_values' (values
+        >= 16 384 ms put on the tail list, counted on past its capacity) and 'tier_b' (entries the 512-value merge tier handed on)"""
+        out = (C.c_uint32 * 8)()
+        capi.check(self.L.gys_debug_huge_counts(self.h, out))
+        return {"huge": out[0], "fallback": out[1], "pool_entries": out[2], "tail_values": out[3], "tier_b": out[4]}
+
     # ---------------------------------------------------------------- measurement helpers
     def profile(self, on=True):
         capi.check(self.L.gys_profile_enable(self.h, 1 if on else 0))

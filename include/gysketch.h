@@ -1008,6 +1008,14 @@ int gys_profile_names(gys_ctx *ctx, char *buf, size_t buflen); /* comma separate
 /* PMC calibration helper: reads nevents 24-byte events with the access pattern of the event kernel (3 x 8-B loads per thread at a 24-B
  * stride) and does nothing else -- FETCH_SIZE of this launch vs the known 24 B x nevents (tools/calibrate_fetch.py) */
 int gys_debug_read_events_dev(gys_ctx *ctx, const void *d_ev24, uint64_t nevents);
+/* test witness of the large-key t-digest path (keys that bring more than 16 384 values in one call): waits for the work queued so far and
+ * copies the path's list lengths.  out[0] large keys of the last response batch, out[1] of them handed to the one-workgroup fallback
+ * (both counted over the whole batch); out[2] pool entries, out[3] values >= 16 384 ms put on the tail list (counts on past its
+ * capacity), out[4] entries the 512-value merge tier handed to the 16 384-value tier -- these three of the batch's LAST pool round
+ * only (an entry the second tier hands on to the fallback is in out[4] and in out[1]).  out[0..2] are cleared at the start of every
+ * response batch; out[3] and out[4] are reset by the path's planning kernel, so they keep their values over batches too small to
+ * hold a large key.  out[5..7] = 0.  Read-only. */
+int gys_debug_huge_counts(gys_ctx *ctx, uint32_t out[8]);
 int gys_gen_resp_events_dev(gys_ctx *ctx, void *d_ev24, uint64_t nevents, uint64_t seed, uint32_t first_host, uint32_t nhosts,
 			    uint32_t svcs_per_host, uint32_t zipf_milli /* 0 = uniform, else s*1000 */, gys_resp_seg *segs_out /* host, nhosts */);
 
