@@ -125,6 +125,18 @@ NO_GROUP = 0xFFFFFFFF
 GROUP_NONE, GROUP_HOST, GROUP_CLUSTER, GROUP_LABEL = 0, 1, 2, 3
 RF_ANY_STATE = 1
 
+
+class TopkEntry(C.Structure):   # gys_topk_entry
+    _fields_ = [("row", C.c_uint32), ("reserved", C.c_uint32), ("value", C.c_double), ("weight", C.c_uint64)]
+
+
+class TopService(C.Structure):   # gys_top_service
+    _fields_ = [("glob_id", C.c_uint64), ("slot", C.c_uint32), ("host_slot", C.c_uint32), ("value", C.c_double), ("total", C.c_uint64)]
+
+
+TOPK_LARGEST, TOPK_SMALLEST = 0, 1
+TOP_QUANTILE, TOP_SHARE_WITHIN, TOP_MISSES, TOP_DISTINCT = 0, 1, 2, 3
+
 SVC_COLS = ["qps5s", "nqry5s", "resp5s", "p95resp5s", "p95resp5m", "nconns", "nactive", "nprocs", "kbin15s", "kbout15s", "sererr", "clierr", "delayus",
             "cpudelus", "iodelus", "vmdelus", "usercpu", "syscpu", "rssmb", "nissue", "state", "issue", "ishttp"]  # GYS_SVC_COL_* in order
 SUMM_COLS = ["nidle", "ngood", "nok", "nbad", "nsevere", "ndown", "totqps", "totaconn", "totkbin", "totkbout", "totsererr", "nsvc", "nactive"]  # GYS_SUMM_COL_*
@@ -198,6 +210,7 @@ SIGNATURES = {
     "gys_tdigest_rollup_dev": (C.c_int, [vp, C.c_int, vp]),
     "gys_tdigest_merge_slabs_dev": (C.c_int, [vp, vp, C.c_uint32, vp]),
     "gys_tdigest_slab_quantiles": (C.c_int, [vp, vp, f64p, C.c_uint32, f64p]),
+    "gys_tdigest_slab_quantiles_dev": (C.c_int, [vp, vp, C.c_uint32, f64p, C.c_uint32, vp]),
     "gys_num_clusters": (C.c_uint32, [vp]),
     "gys_scan_distinct_dev": (C.c_int, [vp, vp]),
     "gys_query_distinct": (C.c_int, [vp, C.c_uint64, f64p]),
@@ -238,6 +251,9 @@ SIGNATURES = {
     "gys_query_svcstate_aggr": (C.c_int, [vp, C.POINTER(SvcFilter), C.c_int, u8p, C.c_uint32, C.POINTER(SvcAggrRow), C.c_uint32, u32p]),
     "gys_set_service_groups": (C.c_int, [vp, u64p, u32p, C.c_uint32]),
     "gys_rollup_filtered_dev": (C.c_int, [vp, C.POINTER(SvcFilter), C.c_uint32, C.c_int, C.c_int, C.c_uint64, C.POINTER(RollupRow), C.c_uint32, u32p, vp, vp, vp]),
+    "gys_topk_dev": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_uint64, C.c_int, C.c_uint32, C.POINTER(TopkEntry), u32p, u64p]),
+    "gys_top_services": (C.c_int, [vp, C.c_int, C.c_double, C.c_int, C.c_uint64, C.POINTER(SvcFilter), C.c_uint32, C.c_uint64, C.c_int, C.c_uint32,
+                                   C.POINTER(TopService), u32p, u64p]),
     "gys_hist_rollup_level_dev": (C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, vp]),
     "gys_hist_rollup_filtered_dev": (C.c_int, [vp, C.POINTER(SvcFilter), C.c_uint32, C.c_int, C.c_int, C.c_uint64, C.POINTER(RollupRow), C.c_uint32, u32p, vp]),
     "gys_hist_rollup_period_dev": (C.c_int, [vp, C.c_int, C.c_int64, C.c_int64, C.c_uint64, vp, C.POINTER(C.c_int)]),

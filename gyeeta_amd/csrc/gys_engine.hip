@@ -41,6 +41,7 @@
 #include "gys_rollsel.hpp"
 #include "gys_svcdel.hpp"
 #include "gys_tdrank.hpp"
+#include "gys_topk.hpp"
 
 using namespace gys;
 
@@ -381,6 +382,9 @@ struct gys_ctx {
 	DevBuf<uint64_t> topn_metric;
 	// filtered multi-host listener-state query (gys_svcquery.hpp): scratch, grow-only
 	DevBuf<unsigned long long> q_cand_key, q_out_keys, q_cnt;
+	// rankings on sketch results (gys_topk.hpp): the tie rows' keys; gys_top_services' metric column, totals and below(x) (grow-only)
+	DevBuf<unsigned long long> q_tie_key, top_weight;
+	DevBuf<double> top_col, top_below;
 	DevBuf<uint32_t> q_cand_slot, q_misc, q_host_mask, q_slot_list;
 	DevBuf<int32_t> q_set;
 	DevBuf<uint8_t> q_out_rows;
@@ -5132,3 +5136,4 @@ try {
 #include "gys_svcquery_host.hpp"
 #include "gys_rollup_host.hpp"
 #include "gys_rollsel_host.hpp"
+#include "gys_topk_host.hpp"

@@ -19,6 +19,8 @@
 //              their minimum / maximum on the way; DPP reductions join the lanes.  Staged words are value << GYS_ROW_BITS | ...: the value counts.
 //              No fold is needed: td_minmax without it lies between the overall and the merged extreme (k_fold and the merges only ever widen
 //              it by values of the buffer), so min(td_minmax.x, min P) is the overall minimum either way.
+// And the quantile direction for slabs, k_td_slab_quantiles (gys_tdigest_slab_quantiles_dev), at the end of this file: the same shape, the
+// arithmetic of the one-slab host call gys_tdigest_slab_quantiles.
 #pragma once
 
 #include <type_traits>
@@ -257,6 +259,109 @@ __global__ __launch_bounds__(GYS_TR_NT, TP >= 8u ? 5 : (TP >= 4u ? 6 : 8)) void 
 			q.below[(size_t)(mem - q.first) * q.nt + lane] = N == 0ull ? (double)nb : r + (double)nb;
 		}
 		if (q.total && lane == 0u) q.total[mem - q.first] = N + npend;
+	}
+}
+
+// ---- quantiles of any number of slabs (gys_tdigest_slab_quantiles_dev): k_td_ranks<1, .>'s shape the other way round.  A wave per slab,
+// grid-stride; lane l holds clusters l + 64 k and their exact integer weight prefix; the centres c_k = (double)W_k + (double)cnt_k * 0.5 are
+// those of the one-slab host call (gys_tdigest_slab_quantiles), which adds the weights up in doubles: the same numbers while a slab weighs
+// less than 2^53.  Per quantile the ballots of "non-empty and t < c_k" give the first such cluster f (lowest bit) and, with the ballots of
+// "non-empty", the last non-empty cluster before it (highest bit below f; the last of all when there is no f): lane t keeps the pair of
+// quantile t, fetches the two clusters from the lanes that hold them and does the host call's double operations in its order.  Loads, wave
+// operations and the slab's output row only: no LDS, no atomics, outputs need not be zeroed.
+struct TdSlabQP {
+	const gys_tdigest_slab *in;
+	uint32_t n, nq;         // slab i writes out[i * nq .. + nq)
+	double q[GYS_TR_MAXT];
+	double *out;
+};
+
+__global__ __launch_bounds__(GYS_TR_NT) void k_td_slab_quantiles(TdSlabQP q)
+{
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+	constexpr uint32_t NW = GYS_TR_NT / 64u;
+	const uint32_t stride = gridDim.x * NW;
+	for (uint32_t mem = blockIdx.x * NW + wave; mem < q.n; mem += stride) {
+		uint64_t cn[GYS_TR_ROWS], sm[GYS_TR_ROWS];
+#pragma unroll
+		for (uint32_t k = 0; k < GYS_TR_ROWS; ++k) {
+			const uint32_t j = lane + 64u * k;
+			cn[k] = 0;
+			sm[k] = 0;
+			if (j < GYS_TD_NB) {
+				cn[k] = q.in[mem].cnt[j];
+				sm[k] = (uint64_t)q.in[mem].sum[j];
+			}
+		}
+		const long long vmn = q.in[mem].vmin, vmx = q.in[mem].vmax;
+		unsigned long long ne[GYS_TR_ROWS];
+		uint64_t pfx[GYS_TR_ROWS], N = 0;
+		double cc[GYS_TR_ROWS];
+#pragma unroll
+		for (uint32_t k = 0; k < GYS_TR_ROWS; ++k) {
+			ne[k] = __ballot(cn[k] != 0);
+			const uint64_t inc = wave_incl_scan_u64(cn[k]);
+			pfx[k] = N + inc;
+			N += tr_last_u64(inc);
+			cc[k] = (double)(pfx[k] - cn[k]) + (double)cn[k] * 0.5;
+		}
+		const double dN = (double)N;
+		// ---- per quantile: f = the first non-empty cluster with t < c_f (-1: none), pv = the last non-empty cluster before it (-1: f is the first)
+		int my_f = -1, my_p = -1;
+		double my_t = 0.0;
+		for (uint32_t t = 0; t < q.nq; ++t) {
+			const double qv = q.q[t], qq = qv < 0.0 ? 0.0 : (qv > 1.0 ? 1.0 : qv), tq = qq * dN;
+			int f = -1, pv = -1;
+#pragma unroll
+			for (uint32_t k = 0; k < GYS_TR_ROWS; ++k) {
+				const unsigned long long lt = __ballot(cn[k] != 0 && tq < cc[k]);
+				if (f < 0 && lt) f = (int)(64u * k) + __ffsll((long long)lt) - 1;
+			}
+#pragma unroll
+			for (uint32_t k = 0; k < GYS_TR_ROWS; ++k) {
+				const int base = (int)(64u * k);
+				unsigned long long m = ne[k];
+				if (f >= 0) {
+					if (f < base) m = 0ull;
+					else if (f < base + 64) m &= (1ull << (uint32_t)(f - base)) - 1ull;
+				}
+				if (m) pv = base + 63 - __clzll((long long)m);
+			}
+			if (lane == t) {
+				my_f = f;
+				my_p = pv;
+				my_t = tq;
+			}
+		}
+		// ---- lane t: its two clusters from the lanes that hold them, then the arithmetic of quantile t
+		const uint32_t jf = my_f < 0 ? 0u : (uint32_t)my_f, jp = my_p < 0 ? 0u : (uint32_t)my_p;
+		const uint64_t sf = tr_fetch(sm, jf), cf = tr_fetch(cn, jf), pf = tr_fetch(pfx, jf);
+		const uint64_t sp = tr_fetch(sm, jp), cp = tr_fetch(cn, jp), pp = tr_fetch(pfx, jp);
+		if (lane < q.nq) {
+			double r = 0.0;
+			if (N) {
+				double prev_mean = 0.0, prev_c = 0.0;
+				if (my_p >= 0) {
+					prev_mean = (double)(int64_t)sp / (double)cp;
+					prev_c = (double)(pp - cp) + (double)cp * 0.5;
+				}
+				if (my_f >= 0) {
+					const double mean = (double)(int64_t)sf / (double)cf, cf_c = (double)(pf - cf) + (double)cf * 0.5;
+					if (my_p < 0) {
+						const double lo = (double)vmn;
+						r = cf_c <= 0.0 ? mean : lo + (mean - lo) * (my_t / cf_c);
+					} else {
+						r = prev_mean + (mean - prev_mean) * ((my_t - prev_c) / (cf_c - prev_c));
+					}
+				} else {
+					const double hi = (double)vmx, span = dN - prev_c;
+					r = span <= 0.0 ? hi : prev_mean + (hi - prev_mean) * ((my_t - prev_c) / span);
+				}
+				r = floor(r + 0.5);
+			}
+			q.out[(size_t)mem * q.nq + lane] = r;
+		}
 	}
 }
 

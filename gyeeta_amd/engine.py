@@ -509,6 +509,46 @@ class SketchEngine:
         capi.check(self.L.gys_tdigest_slab_quantiles(self.h, C.c_void_p(dev_slab.data_ptr() + index * C.sizeof(capi.TDigestSlab)), qa, len(qs), out))
         return list(out)
 
+    def slab_quantiles_dev(self, dev_slabs, n, qs):
+        """quantiles of n slabs on the device in one launch (gys_tdigest_slab_quantiles_dev): (device tensor [n][len(qs)] float64, the same as
+        numpy) -- every entry the bits slab_quantiles gives for that slab and quantile"""
+        qa = (C.c_double * max(len(qs), 1))(*qs)
+        out = self.torch.empty((max(n, 1), max(len(qs), 1)), dtype=self.torch.float64, device=self.device)
+        self.order()
+        capi.check(self.L.gys_tdigest_slab_quantiles_dev(self.h, C.c_void_p(dev_slabs.data_ptr()), n, qa, len(qs), C.c_void_p(out.data_ptr())))
+        self.sync()
+        return out, out[:n].cpu().numpy()
+
+    TOPK_DT = np.dtype([("row", "<u4"), ("reserved", "<u4"), ("value", "<f8"), ("weight", "<u8")])
+    TOPSVC_DT = np.dtype([("glob_id", "<u8"), ("slot", "<u4"), ("host_slot", "<u4"), ("value", "<f8"), ("total", "<u8")])
+
+    def topk(self, col, k, order=capi.TOPK_LARGEST, stride=1, rows=None, weight=None, min_weight=0, nrows=None):
+        """exact top-k of a device column of doubles (gys_topk_dev; "Top-k" in gysketch.h): col = torch float64 device tensor, rows = torch
+        int32 device tensor of distinct row numbers or None (rows 0 .. nrows - 1; nrows defaults to col.numel() // stride), weight = torch
+        int64 device tensor indexed by row or None.  -> (entries as a numpy TOPK_DT array, in order; number of eligible rows)"""
+        if nrows is None:
+            nrows = rows.numel() if rows is not None else col.numel() // max(stride, 1)
+        out = (capi.TopkEntry * max(k, 1))()
+        nout, nel = C.c_uint32(), C.c_uint64()
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self.order()
+        capi.check(self.L.gys_topk_dev(self.h, ptr(col), stride, nrows, ptr(rows), ptr(weight), int(min_weight), order, k, out, C.byref(nout), C.byref(nel)))
+        return np.frombuffer(out, dtype=self.TOPK_DT, count=nout.value).copy(), nel.value
+
+    def top_services(self, metric, param=0.0, k=10, order=capi.TOPK_LARGEST, level=-1, tusec=0, min_total=0, terms=None, group_oper=(), top_oper="and",
+                     machine_ids=None, svcids=None, clusters=None, any_state=False, filtered=None):
+        """the service ranking in one call (gys_top_services): metric = capi.TOP_*, the filter arguments of rollup_filtered (no filter argument
+        at all, or filtered=False: every registered service).  -> (entries as a numpy TOPSVC_DT array, in order; number of eligible services)"""
+        if filtered is None:
+            filtered = bool(terms or machine_ids or clusters or any_state) or svcids is not None
+        f, keep = self._svc_filter(terms, group_oper, top_oper, machine_ids, svcids, clusters)
+        out = (capi.TopService * max(k, 1))()
+        nout, nel = C.c_uint32(), C.c_uint64()
+        self.order()
+        capi.check(self.L.gys_top_services(self.h, metric, float(param), level, int(tusec), C.byref(f) if filtered else None, capi.RF_ANY_STATE if any_state else 0,
+                                           int(min_total), order, k, out, C.byref(nout), C.byref(nel)))
+        return np.frombuffer(out, dtype=self.TOPSVC_DT, count=nout.value).copy(), nel.value
+
     def hist_percentiles(self, glob_id, pcts, which=1):
         pd = (capi.HistData * len(pcts))()
         for i, p in enumerate(pcts):

@@ -479,6 +479,14 @@ int gys_tdigest_rollup_dev(gys_ctx *ctx, int scope, gys_tdigest_slab *d_out);
 int gys_tdigest_merge_slabs_dev(gys_ctx *ctx, const gys_tdigest_slab *d_in, uint32_t n, gys_tdigest_slab *d_out);
 /* quantiles q[i] (0..1) of one DEVICE slab into the HOST array out (same interpolation and rounding as gys_query_quantiles) */
 int gys_tdigest_slab_quantiles(gys_ctx *ctx, const gys_tdigest_slab *d_slab, const double *q, uint32_t nq, double *out);
+/* the same for nslabs DEVICE slabs in one launch: d_out[i * nq + t] (DEVICE) equals, bit for bit, what gys_tdigest_slab_quantiles(ctx,
+ * d_slabs + i, q + t, 1, ...) returns -- the same clamp of q to 0 .. 1, the same interpolation between the centres W_k + cnt_k / 2 of the
+ * non-empty clusters, vmin / vmax at the ends, floor(r + 0.5), 0 for an empty slab.  The one-slab call adds the weights before a cluster up
+ * in doubles, this one in exact integers converted once: the same numbers while a slab weighs less than 2^53 (every slab the engine can
+ * produce is far below that).  q is a HOST array of nq = 1 .. 16 quantiles (GYS_ERR_INVAL otherwise).  Asynchronous on the context stream
+ * (gys_sync); no state is modified. */
+int gys_tdigest_slab_quantiles_dev(gys_ctx *ctx, const gys_tdigest_slab *d_slabs, uint32_t nslabs, const double *q /* HOST */, uint32_t nq,
+				   double *d_out /* DEVICE [nslabs * nq] */);
 /* below(x) ("Ranks" above; P is empty, the extremes are the slab's) of nslabs DEVICE slabs -- the host, cluster and global roll-ups, the rows
  * of gys_rollup_filtered_dev, a cross-rank merge: d_below[i * nt + t], d_total[i] = the slab's weight (DEVICE; d_total may be NULL).
  * Asynchronous on the context stream. */
@@ -793,6 +801,59 @@ enum { GYS_GROUP_NONE = 0, GYS_GROUP_HOST = 1, GYS_GROUP_CLUSTER = 2, GYS_GROUP_
  * gys_tdigest_merge_slabs_dev / gys_hll_merge_files_dev. */
 int gys_rollup_filtered_dev(gys_ctx *ctx, const gys_svc_filter *filter, uint32_t flags, int group_by, int hll_level, uint64_t tusec,
 			    gys_rollup_row *rows, uint32_t maxrows, uint32_t *nrows, gys_tdigest_slab *d_slabs, uint8_t *d_regs, double *d_est);
+
+/* -------------------------------------------------------------------------------------------------------------------
+ * Top-k: WHICH services or groups a scan's results name -- "the 100 services with the worst p99", "the 50 with the lowest share inside
+ * 200 ms", "the 20 hosts with the most distinct clients" -- without copying a column of one double per service to the host and sorting it
+ * there.  Builder-defined.  The definition is FROZEN.  For a DEVICE column d_col of doubles:
+ *   1. The value of row r is d_col[r * stride] (stride = doubles between rows, >= 1).
+ *   2. The candidate rows are 0 .. nrows - 1 (d_rows NULL), or the nrows DISTINCT row numbers at d_rows (DEVICE), in any order.
+ *   3. A candidate r is ELIGIBLE when its value is not a NaN and, if d_weight (DEVICE, indexed by row number) is given, d_weight[r] >= min_weight.
+ *   4. Values compare as real numbers: -0.0 equals +0.0, -infinity is below and +infinity above every finite value.
+ *   5. GYS_TOPK_LARGEST: larger value first, then the LOWER row number.  GYS_TOPK_SMALLEST: smaller value first, then the lower row number.
+ *   6. out (HOST) holds the first min(k, eligible) rows of that total order, in that order: row, value = the column's stored bits (a -0.0
+ *      stays a -0.0), weight = d_weight[r], or 0 without d_weight.  *nout = the entries written, *neligible (may be NULL) = the eligible rows.
+ * The result is a function of the SET of candidate rows alone: the order of d_rows (for a filter's member list, whatever the device's atomics
+ * left) does not change a bit of it.  k == 0 writes nothing and still reports *neligible.  GYS_ERR_INVAL: NULL column or nout, stride 0, an
+ * unknown order, k > 0 with out == NULL.  One small read of the counts inside the call, then the entries; no state is modified.
+ * Cost is linear in nrows whatever the values: a column of 10^7 equal values is a legal input (the ties are cut by row number on the device).
+ * ACROSS RANKS there is no collective of its own: the top-k of the union is the top-k of the ranks' own top-k lists (rows made global by
+ * the caller), so every rank runs the call and the k entries per rank are gathered and ordered again.
+ * GROUPS need no call of their own -- a roll-up, the slabs' figures, the selection.  "The 20 hosts with the worst p99":
+ *     gys_tdigest_rollup_dev(ctx, GYS_ROLLUP_HOST, d_slabs);                                      one slab per host slot
+ *     q = 0.99;  gys_tdigest_slab_quantiles_dev(ctx, d_slabs, nhosts, &q, 1, d_p99);              d_p99[host slot]
+ *     gys_tdigest_slab_ranks_dev(ctx, d_slabs, nhosts, &x, 1, d_below, d_total);                  d_total[host slot]: hosts without data drop out
+ *     gys_topk_dev(ctx, d_p99, 1, nhosts, NULL, d_total, 1, GYS_TOPK_LARGEST, 20, out, &n, NULL); out[i].row = the host slot
+ * and likewise on the rows of gys_rollup_filtered_dev (row = the index into its rows[]) and on its d_est array. */
+typedef struct {
+	uint32_t row, reserved;
+	double value;
+	uint64_t weight;
+} gys_topk_entry; /* 24 bytes */
+enum { GYS_TOPK_LARGEST = 0, GYS_TOPK_SMALLEST = 1 };
+int gys_topk_dev(gys_ctx *ctx, const double *d_col, uint32_t stride, uint32_t nrows, const uint32_t *d_rows, const uint64_t *d_weight,
+		 uint64_t min_weight, int order, uint32_t k, gys_topk_entry *out /* HOST [k] */, uint32_t *nout, uint64_t *neligible);
+
+/* The service ranking in one call: the scan, the filter and the selection.  value is, bit for bit, that service's entry of the scan at the
+ * same moment -- for the two rank metrics one division or one subtraction applied to it; total = the digest's total weight as
+ * gys_scan_ranks_dev reports it (0 for GYS_TOP_DISTINCT); level and tusec are read by GYS_TOP_DISTINCT only.
+ * CANDIDATES: with a filter exactly the members gys_rollup_filtered_dev selects for the same filter and flags (GYS_RF_ANY_STATE or 0) with
+ * GYS_GROUP_NONE; filter NULL: every registered slot that is not free.  ELIGIBLE: total >= max(min_total, 1) for the three digest metrics;
+ * every candidate for GYS_TOP_DISTINCT (min_total is not used).  Order and ties: "Top-k" above with row = service slot.
+ * GYS_ERR_STATE without enable_tdigest (digest metrics), without svc_hll_p (GYS_TOP_DISTINCT) or without svc_hll_levels (a level);
+ * GYS_ERR_INVAL for an unknown metric, order, level or flag, NULL nout, k > 0 with out == NULL. */
+enum { GYS_TOP_QUANTILE = 0,     /* param = q: the service's gys_scan_quantiles_dev value */
+       GYS_TOP_SHARE_WITHIN = 1, /* param = x ms (converted to int64_t): below(x) / (double)total */
+       GYS_TOP_MISSES = 2,       /* param = x ms: (double)total - below(x), the responses slower than x */
+       GYS_TOP_DISTINCT = 3 };   /* the distinct-flow estimate; level -1 = open window, 0 .. 3 = that level at tusec */
+typedef struct {
+	uint64_t glob_id;
+	uint32_t slot, host_slot;
+	double value;
+	uint64_t total;
+} gys_top_service; /* 32 bytes */
+int gys_top_services(gys_ctx *ctx, int metric, double param, int level, uint64_t tusec, const gys_svc_filter *filter /* NULL = every registered service */,
+		     uint32_t flags, uint64_t min_total, int order, uint32_t k, gys_top_service *out /* HOST [k] */, uint32_t *nout, uint64_t *neligible);
 
 /* -------------------------------------------------------------------------------------------------------------------
  * Group response-time histograms of the CLOSED windows for the four levels (gys_config.enable_levels; GYS_ERR_STATE when it is 0, and for
