@@ -34,6 +34,7 @@
 #include "gys_rollup.hpp"
 #include "gys_groups.hpp"
 #include "gys_resp_plan.hpp"
+#include "gys_hostlst.hpp"
 #include "gys_hllroll.hpp"
 #include "gys_histroll.hpp"
 #include "gys_huge.hpp"
@@ -88,44 +89,6 @@ struct ProfEntry {
 };
 
 inline uint64_t align_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
-
-// host mirror of one host's listener sub-table (the device copy lives in the table / list pools, see k_resp_host)
-struct HostListeners {
-	std::vector<uint64_t> tbl;   // open addressing, entries (netns:32|port:16) << 16 | local index, ~0 = free
-	std::vector<uint32_t> slots; // local index -> service slot
-	std::vector<uint32_t> all_slots; // every service slot ever registered for the host (queries)
-	std::vector<uint64_t> keys;  // local index -> (netns:32|port:16)
-	uint32_t tbl_off = 0, tbl_cap = 0, lst_off = 0;
-	bool on_device = false;
-	bool overflow = false;       // more listeners than the LDS path supports (or pools exhausted): general pipeline only
-	// A host with more than GYS_HOST_MAX_LOCAL listeners is cut into `sub.size()` PARTS (a power of two): a listener belongs to part
-	// host_part_of(key48), every part has a sub-table of its own (the members above are then unused) and its own descriptor
-	// hdesc[sub_desc + part]; k_resp_host runs one workgroup per (segment, part), each resolving only its part's events.
-	std::vector<HostListeners> sub;
-	uint32_t sub_desc = 0;
-	// Keys with CANDIDATES (host level; a part's sub-table only holds the entries): a (netns, port) key whose listener is bound to an address, or
-	// that has more than one listener.  chain[key48] = its listeners in registration order; `cands` = the device records of all chains
-	// (a region of the candidate pool, rebuilt when a chain changes); a key that is not in `chain` has ONE any-address listener and its
-	// sub-table entry names the local index directly, as before.
-	struct LAddr {
-		uint32_t ip32 = 0;
-		uint32_t ip128[4] = {0, 0, 0, 0};
-		bool any = true;
-	};
-	struct ChainEnt {
-		uint32_t slot;
-		LAddr a;
-	};
-	std::unordered_map<uint64_t, std::vector<ChainEnt>> chain;
-	std::vector<ListenerCand> cands;
-	std::unordered_map<uint64_t, uint32_t> cand_first; // key48 -> first record of its chain in `cands`
-	uint32_t cand_off = 0, cand_cap = 0;
-	bool dirty = false;                                 // a chain changed: tables and candidate region are rebuilt at the end of the registration call
-	std::unordered_map<uint64_t, uint32_t> okey;        // overflow hosts (no sub-tables): key48 -> slot of the key's one any-address listener
-};
-
-#define GYS_HOST_MAX_LOCAL 2048u // listeners per sub-table the LDS path supports (32 KB LDS table + 48 KB per-key areas + the tile image)
-#define GYS_HOST_MAX_PARTS 16u   // ... and parts per host: up to 32768 listeners per host on the host-local path
 
 struct ArenaLayout {
 	uint64_t off_hll8, off_u32, n_u32, off_i64sum, n_i64sum, off_i64max, n_i64max, total;
@@ -557,50 +520,7 @@ int check_owner(gys_ctx *c, const uint8_t machine_id[16])
 	return GYS_OK;
 }
 
-uint32_t next_pow2(uint64_t v)
-{
-	uint64_t p = 1;
-	while (p < v) p <<= 1;
-	return (uint32_t)p;
-}
-
-// ---- per-host listener sub-tables (host mirror + device pools), used by k_resp_host
-inline uint64_t host_key48(uint32_t netns, uint16_t port) { return ((uint64_t)netns << 16) | (uint64_t)port; }
-
-int64_t host_tbl_find(const HostListeners &hl, uint64_t key48)
-{
-	if (hl.tbl.empty()) return -1;
-	const uint32_t mask = (uint32_t)hl.tbl.size() - 1;
-	uint32_t h = host_tbl_slot(host_tbl_hash(key48), mask);
-	for (uint32_t probes = 0; probes <= mask; ++probes) {
-		const uint64_t e = hl.tbl[h];
-		if (e == GYS_HOST_TBL_EMPTY) return -1;
-		if ((e >> 16) == key48) return (int64_t)h;
-		h = (h + 1) & mask;
-	}
-	return -1;
-}
-
-// `local`: a local index, or GYS_LOCAL_GROUP | first candidate of the key's chain
-void host_tbl_put(HostListeners &hl, uint64_t key48, uint32_t local)
-{
-	const uint32_t mask = (uint32_t)hl.tbl.size() - 1;
-	uint32_t h = host_tbl_slot(host_tbl_hash(key48), mask);
-	while (hl.tbl[h] != GYS_HOST_TBL_EMPTY) h = (h + 1) & mask;
-	hl.tbl[h] = (key48 << 16) | (uint64_t)local;
-}
-
-inline uint32_t host_part_of(uint64_t key48, uint32_t nparts) { return host_tbl_part(host_tbl_hash(key48), nparts - 1u); }
-
-// capacity of a sub-table of n listeners: a QUARTER full while that is at most GYS_HOST_TBL_SPARSE entries (32 KiB of LDS; 97 % of the
-// events then find their listener in the two entries k_resp_host reads at once), half full above (up to 8192 entries for 4096 listeners)
-#define GYS_HOST_TBL_SPARSE 4096u
-inline uint32_t host_tbl_capacity(size_t n)
-{
-	const uint32_t c4 = next_pow2(std::max<uint64_t>(16, (uint64_t)n * 4));
-	return c4 <= GYS_HOST_TBL_SPARSE ? c4 : std::max<uint32_t>(GYS_HOST_TBL_SPARSE, next_pow2(std::max<uint64_t>(16, (uint64_t)n * 2)));
-}
-
+// ---- per-host listener sub-tables: the device pools of the mirror in gys_hostlst.hpp, used by k_resp_host
 // (re)uploads one sub-table, its slot list and its descriptor hdesc[desc]; regions only ever grow, an outgrown region is abandoned in
 // the pool (geometric growth: the abandoned total stays below the final size, which is what the pool capacity accounts for).
 // Returns false when the pools are exhausted.
@@ -675,133 +595,6 @@ int host_lst_upload(gys_ctx *c, uint32_t host)
 	return GYS_OK;
 }
 
-// one listener into one sub-table (grown and rehashed at half full).  `top`: the host (holder of the chains): with chains around, a
-// rehash has to know which keys' entries name a candidate region -- the whole host is rebuilt at the end of the registration call instead
-void host_tbl_insert(HostListeners &top, HostListeners &t, uint64_t key48, uint32_t slot)
-{
-	const uint32_t local = (uint32_t)t.slots.size();
-	t.slots.push_back(slot);
-	t.keys.push_back(key48);
-	// (the plain entries are kept current in any case -- later listeners of the same call look their key up in them; entries of keys with
-	// candidates are put right by host_rebuild at the end of the call)
-	if (host_tbl_capacity(t.slots.size()) > t.tbl.size()) {
-		t.tbl.assign(host_tbl_capacity(t.slots.size()), GYS_HOST_TBL_EMPTY);
-		for (uint32_t l = 0; l < t.keys.size(); ++l) host_tbl_put(t, t.keys[l], l);
-		if (!top.chain.empty()) top.dirty = true;
-	} else {
-		host_tbl_put(t, key48, local);
-	}
-}
-
-// all tables of a host and its candidate records from the locals and the chains (after a chain changed)
-void host_rebuild(HostListeners &hl)
-{
-	hl.cands.clear();
-	hl.cand_first.clear();
-	auto one = [&](HostListeners &t) {
-		t.tbl.assign(std::max<size_t>(t.tbl.size(), host_tbl_capacity(t.slots.size())), GYS_HOST_TBL_EMPTY);
-		std::unordered_map<uint32_t, uint32_t> local_of; // slot -> local, for the locals of keys with candidates
-		for (uint32_t l = 0; l < t.keys.size(); ++l)
-			if (hl.chain.count(t.keys[l])) local_of[t.slots[l]] = l;
-		for (uint32_t l = 0; l < t.keys.size(); ++l) {
-			const uint64_t key48 = t.keys[l];
-			auto ch = hl.chain.find(key48);
-			if (ch == hl.chain.end()) {
-				host_tbl_put(t, key48, l);
-				continue;
-			}
-			if (hl.cand_first.count(key48)) continue; // (the key's entry was made when its first local came by)
-			const uint32_t first = (uint32_t)hl.cands.size();
-			hl.cand_first[key48] = first;
-			for (size_t k = 0; k < ch->second.size(); ++k) {
-				const HostListeners::ChainEnt &e = ch->second[k];
-				ListenerCand cd{};
-				cd.ip32 = e.a.ip32;
-				cd.flags = (e.a.any ? 1u : 0u) | (k + 1 == ch->second.size() ? 2u : 0u);
-				auto lo = local_of.find(e.slot);
-				cd.local = lo != local_of.end() ? lo->second : 0u;
-				cd.slot = e.slot;
-				memcpy(cd.ip128, e.a.ip128, 16);
-				hl.cands.push_back(cd);
-			}
-			host_tbl_put(t, key48, GYS_LOCAL_GROUP | first);
-		}
-	};
-	if (hl.overflow) { // (no sub-tables: only the records, for the global table)
-		for (auto &kv : hl.chain) {
-			hl.cand_first[kv.first] = (uint32_t)hl.cands.size();
-			for (size_t k = 0; k < kv.second.size(); ++k) {
-				ListenerCand cd{};
-				cd.ip32 = kv.second[k].a.ip32;
-				cd.flags = (kv.second[k].a.any ? 1u : 0u) | (k + 1 == kv.second.size() ? 2u : 0u);
-				cd.slot = kv.second[k].slot;
-				memcpy(cd.ip128, kv.second[k].a.ip128, 16);
-				hl.cands.push_back(cd);
-			}
-		}
-	} else if (hl.sub.empty()) {
-		one(hl);
-	} else {
-		for (HostListeners &t : hl.sub) one(t);
-	}
-	hl.dirty = false;
-}
-
-// cuts the host's listeners into nparts sub-tables (from one table, or from fewer parts); false: no descriptor room / too many parts
-bool host_lst_repartition(gys_ctx *c, HostListeners &hl, uint32_t nparts)
-{
-	if (nparts > GYS_HOST_MAX_PARTS || c->hdesc_ext_used + nparts > c->hdesc_ext_cap) return false;
-	std::vector<std::pair<uint64_t, uint32_t>> all;
-	if (hl.sub.empty()) {
-		for (uint32_t l = 0; l < hl.keys.size(); ++l) all.emplace_back(hl.keys[l], hl.slots[l]);
-	} else {
-		for (const HostListeners &t : hl.sub)
-			for (uint32_t l = 0; l < t.keys.size(); ++l) all.emplace_back(t.keys[l], t.slots[l]);
-	}
-	hl.tbl.clear();
-	hl.slots.clear();
-	hl.keys.clear();
-	hl.sub.assign(nparts, HostListeners{});
-	hl.sub_desc = c->hdesc_ext_used; // (the descriptors of the previous cut are abandoned, like outgrown table regions)
-	c->hdesc_ext_used += nparts;
-	for (const auto &kv : all) host_tbl_insert(hl, hl.sub[host_part_of(kv.first, nparts)], kv.first, kv.second);
-	for (HostListeners &t : hl.sub)
-		if (t.tbl.empty()) t.tbl.assign(16, GYS_HOST_TBL_EMPTY);
-	if (!hl.chain.empty()) hl.dirty = true;
-	return true;
-}
-
-// GY_IP_ADDR of a registered listener (set_ip(uint32_t) / set_ip(unsigned __int128), common/gy_common_inc.h:10673-10692)
-inline HostListeners::LAddr listener_addr(const gys_listener_info &li)
-{
-	HostListeners::LAddr a;
-	a.any = li.is_any_ip != 0;
-	if (a.any) return a;
-	if (li.addr_is_v6) {
-		memcpy(a.ip128, li.addr, 16);
-		a.ip32 = ip6_embedded_v4(a.ip128);
-	} else {
-		memcpy(&a.ip32, li.addr, 4);
-	}
-	return a;
-}
-inline bool laddr_equal(const HostListeners::LAddr &x, const HostListeners::LAddr &y) // GY_IP_ADDR::operator== (common/gy_common_inc.h:10629-10636)
-{
-	return (x.ip32 | y.ip32) ? x.ip32 == y.ip32 : memcmp(x.ip128, y.ip128, 16) == 0;
-}
-
-// the local index that holds `slot` in the table of key48 gets `new_slot` (a listener replaced in place)
-void host_rebind_local(HostListeners &hl, uint64_t key48, uint32_t slot, uint32_t new_slot)
-{
-	if (hl.overflow) return;
-	HostListeners &t = hl.sub.empty() ? hl : hl.sub[host_part_of(key48, (uint32_t)hl.sub.size())];
-	for (uint32_t l = 0; l < t.slots.size(); ++l)
-		if (t.slots[l] == slot && t.keys[l] == key48) {
-			t.slots[l] = new_slot;
-			return;
-		}
-}
-
 // after the host's mirror changed: rebuilds what a changed chain invalidated (tables, candidate records, the global table's entries of the
 // keys with candidates) and uploads the sub-tables
 int host_lst_flush(gys_ctx *c, uint32_t host)
@@ -829,86 +622,10 @@ int host_lst_flush(gys_ctx *c, uint32_t host)
 	return host_lst_upload(c, host);
 }
 
-// slotv: the slot of arr[i] (gys_register_listeners_slots), or nullptr: first_slot + i
-int host_lst_add(gys_ctx *c, uint32_t host, const gys_listener_info *arr, uint32_t n, uint32_t first_slot, const uint32_t *slotv = nullptr)
+// the fresh listeners of one call into the host's mirror (slot_of[i]: the service slot of arr[i]) and on to the device
+int host_lst_add(gys_ctx *c, uint32_t host, const gys_listener_info *arr, uint32_t n, const uint32_t *slot_of)
 {
-	HostListeners &hl = c->host_lst[host];
-	// (a flush that failed after gys_delete_listeners compacted keys / slots left the tables behind the locals: the lookups below need them)
-	if (hl.dirty) host_rebuild(hl);
-	auto new_local = [&](uint64_t key48, uint32_t slot) { // false: the host left the LDS path
-		if (hl.overflow) return false;
-		HostListeners *t = hl.sub.empty() ? &hl : &hl.sub[host_part_of(key48, (uint32_t)hl.sub.size())];
-		while (t->slots.size() >= GYS_HOST_MAX_LOCAL) { // the (part of the) host is full: twice the parts
-			if (!host_lst_repartition(c, hl, hl.sub.empty() ? 2u : (uint32_t)hl.sub.size() * 2u)) {
-				// beyond what the LDS sub-tables take: batches with this host use the general pipeline.  The keys of its any-address
-				// listeners move to a flat map (what a later registration on the same key has to find)
-				hl.overflow = true;
-				auto take = [&](const HostListeners &s) {
-					for (uint32_t l = 0; l < s.keys.size(); ++l)
-						if (!hl.chain.count(s.keys[l])) hl.okey[s.keys[l]] = s.slots[l];
-				};
-				if (hl.sub.empty()) take(hl);
-				else for (const HostListeners &s : hl.sub) take(s);
-				return false;
-			}
-			t = &hl.sub[host_part_of(key48, (uint32_t)hl.sub.size())];
-		}
-		host_tbl_insert(hl, *t, key48, slot);
-		return true;
-	};
-	for (uint32_t i = 0; i < n; ++i) {
-		const uint64_t key48 = host_key48(arr[i].netns, arr[i].port);
-		const uint32_t slot = slotv ? slotv[i] : first_slot + i;
-		const HostListeners::LAddr a = listener_addr(arr[i]);
-		auto ch = hl.chain.find(key48);
-		if (ch != hl.chain.end()) {
-			// insert_or_replace (common/gy_socket_stat.cc:1372, :7779) under operator==(listener, NS_IP_PORT) (gy_socket_stat.h:708-714): the first
-			// listener of the key that is any-address or bound to the new one's address is replaced in place, else the new one goes last
-			bool replaced = false;
-			for (HostListeners::ChainEnt &e : ch->second) {
-				if (e.a.any || laddr_equal(e.a, a)) {
-					host_rebind_local(hl, key48, e.slot, slot);
-					e.slot = slot;
-					e.a = a;
-					replaced = true;
-					break;
-				}
-			}
-			if (!replaced) {
-				ch->second.push_back(HostListeners::ChainEnt{slot, a});
-				if (!hl.overflow) new_local(key48, slot);
-			}
-			hl.dirty = true;
-			continue;
-		}
-		// the key has no candidates: no listener yet, or one any-address listener (which every new listener of the key replaces)
-		uint32_t old_slot = GYS_NOSLOT;
-		if (hl.overflow) {
-			auto it = hl.okey.find(key48);
-			if (it != hl.okey.end()) old_slot = it->second;
-		} else {
-			HostListeners *t = hl.sub.empty() ? &hl : &hl.sub[host_part_of(key48, (uint32_t)hl.sub.size())];
-			const int64_t pos = host_tbl_find(*t, key48);
-			if (pos >= 0) {
-				uint32_t &ls = t->slots[(uint32_t)(t->tbl[(size_t)pos] & (GYS_LOCAL_GROUP - 1u))];
-				old_slot = ls;
-				ls = slot; // (re-registration of a listener tuple rebinds it to the newest slot)
-			}
-		}
-		if (old_slot != GYS_NOSLOT) {
-			if (hl.overflow && a.any) hl.okey[key48] = slot;
-		} else if (!hl.overflow) {
-			new_local(key48, slot);
-			if (hl.overflow && a.any) hl.okey[key48] = slot; // (the host left the LDS path with this very listener)
-		} else if (a.any) {
-			hl.okey[key48] = slot;
-		}
-		if (!a.any) { // bound to an address: the key gets candidates
-			hl.okey.erase(key48);
-			hl.chain[key48].push_back(HostListeners::ChainEnt{slot, a});
-			hl.dirty = true;
-		}
-	}
+	host_lst_insert(c->host_lst[host], arr, n, slot_of, c->hdesc_ext_used, c->hdesc_ext_cap);
 	return host_lst_flush(c, host);
 }
 
@@ -2542,83 +2259,6 @@ try {
 	return GYS_OK;
 } GYS_CATCH_ALL
 
-int gys_register_listeners(gys_ctx *c, const uint8_t machine_id[16], const gys_listener_info *arr_in, uint32_t n_in, uint32_t *first_slot)
-try {
-	GYS_ENTER(c);
-	if (!c || !machine_id || (!arr_in && n_in)) return GYS_ERR_INVAL;
-	uint32_t host;
-	int rc = lookup_host(c, machine_id, &host);
-	if (rc) return rc;
-	// a partha resends NEW_LISTENER after a reconnect: a glob_id the engine already knows keeps its slot (and its histograms, digest,
-	// counters); repeats inside one call are dropped as well, so that the device tables never see the same key twice
-	std::vector<gys_listener_info> fresh;
-	const gys_listener_info *arr = arr_in;
-	uint32_t n = n_in;
-	{
-		std::unordered_set<uint64_t> seen;
-		bool dup = false;
-		for (uint32_t i = 0; i < n_in && !dup; ++i) dup = c->gid_map_h.count(arr_in[i].glob_id) != 0 || !seen.insert(arr_in[i].glob_id).second;
-		if (dup) {
-			seen.clear();
-			for (uint32_t i = 0; i < n_in; ++i)
-				if (!c->gid_map_h.count(arr_in[i].glob_id) && seen.insert(arr_in[i].glob_id).second) fresh.push_back(arr_in[i]);
-			arr = fresh.data();
-			n = (uint32_t)fresh.size();
-		}
-	}
-	if ((uint64_t)c->nsvc + n > c->cfg.max_services) {
-		set_err("max_services exhausted");
-		return GYS_ERR_NOMEM;
-	}
-	if (first_slot) *first_slot = c->nsvc;
-	if (!n) return GYS_OK;
-	std::vector<uint64_t> keys(2 * (size_t)n);
-	for (uint32_t i = 0; i < n; ++i) {
-		if (arr[i].glob_id == GYS_EMPTY_KEY) {
-			set_err("glob_id ~0 is reserved");
-			return GYS_ERR_INVAL;
-		}
-		keys[i] = arr[i].glob_id;
-		keys[n + i] = listener_key(host, arr[i].netns, arr[i].port);
-	}
-	rc = ensure_staging(c, keys.size() * 8, 0);
-	if (rc) return rc;
-	HIPCHK(hipMemcpyAsync(c->dev_staging, keys.data(), keys.size() * 8, hipMemcpyHostToDevice, c->stream));
-	HIPCHK(hipMemcpyAsync(c->svc_gid + c->nsvc, c->dev_staging, (size_t)n * 8, hipMemcpyDeviceToDevice, c->stream));
-	HIPCHK(hipMemsetAsync(c->misc, 0, 4, c->stream));
-	hipLaunchKernelGGL(k_table_insert, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->gid_tbl, (const uint64_t *)c->dev_staging.p, c->nsvc, n, c->misc);
-	hipLaunchKernelGGL(k_table_insert, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->lk_tbl, (const uint64_t *)c->dev_staging.p + n, c->nsvc, n,
-			   c->misc);
-	uint32_t nfail = 0;
-	HIPCHK(hipMemcpyAsync(&nfail, c->misc, 4, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipStreamSynchronize(c->stream));
-	if (nfail) {
-		set_err("key table full (%u inserts failed)", nfail);
-		return GYS_ERR_NOMEM;
-	}
-	{
-		std::vector<uint32_t> hs(n, host);
-		HIPCHK(hipMemcpyAsync(c->svc_host + c->nsvc, hs.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-		HIPCHK(hipStreamSynchronize(c->stream));
-	}
-	rc = host_lst_add(c, host, arr, n, c->nsvc);
-	if (rc) return rc;
-	for (uint32_t i = 0; i < n; ++i) {
-		c->gid_map_h[arr[i].glob_id] = c->nsvc + i;
-		c->host_lst[host].all_slots.push_back(c->nsvc + i);
-		std::array<char, 16> cm{};
-		memcpy(cm.data(), arr[i].comm, 16);
-		c->svc_comm.push_back(cm);
-		c->svc_gid_h.push_back(arr[i].glob_id);
-		c->svc_port_h.push_back(arr[i].port);
-		c->svc_host_h.push_back(host);
-		c->svc_key_h.push_back(host_key48(arr[i].netns, arr[i].port));
-	}
-	c->nsvc += n;
-	c->registry_gen++;
-	return GYS_OK;
-} GYS_CATCH_ALL
-
 // ------------------------------------------------------------------------------------------------ deleting listeners (gys_svcdel.hpp)
 // every per-service array of the context as k_svc_clear segments, with the contents gys_create leaves
 static void svc_clear_segments(gys_ctx *c, std::vector<SvcClearSeg> &segs)
@@ -2731,46 +2371,9 @@ try {
 	for (uint32_t s : del) keys.push_back(c->svc_gid_h[s]);
 	for (auto &hv : by_host) {
 		const uint32_t host = hv.first;
-		const std::unordered_set<uint32_t> &dead = hv.second;
-		HostListeners &hl = c->host_lst[host];
-		std::unordered_set<uint64_t> touched; // keys a deleted listener was registered under
-		for (uint32_t s : dead) {
-			const uint64_t key48 = c->svc_key_h[s];
-			touched.insert(key48);
-			auto ch = hl.chain.find(key48);
-			if (ch != hl.chain.end()) {
-				auto &v = ch->second;
-				v.erase(std::remove_if(v.begin(), v.end(), [&](const HostListeners::ChainEnt &e) { return e.slot == s; }), v.end());
-				if (v.empty()) hl.chain.erase(ch);
-			}
-			auto ok = hl.okey.find(key48);
-			if (ok != hl.okey.end() && ok->second == s) hl.okey.erase(ok);
-		}
-		hl.all_slots.erase(std::remove_if(hl.all_slots.begin(), hl.all_slots.end(), [&](uint32_t s) { return dead.count(s) != 0; }), hl.all_slots.end());
-		std::unordered_set<uint64_t> live; // touched keys that still have a listener bound
-		if (hl.overflow) {
-			for (uint64_t k : touched)
-				if (hl.chain.count(k) || hl.okey.count(k)) live.insert(k);
-		} else {
-			// the locals (key, slot) of the deleted listeners go; the survivors close up and the tables are rebuilt from them, hole-free
-			auto compact = [&](HostListeners &t) {
-				size_t w = 0;
-				for (size_t l = 0; l < t.slots.size(); ++l) {
-					if (dead.count(t.slots[l])) continue;
-					if (touched.count(t.keys[l])) live.insert(t.keys[l]);
-					t.slots[w] = t.slots[l];
-					t.keys[w] = t.keys[l];
-					++w;
-				}
-				t.slots.resize(w);
-				t.keys.resize(w);
-			};
-			if (hl.sub.empty()) compact(hl);
-			else for (HostListeners &t : hl.sub) compact(t);
-		}
-		for (uint64_t k : touched)
-			if (!live.count(k)) keys.push_back(listener_key(host, (uint32_t)(k >> 16), (uint16_t)(k & 0xFFFFu)));
-		hl.dirty = true;
+		std::vector<uint64_t> gone;
+		host_lst_remove(c->host_lst[host], hv.second, c->svc_key_h.data(), gone);
+		for (uint64_t k : gone) keys.push_back(listener_key(host, (uint32_t)(k >> 16), (uint16_t)(k & 0xFFFFu)));
 	}
 	// ---- device: the keys leave the tables, the hosts' sub-tables are rebuilt, the slots are cleared -- all behind the drained queues
 	const uint32_t nlk = (uint32_t)keys.size() - nd;
@@ -2806,6 +2409,100 @@ try {
 		}
 	}
 	return GYS_OK;
+} GYS_CATCH_ALL
+
+// ------------------------------------------------------------------------------------------------ registering listeners
+// The one registration path: the fresh (new, de-duplicated) listeners arr[0 .. n) of `host` take the service slots sl[i].  sl[0 .. nfree)
+// are reused slots, the others the tail [nsvc, nsvc + n - nfree).  One staging copy, one synchronisation before the mirror follows.
+static int register_fresh(gys_ctx *c, uint32_t host, const gys_listener_info *arr, uint32_t n, const std::vector<uint32_t> &sl, uint32_t nfree)
+{
+	std::vector<uint64_t> stage(2 * (size_t)n + ((size_t)n + 1) / 2); // [glob ids][listener keys][slot numbers, two to a word]
+	for (uint32_t i = 0; i < n; ++i) {
+		stage[i] = arr[i].glob_id;
+		stage[n + i] = listener_key(host, arr[i].netns, arr[i].port);
+	}
+	memcpy(stage.data() + 2 * (size_t)n, sl.data(), (size_t)n * 4);
+	std::vector<SvcClearSeg> segs;
+	int rc = nfree ? svc_clear_prepare(c, segs, stage.size() * 8) : ensure_staging(c, stage.size() * 8, 0);
+	if (rc) return rc;
+	const uint64_t *d_keys = (const uint64_t *)c->dev_staging.p;
+	const uint32_t *d_sl = (const uint32_t *)(d_keys + 2 * (size_t)n);
+	HIPCHK(hipMemcpyAsync(c->dev_staging, stage.data(), stage.size() * 8, hipMemcpyHostToDevice, c->stream));
+	HIPCHK(hipMemsetAsync(c->misc, 0, 4, c->stream));
+	// A free slot is part of every pass over [0, nsvc): a window close that went by while it was free wrote for it what it writes for a
+	// registered service without data (the first-close time of the since-start period, the level-0 tag, snapshots).  The slot is handed
+	// out as gys_create left it -- a listener's series starts at ITS first close, like a tail slot's -- so it is cleared once more here.
+	if (nfree) {
+		rc = svc_clear_launch(c, segs, d_sl, nfree);
+		if (rc) return rc;
+	}
+	const dim3 grid((n + 255) / 256), block(256);
+	hipLaunchKernelGGL(k_scatter_u64, grid, block, 0, c->stream, c->svc_gid, d_sl, d_keys, n);
+	hipLaunchKernelGGL(k_table_insert_vals, grid, block, 0, c->stream, c->gid_tbl, d_keys, d_sl, n, c->misc);
+	hipLaunchKernelGGL(k_table_insert_vals, grid, block, 0, c->stream, c->lk_tbl, d_keys + n, d_sl, n, c->misc);
+	hipLaunchKernelGGL(k_scatter_const_u32, grid, block, 0, c->stream, c->svc_host, d_sl, host, n);
+	uint32_t nfail = 0;
+	HIPCHK(hipMemcpyAsync(&nfail, c->misc, 4, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream)); // (stage / segs are locals)
+	if (nfail) {
+		set_err("key table full (%u inserts failed)", nfail);
+		return GYS_ERR_NOMEM;
+	}
+	rc = host_lst_add(c, host, arr, n, sl.data());
+	if (rc) return rc;
+	const uint32_t top = c->nsvc + (n - nfree);
+	c->svc_comm.resize(top);
+	c->svc_gid_h.resize(top);
+	c->svc_port_h.resize(top);
+	c->svc_host_h.resize(top);
+	c->svc_key_h.resize(top);
+	for (uint32_t i = 0; i < n; ++i) {
+		const uint32_t s = sl[i];
+		c->gid_map_h[arr[i].glob_id] = s;
+		c->host_lst[host].all_slots.push_back(s);
+		memcpy(c->svc_comm[s].data(), arr[i].comm, 16);
+		c->svc_gid_h[s] = arr[i].glob_id;
+		c->svc_port_h[s] = arr[i].port;
+		c->svc_host_h[s] = host;
+		c->svc_key_h[s] = host_key48(arr[i].netns, arr[i].port);
+		c->free_slots.erase(s);
+	}
+	c->nsvc = top;
+	c->registry_gen++;
+	return GYS_OK;
+}
+
+int gys_register_listeners(gys_ctx *c, const uint8_t machine_id[16], const gys_listener_info *arr_in, uint32_t n_in, uint32_t *first_slot)
+try {
+	GYS_ENTER(c);
+	if (!c || !machine_id || (!arr_in && n_in)) return GYS_ERR_INVAL;
+	uint32_t host;
+	int rc = lookup_host(c, machine_id, &host);
+	if (rc) return rc;
+	// a partha resends NEW_LISTENER after a reconnect: a glob_id the engine already knows keeps its slot (and its histograms, digest,
+	// counters); repeats inside one call are dropped as well, so that the device tables never see the same key twice
+	std::vector<gys_listener_info> fresh;
+	{
+		std::unordered_set<uint64_t> seen;
+		for (uint32_t i = 0; i < n_in; ++i)
+			if (!c->gid_map_h.count(arr_in[i].glob_id) && seen.insert(arr_in[i].glob_id).second) fresh.push_back(arr_in[i]);
+	}
+	const uint32_t n = (uint32_t)fresh.size();
+	if ((uint64_t)c->nsvc + n > c->cfg.max_services) { // (the tail only: this call never takes a free slot)
+		set_err("max_services exhausted");
+		return GYS_ERR_NOMEM;
+	}
+	if (first_slot) *first_slot = c->nsvc;
+	if (!n) return GYS_OK;
+	std::vector<uint32_t> sl(n);
+	for (uint32_t i = 0; i < n; ++i) {
+		if (fresh[i].glob_id == GYS_EMPTY_KEY) {
+			set_err("glob_id ~0 is reserved");
+			return GYS_ERR_INVAL;
+		}
+		sl[i] = c->nsvc + i;
+	}
+	return register_fresh(c, host, fresh.data(), n, sl, 0);
 } GYS_CATCH_ALL
 
 int gys_register_listeners_slots(gys_ctx *c, const uint8_t machine_id[16], const gys_listener_info *arr_in, uint32_t n_in, uint32_t *slots)
@@ -2844,61 +2541,8 @@ try {
 		for (uint32_t i = 0; i < ntail; ++i) sl[nfree + i] = c->nsvc + i;
 	}
 	if (n) {
-		const gys_listener_info *arr = fresh.data();
-		std::vector<uint64_t> keys(2 * (size_t)n);
-		for (uint32_t i = 0; i < n; ++i) {
-			keys[i] = arr[i].glob_id;
-			keys[n + i] = listener_key(host, arr[i].netns, arr[i].port);
-		}
-		const uint64_t keys_bytes = keys.size() * 8;
-		std::vector<SvcClearSeg> segs;
-		rc = nfree ? svc_clear_prepare(c, segs, keys_bytes + (uint64_t)n * 4) : ensure_staging(c, keys_bytes + (uint64_t)n * 4, 0);
+		rc = register_fresh(c, host, fresh.data(), n, sl, nfree);
 		if (rc) return rc;
-		const uint64_t *d_keys = (const uint64_t *)c->dev_staging.p;
-		const uint32_t *d_sl = (const uint32_t *)(c->dev_staging + keys_bytes);
-		HIPCHK(hipMemcpyAsync(c->dev_staging, keys.data(), keys_bytes, hipMemcpyHostToDevice, c->stream));
-		HIPCHK(hipMemcpyAsync(c->dev_staging + keys_bytes, sl.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-		HIPCHK(hipMemsetAsync(c->misc, 0, 4, c->stream));
-		// A free slot is part of every pass over [0, nsvc): a window close that went by while it was free wrote for it what it writes for a
-		// registered service without data (the first-close time of the since-start period, the level-0 tag, snapshots).  The slot is handed
-		// out as gys_create left it -- a listener's series starts at ITS first close, like a tail slot's -- so it is cleared once more here.
-		if (nfree) {
-			rc = svc_clear_launch(c, segs, d_sl, nfree); // (sl[0 .. nfree) are the reused slots)
-			if (rc) return rc;
-		}
-		const dim3 grid((n + 255) / 256), block(256);
-		hipLaunchKernelGGL(k_scatter_u64, grid, block, 0, c->stream, c->svc_gid, d_sl, d_keys, n);
-		hipLaunchKernelGGL(k_table_insert_vals, grid, block, 0, c->stream, c->gid_tbl, d_keys, d_sl, n, c->misc);
-		hipLaunchKernelGGL(k_table_insert_vals, grid, block, 0, c->stream, c->lk_tbl, d_keys + n, d_sl, n, c->misc);
-		hipLaunchKernelGGL(k_scatter_const_u32, grid, block, 0, c->stream, c->svc_host, d_sl, host, n);
-		uint32_t nfail = 0;
-		HIPCHK(hipMemcpyAsync(&nfail, c->misc, 4, hipMemcpyDeviceToHost, c->stream));
-		HIPCHK(hipStreamSynchronize(c->stream));
-		if (nfail) {
-			set_err("key table full (%u inserts failed)", nfail);
-			return GYS_ERR_NOMEM;
-		}
-		rc = host_lst_add(c, host, arr, n, 0, sl.data());
-		if (rc) return rc;
-		const uint32_t top = c->nsvc + ntail;
-		c->svc_comm.resize(top);
-		c->svc_gid_h.resize(top);
-		c->svc_port_h.resize(top);
-		c->svc_host_h.resize(top);
-		c->svc_key_h.resize(top);
-		for (uint32_t i = 0; i < n; ++i) {
-			const uint32_t s = sl[i];
-			c->gid_map_h[arr[i].glob_id] = s;
-			c->host_lst[host].all_slots.push_back(s);
-			memcpy(c->svc_comm[s].data(), arr[i].comm, 16);
-			c->svc_gid_h[s] = arr[i].glob_id;
-			c->svc_port_h[s] = arr[i].port;
-			c->svc_host_h[s] = host;
-			c->svc_key_h[s] = host_key48(arr[i].netns, arr[i].port);
-			c->free_slots.erase(s);
-		}
-		c->nsvc = top;
-		c->registry_gen++;
 	}
 	if (slots)
 		for (uint32_t i = 0; i < n_in; ++i) slots[i] = fresh_of[i] != GYS_NOSLOT ? sl[fresh_of[i]] : c->gid_map_h[arr_in[i].glob_id];

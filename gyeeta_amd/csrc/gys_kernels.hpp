@@ -36,23 +36,6 @@ enum { CTR_RESP_EVENTS = 0, CTR_RESP_DROP_RANGE, CTR_RESP_DROP_NOLISTENER, CTR_C
        CTR_CONN_NEW, CTR_CONN_CLOSED, CTR_CONN_CLOSED_NO_NOTIFY, CTR_CONN_CLI_SIDE, CTR_RESP_RUN_OVERFLOW, CTR_NUM };
 
 // ---------------------------------------------------------------------------------------------------- table insert
-__global__ void k_table_insert(DevTable t, const uint64_t *keys, uint32_t first_val, uint32_t n, uint32_t *nfail)
-{
-	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n) return;
-	const uint64_t key = keys[i];
-	uint32_t h = get_uint64_hash(key) & t.mask;
-	for (uint32_t probes = 0; probes <= t.mask; ++probes) {
-		const unsigned long long prev = atomicCAS((unsigned long long *)&t.ent[h].key, (unsigned long long)GYS_EMPTY_KEY, (unsigned long long)key);
-		if (prev == GYS_EMPTY_KEY || prev == key) {
-			t.ent[h].val = first_val + i; // re-registration of a key rebinds it to the newest slot
-			return;
-		}
-		h = (h + 1) & t.mask;
-	}
-	atomicAdd(nfail, 1u);
-}
-
 // kv[2 i] = key, kv[2 i + 1] = value: the key (inserted if new) gets exactly that value
 __global__ void k_table_set(DevTable t, const uint64_t *kv, uint32_t n)
 {

@@ -9,12 +9,13 @@
 //   k_table_erase        keys out of an open-addressing table (gys_device.hpp) by BACKWARD-SHIFT deletion: the entries of the probe run
 //                        behind the hole move up as far as their home position allows, so the table is afterwards what inserting the
 //                        remaining keys alone could have produced -- no tombstone, "no key behind an empty entry" (tbl_lookup,
-//                        k_table_insert and k_table_set rely on it) holds, and probe lengths are those of the live keys however many
+//                        k_table_insert_vals and k_table_set rely on it) holds, and probe lengths are those of the live keys however many
 //                        register / delete cycles have passed.  Two erases in overlapping runs would race, and a batch is at most a few
 //                        hundred keys with runs of two or three entries at the table's load of <= 1/2: one thread walks the list.
 //                        BATCH SIZE: the kernel is one lane, a few dependent global accesses per key -- right for the hundreds of ids
 //                        of a delete message or a cleanup round (the shim deletes 512 per call), not for 10^5 ids in one call.
-//   k_table_insert_vals  k_table_insert with a value per key (a reused slot is not `first_val + i`).
+//   k_table_insert_vals  keys into a table, each with its value (the service slot: a reused one or one of the tail); a key that is
+//                        already there is rebound to the new value.
 //   k_svc_clear          per listed slot, every per-service array back to its initial contents.  The arrays are described by a segment
 //                        list the host fills in (SvcClearSeg: base, bytes per service, fill words): a workgroup per slot, its four waves
 //                        take the segments in turn, the lanes of a wave store 16 bytes each (segments of 4 or 8 bytes per service: dwords).

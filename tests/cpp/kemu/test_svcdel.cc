@@ -1,7 +1,7 @@
 // TEST INFRASTRUCTURE (CPU): the LOGIC of the listener-deletion kernels (gyeeta_amd/csrc/gys_svcdel.hpp) under the CPU stand-in of the
 // device model:
 //   * key tables: a 64-entry table with at most 32 live keys; a probe run of keys that all hash to one entry (and one that wraps round the
-//     table's end) with erases from its middle, head and tail; then 10 000 random steps of k_table_insert_vals / k_table_insert /
+//     table's end) with erases from its middle, head and tail; then 10 000 random steps of k_table_insert_vals /
 //     k_table_erase (of live keys, of keys that are not there, re-inserts of live keys with a new value) against std::unordered_map.  After
 //     EVERY step every live key is found with its value by tbl_lookup, every other key of the universe is not, no insert has failed and
 //     the table holds exactly as many entries as there are live keys (no tombstone, nothing lost, nothing doubled);
@@ -52,7 +52,7 @@ struct Table {
 		t.ent = ent.data();
 		t.mask = CAP - 1;
 	}
-	void insert(uint64_t key, uint32_t val, bool by_vals)
+	void insert(uint64_t key, uint32_t val)
 	{
 		std::vector<uint64_t> k(1, key);
 		std::vector<uint32_t> v(1, val);
@@ -60,10 +60,7 @@ struct Table {
 		const uint64_t *kp = k.data();
 		const uint32_t *vp = v.data();
 		uint32_t *nf = nfail.data();
-		if (by_vals)
-			kemu::launch(1, 1, 0, [=] { k_table_insert_vals(tt, kp, vp, 1u, nf); });
-		else
-			kemu::launch(1, 1, 0, [=] { k_table_insert(tt, kp, val, 1u, nf); });
+		kemu::launch(1, 1, 0, [=] { k_table_insert_vals(tt, kp, vp, 1u, nf); });
 	}
 	uint32_t erase(const std::vector<uint64_t> &keys)
 	{
@@ -120,7 +117,7 @@ void test_tables(uint64_t seed)
 		std::unordered_map<uint64_t, uint32_t> live;
 		uint32_t val = 100;
 		auto ins = [&](uint64_t k) {
-			tb.insert(k, val, true);
+			tb.insert(k, val);
 			live[k] = val++;
 		};
 		for (int i = 0; i < 10; ++i) ins(run5[i]);
@@ -156,7 +153,7 @@ void test_tables(uint64_t seed)
 		if (live.size() < 32 && (r < 50 || live.size() < 4)) {
 			const uint64_t k = universe[rng() % universe.size()]; // (a live key: rebound to the new value)
 			const uint32_t v = (uint32_t)(rng() % 1000000);
-			tb.insert(k, v, r & 1u);
+			tb.insert(k, v);
 			live[k] = v;
 		} else if (r < 90 || live.size() >= 32) {
 			// one to three keys in one launch: live ones, and now and then one that is not there

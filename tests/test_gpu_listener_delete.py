@@ -481,6 +481,51 @@ def test_the_old_call_takes_tail_slots_only(torch_mod):
     eng.close()
 
 
+def test_both_registration_calls_build_the_same_registry(torch_mod, oracle):
+    """No deletion ever: one engine registers the world through register_listeners, one through register_listeners_slots -- hosts of 40 and
+    40 listeners (host 0 with the shared bound-address key) and one of 2 049, the smallest that is cut into parts.  The slot numbers are
+    equal, and after an IPv4 and an IPv6 response batch per host both engines equal the oracle and, behind a window close, each other in
+    every export."""
+    ncut = 2049
+    world = ((0, NSMALL, 30), (1, NSMALL, 30), (2, ncut, 1))
+    rng = np.random.default_rng(17)
+    batches = [(h, v6, _events(rng, h, np.arange(n), max(per // (4 if v6 else 1), 1), v6)[0]) for h, n, per in world for v6 in (False, True)]
+    orc = oracle.OracleEngine(2 * NSMALL + ncut)
+    outs, slots = {}, {}
+    for call in ("tail", "slots"):
+        eng = _engine(max_hosts=4, max_services=8192, max_batch_events=1 << 20, enable_levels=True, svc_hll_p=6, svc_hll_levels=1)
+        mids = {h: wire.machine_id(h) for h in range(3)}
+        hslot = {h: eng.register_host(mids[h], "cluster%d" % (h % 2)) for h in range(3)}
+        slots[call] = []
+        for h, n, _ in world:
+            g, ns, pt, addrs = _listeners(h, np.arange(n))
+            if call == "tail":
+                slots[call].append(eng.register_listeners(mids[h], g, ns, pt, addrs=addrs) + np.arange(n))
+                for i in range(n):
+                    assert orc.register_addr(hslot[h], int(g[i]), int(ns[i]), int(pt[i]), addrs[i]) == slots[call][-1][i]
+            else:
+                slots[call].append(eng.register_listeners_slots(mids[h], g, ns, pt, addrs=addrs))
+        for h, v6, ev in batches:
+            (eng.handle_resp_events_v6 if v6 else eng.handle_resp_events)(mids[h], ev)
+            if call == "tail":
+                (orc.resp_batch_v6 if v6 else orc.resp_batch)(ev.tobytes(), [hslot[h]], [0])
+        eng.sync()
+        n = eng.num_services()
+        assert n == orc.nsvc == 2 * NSMALL + ncut
+        helpers.assert_hist_equal(eng.export_hist(0, 0, n), orc.hist(), n)
+        gs, gc, gm = eng.export_tdigest(0, n)
+        os_, oc, om = orc.td_arrays()
+        assert (gc == oc).all() and (gs == os_).all() and (gm == om).all()
+        c, oc_ = eng.counters(), orc.counters()
+        assert c["resp_events"] == oc_["events"] == sum(len(ev) for _, _, ev in batches) and c["resp_dropped_nolistener"] == oc_["dropped_nolistener"] == 0
+        eng.window_close(T0 * 1_000_000)
+        outs[call] = _exports(eng, (T0 + 31) * 1_000_000)
+        eng.close()
+    assert np.concatenate(slots["tail"]).tolist() == np.concatenate(slots["slots"]).tolist() == list(range(2 * NSMALL + ncut))
+    assert outs["tail"]["hist1"][:, 15, 0].sum() == sum(len(ev) for _, _, ev in batches)  # (every event reached a service)
+    _assert_same(outs["tail"], outs["slots"])
+
+
 def test_mid_window_delete(torch_mod):
     """A: everything ingested (one batch from two threads through the submission queue), then host 1's services 0..9 deleted mid-window.
     B: never got their events.  C: got everything, deleted nothing."""
