@@ -30,6 +30,7 @@
 #include <rccl/rccl.h>
 
 #include "gys_devmem.hpp"
+#include "gys_subq.hpp"
 #include "gys_kernels.hpp"
 #include "gys_rollup.hpp"
 #include "gys_groups.hpp"
@@ -87,8 +88,6 @@ struct ProfEntry {
 	uint64_t launches = 0;
 	std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
 };
-
-inline uint64_t align_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
 
 struct ArenaLayout {
 	uint64_t off_hll8, off_u32, n_u32, off_i64sum, n_i64sum, off_i64max, n_i64max, total;
@@ -268,71 +267,12 @@ struct gys_ctx {
 	uint64_t close_graph_launches = 0;
 	bool have_last = false;
 
-	// staging for host-buffer ingest
-	// host-pointer boundary (gys_ingest_resp_events / _tcp_conn / _listener_state): a ring of pinned host + device staging
-	// buffers.  A call copies the caller's records into a slot's pinned buffer (the caller's buffer is free when the call returns --
-	// the reference's pone points into the L1 receive buffer, valid only for the call), enqueues ONE H2D copy + the kernels and
-	// returns without waiting for the GPU; a slot is reused after the event recorded behind its kernels has fired.  Up to
-	// MAX_L2_MISC_THREADS = 16 L2 threads (server/gy_mconnhdlr.h:60) call concurrently: slots are handed out under stage_mu, the
-	// memcpy into pinned memory runs outside any lock, the enqueue (stream order, shared flags) under enq_mu.
-	struct Stage {
-		PinnedPair<uint8_t> buf;
-		hipEvent_t done = nullptr;
-		hipEvent_t copied = nullptr; // (record batches: the slot's H2D copy on the copy stream)
-	};
-	static constexpr int NSTAGE = 16;
-	Stage stage[NSTAGE];
-	std::deque<int> stage_free; // handed out OLDEST FIRST (pop_front / push_back): a slot's event has normally fired long before the slot comes round again
-	std::mutex stage_mu, enq_mu;
-	std::condition_variable stage_cv;
-	std::atomic<uint64_t> stage_waits{0}; // times a host-pointer call found its ring slot still in flight and waited for the GPU
-	// Submission queues of the host-pointer calls ("group commit", SURVEY 8b second option): one for gys_ingest_resp_events, one for
-	// gys_ingest_tcp_conn (TCP_CONN_NOTIFY), one for gys_ingest_listener_state (LISTENER_STATE_NOTIFY).  The calls of all L2 threads are
-	// appended to ONE pinned batch and a batch is copied and launched once, so that the fixed cost of a submission is paid per batch
-	// instead of per call: the ~12 launches of a response batch per 65536-event call; for the records, through the 16-slot staging ring,
-	// an H2D copy, two event records, a stream wait and a launch -- five runtime calls of ~5 us each under enq_mu for a 2048-record
-	// (0.57 MB) or 512-record (45 KB) message: 69 M connection records/s and 24 M listener records/s from 16 threads, a third and a
-	// twentieth of what the link carries, with the ring wrapping all the time (gys_counters.stage_waits).
-	// The protocol (subq_* below): a caller reserves its place in the open batch under mu, copies outside any lock (`writers` counts the
-	// copies in progress), and whoever finds no submission being made submits what has accumulated.  A lone caller submits its own call at
-	// once: no added latency.  While GYS_RQ_INFLIGHT submissions are still executing on the GPU, further calls accumulate and go out
-	// together as soon as one of them has finished -- the GPU always has the next submission queued behind the running one, and the fixed
-	// cost is amortised exactly when the GPU is the bottleneck.  Batches are submitted in the order they were sealed.  The tail of a
-	// burst: calls that found GYS_RQ_INFLIGHT submissions on the GPU left their data in the open batch, and after the burst nobody calls
-	// again -- a flusher thread (started with the first queued call) submits that batch once a submission has retired.
-	// Responses: a segment per call, and a host appears at most once per batch (its keys see their per-call value multisets in call
-	// order: the digests stay bit-identical to per-call ingestion).  Records: the records, then an offset (and, for listener states, the
-	// sender's host slot) per record; they keep the order in which the calls reserved their place, so "the last record of a listener
-	// wins" holds across the messages of a batch as it does across calls.
-	struct SubQ {
-		enum Kind { RESP, CONN, LSTATE } kind = RESP; // (also its index in gys_ctx::sq)
-		struct Batch {
-			PinnedPair<uint8_t> buf;            // RESP: events; else [records: cap][offset per record: u32 x cap_recs][host slot per record: u32 x cap_recs]
-			uint64_t fill = 0;                  // RESP: events; else record bytes (8-byte aligned per call)
-			uint32_t nrec = 0;                  // records (not RESP)
-			std::vector<gys_resp_seg> segs;     // RESP: a segment per call
-			hipEvent_t done = nullptr;          // behind the batch's kernels: its buffers are not reused before
-			hipEvent_t copied = nullptr;        // the batch's H2D copies on the copy stream (the engine stream waits for it before the batch's kernels)
-			uint32_t writers = 0;
-		} b[6];
-		int nb = 0;                     // batches in use: 6 (RESP) / 4
-		uint64_t cap = 0, buf_bytes = 0; // per batch: `fill` it holds, size of buf
-		uint32_t cap_recs = 0;
-		std::mutex mu;
-		std::condition_variable cv;
-		std::deque<int> free, sealed, inflight; // sealed: awaiting submission, oldest first; inflight: submitted, GPU not done yet
-		int open = -1;
-		bool submitting = false;
-		int async_rc = 0; // first error of a submission made on behalf of other callers; surfaces at the next call
-		std::string async_err;
-		uint64_t calls = 0, submissions = 0, tail_flushes = 0;
-		std::vector<uint32_t> host_stamp; // RESP: host -> stamp of the open batch it is in
-		uint32_t stamp = 0;
-		std::condition_variable fcv;
-		std::thread flusher;
-		bool flusher_on = false, stop = false;
-		const char *word() const { return kind == RESP ? "response" : "record"; } // (error texts)
-	} sq[3];
+	// host-pointer boundary (gys_subq.hpp): the submission queues of gys_ingest_resp_events / _tcp_conn / _listener_state (indexed by
+	// SubQ::Kind), the ring of pinned staging slots of the calls that go on their own, and what both use of this context (bound at gys_create)
+	IngestEnv ingest;
+	SubQ sq[3];
+	StageRing ring;
+	std::mutex enq_mu; // the enqueue of a concurrent host-pointer call: stream order, shared flags
 	DevBuf<uint8_t> dev_staging; // device-pointer record calls: the records and their offsets (grow)
 	DevBuf<uint32_t> dev_offsets;
 	// which service belongs to which host, which host to which cluster: counted up by every call that changes either (services added or
@@ -447,49 +387,6 @@ inline uint32_t grid_for(uint64_t n, uint32_t block, uint32_t cap)
 	if (g < 1) g = 1;
 	if (g > cap) g = cap;
 	return (uint32_t)g;
-}
-
-// ---- staging ring of the host-pointer boundary (gys_ctx::Stage)
-int stage_acquire(gys_ctx *c, uint64_t bytes, int *idx)
-{
-	int i;
-	{
-		std::unique_lock<std::mutex> lk(c->stage_mu);
-		c->stage_cv.wait(lk, [&] { return !c->stage_free.empty(); });
-		i = c->stage_free.front();
-		c->stage_free.pop_front();
-	}
-	gys_ctx::Stage &st = c->stage[i];
-	// the calling (L2) thread's current device is whatever it used last -- 0 for a fresh thread: the slot's buffers, the copy and the
-	// kernels must live on the context's device
-	hipError_t e = hipSetDevice(c->device);
-	if (e == hipSuccess && !st.done) e = hipEventCreateWithFlags(&st.done, hipEventDisableTiming);
-	if (e == hipSuccess && !st.copied) e = hipEventCreateWithFlags(&st.copied, hipEventDisableTiming);
-	if (e == hipSuccess && hipEventQuery(st.done) == hipErrorNotReady) c->stage_waits++;
-	(void)hipGetLastError();
-	if (e == hipSuccess) e = hipEventSynchronize(st.done); // the kernels that read this slot last time are done (no-op unless the ring wrapped)
-	int rc = GYS_OK;
-	if (e != hipSuccess) {
-		set_err("staging slot: %s", hipGetErrorString(e));
-		rc = GYS_ERR_HIP;
-	} else if (bytes > st.buf.cap) {
-		rc = st.buf.grow(align_up(bytes, 4096), 1u << 20);
-	}
-	if (rc) {
-		std::lock_guard<std::mutex> lk(c->stage_mu);
-		c->stage_free.push_back(i);
-		c->stage_cv.notify_one();
-		return rc;
-	}
-	*idx = i;
-	return GYS_OK;
-}
-
-void stage_release(gys_ctx *c, int idx)
-{
-	std::lock_guard<std::mutex> lk(c->stage_mu);
-	c->stage_free.push_back(idx);
-	c->stage_cv.notify_one();
 }
 
 int ensure_staging(gys_ctx *c, uint64_t bytes, uint32_t nrec)
@@ -1523,293 +1420,14 @@ int run_lstate(gys_ctx *c, const uint8_t *d_batch, const uint32_t *d_offsets, co
 	return GYS_OK;
 }
 
-// records of one variable-stride batch [batch, batch + bytes) + their offsets through a staging slot: one pinned copy, one H2D copy
-// (records, then the offsets behind them), the ingest kernel, no wait
-int ingest_staged_records(gys_ctx *c, uint32_t host, const void *batch, uint64_t bytes, const std::vector<uint32_t> &offs, bool conn)
+// ---- host-pointer boundary (gys_subq.hpp: the queues' protocol and the staging ring are described there)
+// the launch of a submission queue's copied batch (IngestEnv::launch; enq_mu is held)
+int launch_batch(gys_ctx *c, SubQ::Kind kind, const uint8_t *dev, uint64_t fill, uint32_t nrec, const std::vector<gys_resp_seg> &segs)
 {
-	const uint64_t off_at = align_up(bytes, 8), total = off_at + offs.size() * 4;
-	int si;
-	int rc = stage_acquire(c, total, &si);
-	if (rc) return rc;
-	gys_ctx::Stage &st = c->stage[si];
-	memcpy(st.buf.host, batch, bytes);
-	memcpy(st.buf.host + off_at, offs.data(), offs.size() * 4);
-	{
-		std::lock_guard<std::mutex> g(c->enq_mu);
-		// (copy on the copy stream, kernels on the engine stream behind an event -- as for the response submissions: the copy of one
-		// message runs under the kernels of the message before it)
-		hipError_t e = hipMemcpyAsync(st.buf.dev, st.buf.host, total, hipMemcpyHostToDevice, c->copy_stream);
-		if (e == hipSuccess) e = hipEventRecord(st.copied, c->copy_stream);
-		if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, st.copied, 0);
-		if (e == hipSuccess) {
-			rc = conn ? run_conn(c, st.buf.dev, (const uint32_t *)(st.buf.dev + off_at), (uint32_t)offs.size())
-				  : run_lstate(c, st.buf.dev, (const uint32_t *)(st.buf.dev + off_at), nullptr, host, (uint32_t)offs.size());
-			e = hipEventRecord(st.done, c->stream);
-		}
-		if (e != hipSuccess) {
-			set_err("ingest: %s", hipGetErrorString(e));
-			rc = GYS_ERR_HIP;
-		}
-	}
-	stage_release(c, si);
-	return rc;
-}
-
-
-// ---- submission queues of the host-pointer response / connection / listener-state calls (gys_ctx::SubQ: the protocol is described there)
-using SubQ = gys_ctx::SubQ;
-constexpr uint64_t GYS_RQ_EVENTS = 1u << 21; // events per combined batch (48 MiB pinned + 48 MiB device each)
-constexpr uint64_t GYS_CQ_CONN_BYTES = 16u << 20, GYS_CQ_LSTATE_BYTES = 4u << 20; // record bytes per combined batch
-constexpr size_t GYS_RQ_INFLIGHT = 2; // submissions executing / queued on the GPU before new calls start to accumulate
-
-void subq_init(gys_ctx *c, SubQ::Kind kind)
-{
-	SubQ &q = c->sq[kind];
-	q.kind = kind;
-	if (kind == SubQ::RESP) {
-		q.nb = 6;
-		q.cap = std::min<uint64_t>(GYS_RQ_EVENTS, std::max<uint64_t>(c->cfg.max_batch_events, 1));
-		q.buf_bytes = q.cap * 24;
-	} else {
-		q.nb = 4;
-		q.cap = kind == SubQ::CONN ? GYS_CQ_CONN_BYTES : GYS_CQ_LSTATE_BYTES;
-		q.cap_recs = (uint32_t)(q.cap / (kind == SubQ::CONN ? 280u : 88u));
-		q.buf_bytes = q.cap + (uint64_t)q.cap_recs * 8;
-	}
-	for (int i = 0; i < q.nb; ++i) q.free.push_back(i);
-}
-
-// submits batch b of q (sealed, no writers); q.mu NOT held
-int subq_submit_one(gys_ctx *c, SubQ &q, SubQ::Batch &b)
-{
-	const bool resp = q.kind == SubQ::RESP;
-	int rc = GYS_OK;
-	std::lock_guard<std::mutex> g(c->enq_mu);
-	// copy on its own stream, kernels on the engine stream behind an event: with everything on one stream the 48-MiB copy of a response
-	// submission (0.85 ms at 57 GB/s) and its kernels alternate; the batch's buffers are not reused before `done` has fired
-	hipStream_t cs = c->copy_stream;
-	const uint64_t off_at = q.cap, host_at = q.cap + (uint64_t)q.cap_recs * 4;
-	hipError_t e = hipMemcpyAsync(b.buf.dev, b.buf.host, resp ? b.fill * 24 : b.fill, hipMemcpyHostToDevice, cs);
-	if (e == hipSuccess && !resp) e = hipMemcpyAsync(b.buf.dev + off_at, b.buf.host + off_at, (uint64_t)b.nrec * 4, hipMemcpyHostToDevice, cs);
-	if (e == hipSuccess && q.kind == SubQ::LSTATE) e = hipMemcpyAsync(b.buf.dev + host_at, b.buf.host + host_at, (uint64_t)b.nrec * 4, hipMemcpyHostToDevice, cs);
-	if (e == hipSuccess) e = hipEventRecord(b.copied, cs);
-	if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, b.copied, 0);
-	if (e == hipSuccess) {
-		if (resp) rc = run_resp_batch(c, b.segs.data(), (uint32_t)b.segs.size(), b.buf.dev, b.fill);
-		else if (q.kind == SubQ::CONN) rc = run_conn(c, b.buf.dev, (const uint32_t *)(b.buf.dev + off_at), b.nrec);
-		else rc = run_lstate(c, b.buf.dev, (const uint32_t *)(b.buf.dev + off_at), (const uint32_t *)(b.buf.dev + host_at), 0, b.nrec);
-		e = hipEventRecord(b.done, c->stream);
-	}
-	if (e != hipSuccess) {
-		set_err("%s submission: %s", q.word(), hipGetErrorString(e));
-		rc = GYS_ERR_HIP;
-	}
-	return rc;
-}
-
-// q.mu held: batches whose kernels have finished go back to the free list
-void subq_reap(SubQ &q)
-{
-	// anything but "not ready" ends a submission's stay on the in-flight list: an event in an error state never turns into hipSuccess, and
-	// a head that is never reaped would leave every later caller waiting once the free list has drained
-	while (!q.inflight.empty()) {
-		const hipError_t e = hipEventQuery(q.b[q.inflight.front()].done);
-		if (e == hipErrorNotReady) break;
-		if (e != hipSuccess && !q.async_rc) {
-			q.async_rc = GYS_ERR_HIP;
-			q.async_err = std::string(q.word()) + " submission: " + hipGetErrorString(e);
-		}
-		q.free.push_back(q.inflight.front());
-		q.inflight.pop_front();
-	}
-	(void)hipGetLastError(); // (hipErrorNotReady is not an error)
-}
-
-// With q.mu held (lk): submit, oldest first, every sealed batch whose writers are done -- and the open batch too when `all`, or when it
-// has data, no writer, and fewer than GYS_RQ_INFLIGHT submissions are still on the GPU.  Returns the first error of a batch that
-// carried the caller's own data (`mine`), other errors are parked in q.async_rc.
-int subq_drain(gys_ctx *c, SubQ &q, std::unique_lock<std::mutex> &lk, int mine, bool all)
-{
-	int my_rc = GYS_OK;
-	if (q.submitting) {
-		if (!all) return GYS_OK; // the thread inside the submission picks up what accumulates
-		q.cv.wait(lk, [&] { return !q.submitting; });
-	}
-	for (;;) {
-		if (q.sealed.empty() && q.open >= 0 && q.b[q.open].fill && q.b[q.open].writers == 0) {
-			subq_reap(q);
-			if (all || q.inflight.size() < GYS_RQ_INFLIGHT) {
-				q.sealed.push_back(q.open);
-				q.open = -1;
-			}
-		}
-		if (q.sealed.empty()) break;
-		const int bi = q.sealed.front();
-		SubQ::Batch &b = q.b[bi];
-		if (b.writers) {
-			if (!all) break; // its last writer drains
-			q.cv.wait(lk, [&] { return b.writers == 0; });
-		}
-		q.sealed.pop_front();
-		q.submitting = true;
-		lk.unlock();
-		const int rc = subq_submit_one(c, q, b);
-		lk.lock();
-		q.submitting = false;
-		q.submissions++;
-		b.fill = 0;
-		b.nrec = 0;
-		b.segs.clear();
-		q.inflight.push_back(bi);
-		q.cv.notify_all();
-		if (rc) {
-			if (bi == mine) my_rc = rc;
-			else if (!q.async_rc) {
-				q.async_rc = rc;
-				q.async_err = g_err;
-			}
-		}
-	}
-	return my_rc;
-}
-
-// q.mu held: the error of a submission made for other callers (or by the flusher) is reported once, by the first call that comes by
-int subq_parked_error(SubQ &q)
-{
-	const int rc = q.async_rc;
-	if (rc) {
-		set_err("%s", q.async_err.c_str());
-		q.async_rc = 0;
-	}
-	return rc;
-}
-
-// everything the queue holds is on the stream when this returns (entry points other than the concurrent ingest calls start with it)
-int subq_flush(gys_ctx *c, SubQ &q)
-{
-	std::unique_lock<std::mutex> lk(q.mu);
-	if (q.open >= 0 || !q.sealed.empty() || q.submitting) (void)subq_drain(c, q, lk, -1, true); // (no batch of this caller's: errors are parked)
-	return subq_parked_error(q);
-}
-
-// flusher thread of a submission queue: sleeps until a call leaves data behind in the open batch, then tries every 200 us to submit
-// it (subq_drain submits only while fewer than GYS_RQ_INFLIGHT submissions are on the GPU); an error lands in q.async_rc for the next caller
-void subq_flusher(gys_ctx *c, SubQ *qp)
-{
-	SubQ &q = *qp;
-	(void)hipSetDevice(c->device);
-	std::unique_lock<std::mutex> lk(q.mu);
-	for (;;) {
-		q.fcv.wait(lk, [&] { return q.stop || (q.open >= 0 && q.b[q.open].fill != 0); });
-		if (q.stop) break;
-		// the GPU is the bottleneck while GYS_RQ_INFLIGHT submissions are on it: wait for the oldest one's event (outside the lock) rather than
-		// wake every 200 us to find nothing to do; otherwise give the burst 200 us to bring more calls before its tail goes out
-		hipEvent_t busy = q.inflight.size() >= GYS_RQ_INFLIGHT ? q.b[q.inflight.front()].done : nullptr;
-		lk.unlock();
-		if (busy) (void)hipEventSynchronize(busy);
-		else std::this_thread::sleep_for(std::chrono::microseconds(200));
-		lk.lock();
-		if (q.stop) break;
-		if (q.open >= 0 && q.b[q.open].fill && q.b[q.open].writers == 0 && !q.submitting) {
-			const uint64_t before = q.submissions;
-			(void)subq_drain(c, q, lk, -1, false);
-			if (q.submissions != before) q.tail_flushes++;
-		}
-	}
-}
-
-// one call of the sender in slot `host`.  Responses: n events of 24 bytes at `data` (offs unused).  Records: one message, `bytes` of
-// records at `data`, offs[i] = offset of record i of n in it.
-int subq_ingest(gys_ctx *c, SubQ &q, uint32_t host, const void *data, uint64_t bytes, uint32_t n, const uint32_t *offs)
-{
-	const bool resp = q.kind == SubQ::RESP;
-	const uint64_t need = resp ? n : align_up(bytes, 8); // of a batch's `fill`
-	std::unique_lock<std::mutex> lk(q.mu);
-	if (!q.flusher_on) {
-		q.flusher_on = true;
-		q.flusher = std::thread(subq_flusher, c, &q);
-	}
-	// (an earlier submission made for other callers may have failed: that error is reported once, by the first call that comes by -- AFTER
-	// the caller's own data has been queued below, never instead of it)
-	q.calls++;
-	if (resp && q.host_stamp.size() < c->hosts.size()) q.host_stamp.resize(c->hosts.size(), 0);
-	int bi;
-	for (;;) {
-		if (q.open < 0) {
-			subq_reap(q);
-			if (q.free.empty()) {
-				if (!q.inflight.empty()) { // every batch is on the GPU: wait for the oldest (outside the lock), then look again
-					hipEvent_t ev = q.b[q.inflight.front()].done;
-					lk.unlock();
-					(void)hipEventSynchronize(ev);
-					lk.lock();
-				} else {
-					q.cv.wait(lk, [&] { return !q.free.empty() || !q.inflight.empty(); }); // (sealed / being submitted by others)
-				}
-				continue;
-			}
-			bi = q.free.front();
-			q.free.pop_front();
-			SubQ::Batch &nb = q.b[bi];
-			lk.unlock(); // (first-use allocation: outside the lock; the batch is not visible yet)
-			// the buffers (both or none: PinnedPair) and the two events; what a failure leaves built, the next caller of this batch completes
-			int arc = nb.buf.cap ? GYS_OK : nb.buf.grow(q.buf_bytes, 0);
-			hipError_t e = hipSuccess;
-			if (!arc && !nb.done) e = hipEventCreateWithFlags(&nb.done, hipEventDisableTiming);
-			if (!arc && e == hipSuccess && !nb.copied) e = hipEventCreateWithFlags(&nb.copied, hipEventDisableTiming);
-			if (e != hipSuccess) {
-				set_err("%s batch events: %s", q.word(), hipGetErrorString(e));
-				arc = GYS_ERR_HIP;
-			}
-			lk.lock();
-			if (arc) {
-				q.free.push_back(bi);
-				q.cv.notify_all();
-				return arc;
-			}
-			if (q.open >= 0) { // another caller opened one meanwhile
-				q.free.push_front(bi);
-				q.cv.notify_all();
-				continue;
-			}
-			q.open = bi;
-			++q.stamp;
-		}
-		bi = q.open;
-		const SubQ::Batch &ob = q.b[bi];
-		if (ob.fill + need <= q.cap && (resp ? q.host_stamp[host] != q.stamp : ob.nrec + n <= q.cap_recs)) break;
-		// no room, or the host already has a segment in this batch: seal it (submitted before anything opened later)
-		q.sealed.push_back(bi);
-		q.open = -1;
-		(void)subq_drain(c, q, lk, -1, false); // (no batch of this caller's yet: errors are parked, the result is always GYS_OK)
-	}
-	SubQ::Batch &b = q.b[bi];
-	const uint64_t at = b.fill;
-	const uint32_t r0 = b.nrec;
-	b.fill += need;
-	if (resp) {
-		b.segs.push_back(gys_resp_seg{host, 0, at});
-		q.host_stamp[host] = q.stamp;
-	} else {
-		b.nrec += n;
-	}
-	b.writers++;
-	lk.unlock();
-	if (resp) {
-		memcpy(b.buf.host + at * 24, data, (uint64_t)n * 24);
-	} else {
-		memcpy(b.buf.host + at, data, bytes);
-		uint32_t *o = (uint32_t *)(b.buf.host + q.cap) + r0;
-		for (uint32_t i = 0; i < n; ++i) o[i] = offs[i] + (uint32_t)at;
-		if (q.kind == SubQ::LSTATE) std::fill_n(o + q.cap_recs, n, host);
-	} // the caller's buffer is free from here on
-	lk.lock();
-	b.writers--;
-	if (b.writers == 0) q.cv.notify_all();
-	int rc = subq_drain(c, q, lk, bi, false);
-	if (q.open >= 0 && q.b[q.open].fill) q.fcv.notify_one(); // data stays behind in the open batch: the flusher sees to it if no call follows
-	if (!rc) rc = subq_parked_error(q);
-	return rc;
+	if (kind == SubQ::RESP) return run_resp_batch(c, segs.data(), (uint32_t)segs.size(), dev, fill);
+	const SubQ &q = c->sq[kind];
+	const uint32_t *d_offs = (const uint32_t *)(dev + q.cap);
+	return kind == SubQ::CONN ? run_conn(c, dev, d_offs, nrec) : run_lstate(c, dev, d_offs, d_offs + q.cap_recs, 0, nrec);
 }
 
 // a record message: combined with the other callers' pending messages, unless it has many messages' size (a replayed backlog) -- then on
@@ -1818,38 +1436,37 @@ int ingest_records(gys_ctx *c, SubQ &q, uint32_t host, const void *batch, const 
 {
 	const uint64_t bytes = (uint64_t)((const uint8_t *)pend - (const uint8_t *)batch);
 	const uint32_t n = (uint32_t)offs.size();
-	if (align_up(bytes, 8) <= q.cap / 2 && n <= q.cap_recs / 2) return subq_ingest(c, q, host, batch, bytes, n, offs.data());
-	const int rc = subq_flush(c, q);
-	return rc ? rc : ingest_staged_records(c, host, batch, bytes, offs, q.kind == SubQ::CONN);
+	if (align_up(bytes, 8) <= q.cap / 2 && n <= q.cap_recs / 2) return subq_ingest(c->ingest, q, host, c->hosts.size(), batch, bytes, n, offs.data());
+	const int rc = subq_flush(c->ingest, q);
+	if (rc) return rc;
+	// one pinned copy, one H2D copy on the copy stream (records, then the offsets behind them), the ingest kernel, no wait
+	const uint64_t off_at = align_up(bytes, 8);
+	return stage_call(
+		c->ingest, c->ring, off_at + (uint64_t)n * 4,
+		[&](uint8_t *pinned) {
+			memcpy(pinned, batch, bytes);
+			memcpy(pinned + off_at, offs.data(), (uint64_t)n * 4);
+		},
+		true, "ingest",
+		[&](const uint8_t *dev) {
+			const uint32_t *d_offs = (const uint32_t *)(dev + off_at);
+			return q.kind == SubQ::CONN ? run_conn(c, dev, d_offs, n) : run_lstate(c, dev, d_offs, nullptr, host, n);
+		});
 }
 
 // a response call as its own submission through the staging ring, behind whatever the response queue holds (same-host calls keep their
 // order: a service's per-call value multisets keep the order of the calls); `fn`: the entry point, for the error text
 int ingest_staged_resp(gys_ctx *c, uint32_t host, const void *ev, uint32_t nevents, uint32_t evsize, bool v6, const char *fn)
 {
-	int rc = subq_flush(c, c->sq[SubQ::RESP]);
+	const int rc = subq_flush(c->ingest, c->sq[SubQ::RESP]);
 	if (rc) return rc;
 	const uint64_t bytes = (uint64_t)nevents * evsize;
-	int si;
-	rc = stage_acquire(c, bytes, &si);
-	if (rc) return rc;
-	gys_ctx::Stage &st = c->stage[si];
-	memcpy(st.buf.host, ev, bytes); // the caller's buffer is free from here on
-	{
-		std::lock_guard<std::mutex> g(c->enq_mu);
-		hipError_t e = hipMemcpyAsync(st.buf.dev, st.buf.host, bytes, hipMemcpyHostToDevice, c->stream);
-		if (e == hipSuccess) {
+	return stage_call(
+		c->ingest, c->ring, bytes, [&](uint8_t *pinned) { memcpy(pinned, ev, bytes); }, false, fn,
+		[&](const uint8_t *dev) {
 			gys_resp_seg seg{host, 0, 0};
-			rc = run_resp_batch(c, &seg, 1, st.buf.dev, nevents, v6);
-			e = hipEventRecord(st.done, c->stream);
-		}
-		if (e != hipSuccess) {
-			set_err("%s: %s", fn, hipGetErrorString(e));
-			rc = GYS_ERR_HIP;
-		}
-	}
-	stage_release(c, si);
-	return rc;
+			return run_resp_batch(c, &seg, 1, dev, nevents, v6);
+		});
 }
 
 } // namespace
@@ -1871,7 +1488,7 @@ int ingest_staged_resp(gys_ctx *c, uint32_t host, const void *ev, uint32_t neven
 		GYS_ENTER_NOFLUSH(c);                                          \
 		if (c)                                                         \
 			for (auto &q_ : (c)->sq) {                             \
-				const int rcq_ = subq_flush(c, q_);            \
+				const int rcq_ = subq_flush((c)->ingest, q_);  \
 				if (rcq_) return rcq_;                         \
 			}                                                      \
 	} while (0)
@@ -1933,9 +1550,7 @@ try {
 		(void)hipGetLastError();
 	});
 	gys_ctx *c = guard.get();
-	for (int i = 0; i < gys_ctx::NSTAGE; ++i) c->stage_free.push_back(i);
 	c->cfg = *cfg;
-	for (SubQ::Kind k : {SubQ::RESP, SubQ::CONN, SubQ::LSTATE}) subq_init(c, k);
 	if (cfg->device >= 0) {
 		c->device = cfg->device;
 		HIPCHK(hipSetDevice(c->device));
@@ -1952,6 +1567,15 @@ try {
 		c->own_stream = true;
 	}
 	HIPCHK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking)); // H2D copies of the host-pointer submissions
+	c->ingest.device = c->device;
+	c->ingest.stream = c->stream;
+	c->ingest.copy_stream = c->copy_stream;
+	c->ingest.enq_mu = &c->enq_mu;
+	c->ingest.max_batch_events = cfg->max_batch_events;
+	c->ingest.launch = [c](SubQ::Kind kind, const uint8_t *dev, uint64_t fill, uint32_t nrec, const std::vector<gys_resp_seg> &segs) {
+		return launch_batch(c, kind, dev, fill, nrec, segs);
+	};
+	for (SubQ::Kind k : {SubQ::RESP, SubQ::CONN, SubQ::LSTATE}) subq_init(c->ingest, c->sq[k], k);
 	const uint64_t S = cfg->max_services, H = cfg->max_hosts;
 	const uint32_t cap = next_pow2(S * 2);
 	int rc;
@@ -2157,36 +1781,20 @@ void gys_destroy(gys_ctx *c)
 {
 	if (c) (void)hipSetDevice(c->device);
 	if (!c) return;
-	for (auto &q : c->sq) {
-		if (!q.flusher_on) continue;
-		{
-			std::lock_guard<std::mutex> g(q.mu);
-			q.stop = true;
+	// the flushers joined, the stream drained, the graphs and then the events destroyed, the streams last
+	ingest_teardown(c->sq, 3, c->ring, [c] {
+		if (c->stream) hipStreamSynchronize(c->stream);
+		if (c->win_graph_exec) hipGraphExecDestroy(c->win_graph_exec);
+		if (c->win_graph) hipGraphDestroy(c->win_graph);
+		for (auto &cg : c->close_graph) {
+			if (cg.x) hipGraphExecDestroy(cg.x);
+			if (cg.g) hipGraphDestroy(cg.g);
 		}
-		q.fcv.notify_all();
-		if (q.flusher.joinable()) q.flusher.join();
-		q.flusher_on = false;
-	}
-	if (c->stream) hipStreamSynchronize(c->stream);
-	if (c->win_graph_exec) hipGraphExecDestroy(c->win_graph_exec);
-	if (c->win_graph) hipGraphDestroy(c->win_graph);
-	for (auto &cg : c->close_graph) {
-		if (cg.x) hipGraphExecDestroy(cg.x);
-		if (cg.g) hipGraphDestroy(cg.g);
-	}
-	for (auto &sl : c->seg_ring) {
-		if (sl.done) hipEventDestroy(sl.done);
-	}
-	for (auto &q : c->sq)
-		for (auto &b : q.b) {
-			if (b.done) hipEventDestroy(b.done);
-			if (b.copied) hipEventDestroy(b.copied);
+		for (auto &sl : c->seg_ring) {
+			if (sl.done) hipEventDestroy(sl.done);
 		}
+	});
 	if (c->copy_stream) hipStreamDestroy(c->copy_stream);
-	for (auto &st : c->stage) {
-		if (st.done) hipEventDestroy(st.done);
-		if (st.copied) hipEventDestroy(st.copied);
-	}
 	prof_resolve(c);
 	if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
 	delete c; // (frees all device and pinned memory: the members' destructors)
@@ -2620,7 +2228,7 @@ try {
 	if (rc) return rc;
 	if (!nevents) return GYS_OK;
 	if ((uint64_t)nevents <= std::min<uint64_t>(GYS_RQ_EVENTS, c->cfg.max_batch_events))
-		return subq_ingest(c, c->sq[SubQ::RESP], host, ev24, 0, nevents, nullptr); // combined with the other callers' pending calls
+		return subq_ingest(c->ingest, c->sq[SubQ::RESP], host, c->hosts.size(), ev24, 0, nevents, nullptr); // combined with the other callers' pending calls
 	return ingest_staged_resp(c, host, ev24, nevents, 24, false, "gys_ingest_resp_events"); // larger than a combined batch
 } GYS_CATCH_ALL
 
@@ -2696,25 +2304,9 @@ try {
 	const uint32_t n = (uint32_t)std::min<uint64_t>(nitems, avail);
 	if (!n) return GYS_OK;
 	const uint64_t bytes = (uint64_t)n * 104u;
-	int si;
-	rc = stage_acquire(c, bytes, &si);
-	if (rc) return rc;
-	gys_ctx::Stage &st = c->stage[si];
-	memcpy(st.buf.host, batch, bytes);
-	{
-		std::lock_guard<std::mutex> g(c->enq_mu);
-		hipError_t e = hipMemcpyAsync(st.buf.dev, st.buf.host, bytes, hipMemcpyHostToDevice, c->stream);
-		if (e == hipSuccess) {
-			rc = run_actconn(c, st.buf.dev, n);
-			e = hipEventRecord(st.done, c->stream);
-		}
-		if (e != hipSuccess) {
-			set_err("gys_ingest_active_conns: %s", hipGetErrorString(e));
-			rc = GYS_ERR_HIP;
-		}
-	}
-	stage_release(c, si);
-	return rc;
+	return stage_call(
+		c->ingest, c->ring, bytes, [&](uint8_t *pinned) { memcpy(pinned, batch, bytes); }, false, "gys_ingest_active_conns",
+		[&](const uint8_t *dev) { return run_actconn(c, dev, n); });
 } GYS_CATCH_ALL
 
 int gys_ingest_listener_state(gys_ctx *c, const uint8_t machine_id[16], const void *batch, uint32_t nrecs, const void *pend)
@@ -4383,7 +3975,7 @@ try {
 	out->actconn_records = v[CTR_ACTCONN_RECORDS];
 	out->actconn_remote_listen = v[CTR_ACTCONN_REMOTE_LISTEN];
 	out->actconn_unknown_listener = v[CTR_ACTCONN_UNKNOWN];
-	out->stage_waits = c->stage_waits.load();
+	out->stage_waits = c->ring.waits.load();
 	auto snap = [](SubQ &q, uint64_t *calls, uint64_t *submissions) {
 		std::lock_guard<std::mutex> g(q.mu);
 		*calls = q.calls;

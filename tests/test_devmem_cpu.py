@@ -20,7 +20,8 @@ KEMU = os.path.join(ROOT, "tests", "cpp", "kemu")
 ALLOC_CALLS = ("hipMalloc(", "hipFree(", "hipHostMalloc(", "hipHostFree(")
 
 # gys_ctx members that may be declared `= nullptr`: VIEWS and runtime handles, none of which owns memory
-RAW_POINTER_VIEWS = {("uint8_t", "arena")}  # the caller's reduce arena, or arena_own
+RAW_POINTER_VIEWS = {("uint8_t", "arena"),  # the caller's reduce arena, or arena_own
+                     ("std::mutex", "enq_mu")}  # IngestEnv: the context's own enqueue mutex
 HANDLE_TYPES = {"hipStream_t", "hipGraph_t", "hipGraphExec_t", "hipEvent_t"}  # destroyed explicitly, in order, by gys_destroy
 HANDLES = {("hipStream_t", "stream"), ("hipStream_t", "copy_stream"), ("hipGraph_t", "win_graph"), ("hipGraphExec_t", "win_graph_exec"),
            ("hipGraph_t", "g"), ("hipGraphExec_t", "x"), ("hipEvent_t", "done"), ("hipEvent_t", "copied")}
@@ -40,12 +41,24 @@ def test_destroy_has_no_free_list():
     assert "ptrs[]" not in _src("gys_engine.hip")
 
 
-def _ctx_body():
-    s = _src("gys_engine.hip")
-    a = s.index("struct gys_ctx {")
+# the structs of gys_subq.hpp that gys_ctx holds by value (the submission queues, the staging ring, what both use of the context): their
+# members are members of the context
+SUBQ_STRUCTS = ("SubQ", "IngestEnv", "Stage", "StageRing")
+
+
+def _struct_body(s, head):
+    a = s.index(head)
     b = s.index("\n};\n", a)  # (the struct's own closing brace is the first one in column 0)
-    body = re.sub(r"//[^\n]*", "", s[a + len("struct gys_ctx {"):b])
+    body = re.sub(r"//[^\n]*", "", s[a + len(head):b])
     return re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+
+
+def _ctx_body():
+    body = _struct_body(_src("gys_engine.hip"), "struct gys_ctx {")
+    for name in SUBQ_STRUCTS:
+        assert re.search(r"\b%s \w+(\[\w*\])?;" % name, body) or name == "Stage", name  # (Stage: inside StageRing)
+        body += ";" + _struct_body(_src("gys_subq.hpp"), "struct %s {" % name)
+    return body
 
 
 def test_ctx_members_are_owners_or_listed_views():

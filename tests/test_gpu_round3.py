@@ -91,20 +91,23 @@ def test_resp_calls_from_16_threads_are_combined_and_bit_exact(torch_mod, oracle
 
 
 def test_staging_ring_is_fifo(torch_mod, oracle):
-    """gys_ingest_listener_state / _tcp_conn copy into a ring of 16 pinned slots; a slot is taken oldest first, so a burst shorter
-    than the ring never waits for the GPU (gys_counters.stage_waits)"""
+    """gys_ingest_active_conns (like an oversize record message and an IPv6 response call) copies into a ring of 16 pinned slots; a slot
+    is taken oldest first, so a burst shorter than the ring never waits for the GPU (gys_counters.stage_waits).  The listener-state and
+    connection messages of ordinary size go through their submission queues instead (tests/test_gpu_round4.py)."""
     nh, sp = 4, 16
     eng = _engine(max_hosts=nh, max_services=nh * sp, enable_tdigest=False)
     info, gids = helpers.register_world(eng, None, range(nh), sp)
     rng = np.random.default_rng(5)
-    recs = [wire.synth_listener_states(rng, h, np.arange(sp)) for h in range(nh)]
+    recs = [wire.synth_active_conns(rng, 64, h, sp, remote_listen_frac=0.0) for h in range(nh)]
     eng.sync()
-    w0 = eng.counters()["stage_waits"]
+    c0 = eng.counters()
     for i in range(12):
         h = i % nh
-        eng.partha_listener_state(info[h][0], recs[h].tobytes(), sp)
+        eng.handle_partha_active_conns(info[h][0], recs[h].tobytes(), len(recs[h]))
     eng.sync()
-    assert eng.counters()["stage_waits"] == w0
+    c1 = eng.counters()
+    assert c1["stage_waits"] == c0["stage_waits"]
+    assert c1["actconn_records"] - c0["actconn_records"] == 12 * 64  # (the calls did go through the ring and were ingested)
     eng.close()
 
 

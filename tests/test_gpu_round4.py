@@ -470,6 +470,49 @@ def test_conn_and_listener_state_calls_from_16_threads_are_combined_and_equal_se
         e.close()
 
 
+def test_oversize_record_message_goes_through_the_ring_behind_the_queue(oracle):
+    """A record message above half a combined batch (more than 2 MiB of listener states, more than 8 MiB of connections: a replayed
+    backlog) is not queued: the queue is flushed and the message goes on its own through the staging ring.  One host sends a small
+    message (queued), an oversize one, a small one again; the state must equal the same records sent as small messages one by one --
+    "the last record of a listener wins" holds across the queue -> ring -> queue boundary -- and the oversize call is not counted as queued."""
+    from gyeeta_amd.engine import SketchEngine
+    sp = 64
+    rng = np.random.default_rng(123)
+    engs = [SketchEngine(max_hosts=2, max_services=2 * sp, enable_tdigest=False) for _ in range(2)]
+    mids = [helpers.register_world(e, None, range(2), sp)[0][0][0] for e in engs]
+    nbig_ls, nbig_conn = 23832, 29960  # 2 097 216 and 8 388 800 bytes: just above the queues' half capacities (and half record counts)
+    ls = [wire.synth_listener_states(rng, 0, np.arange(n) % sp, delete_frac=0.01, bad_state_frac=0.01) for n in (sp, nbig_ls, sp)]
+    conn = [wire.synth_tcp_conns(rng, n, [0], sp, dup_frac=0.2, v6_frac=0.1) for n in (700, nbig_conn, 700)]
+    assert ls[1].nbytes == 2097216 and conn[1].nbytes == 8388800
+    for name, msgs, send, small in (("lstate", ls, "partha_listener_state", 512), ("conn", conn, "partha_tcp_conn_info", 2048)):
+        before = engs[0].counters()
+        for m in msgs:  # (no other call in between: the first message is still in the queue when the oversize one arrives)
+            getattr(engs[0], send)(mids[0], m.tobytes(), len(m))
+        after = engs[0].counters()
+        assert after[name + "_calls_queued"] - before[name + "_calls_queued"] == 2, name  # the two small ones: the oversize one was not queued
+        allrec = np.concatenate(msgs)
+        for i in range(0, len(allrec), small):
+            getattr(engs[1], send)(mids[1], allrec[i:i + small].tobytes(), len(allrec[i:i + small]))
+    c0, c1 = engs[0].counters(), engs[1].counters()
+    for k in ("conn_events", "conn_unknown_service", "conn_new", "conn_closed", "conn_closed_no_notify", "conn_client_side",
+              "lstate_records", "lstate_missed", "lstate_errors", "lstate_deleted"):
+        assert c0[k] == c1[k], k
+    assert c0["lstate_records"] == nbig_ls + 2 * sp and c0["conn_events"] == nbig_conn + 1400
+    s0, h0, r0, n0 = engs[0].svcstate_scan(maxrecs=2 * sp + 10)
+    s1, h1, r1, n1 = engs[1].svcstate_scan(maxrecs=2 * sp + 10)
+    assert n0 == n1 == len(s0) == len(s1) and n0 > 0.8 * sp
+    assert (s0 == s1).all() and (h0 == h1).all() and r0.tobytes() == r1.tobytes()
+    for e in engs:
+        e.window_close()
+    assert (engs[0].export_hll() == engs[1].export_hll()).all()
+    for w in (0, 1):
+        assert (engs[0].export_cms(w) == engs[1].export_cms(w)).all()
+    assert (engs[0].export_svc_counters() == engs[1].export_svc_counters()).all()
+    assert engs[0].svcsumm(mids[0]).as_tuple() == engs[1].svcsumm(mids[1]).as_tuple()
+    for e in engs:
+        e.close()
+
+
 def test_service_name_criterion_resolves_to_service_ids():
     """gys_svc_ids_by_name: the reference's string comparators on the service name (CRITERION_ONE::match_str_criterian,
     common/gy_query_criteria.h:1335-1383: = / != whole name, substr / notsubstr memmem, like / notlike a regular expression matched
