@@ -2078,11 +2078,23 @@ __global__ __launch_bounds__(NT) void k_digest_merge(MergeP q)
 #define GYS_MB_BINS 2048u // 1024 one-value bins + 10 octaves x 64 cells (values < 2^20), padded to 8 bins per thread
 #define GYS_MB_BPT 8u
 
-__device__ __forceinline__ uint32_t mb_bin(uint32_t v)
+// the bin of a value by its bit pattern: 1024 + (msb - 10) * 64 + the six bits below the msb (v >= 1024)
+__device__ __forceinline__ uint32_t mb_bin_clz(uint32_t v)
 {
 	if (v < GYS_MB_EXACT) return v;
 	const uint32_t msb = 31u - (uint32_t)__clz((int)v);
 	return GYS_MB_EXACT + (msb - 10u) * 64u + ((v >> (msb - 6u)) & 63u);
+}
+
+// The same bin through the float conversion, for v < 2^24 (exact as a float; the merge's values and cluster thresholds are at most 1 000 000): the
+// exponent field is 127 + msb and the top six mantissa bits are the cell, so (bits >> 17) - (127 + 10) * 64 + 1024 is the formula above -- one
+// conversion, one shift and one add in place of clz, two subtractions, two shifts, an and and an add (tests/cpp/kemu/test_bins_edges.cc compares
+// the two forms for every v < 2^20; the merge kernel 2.889 -> 2.823 ms per window, profiles/r8a_merge_kernel_ab.txt).  A value that may be larger
+// (rb_bin of gys_rollup.hpp: 26 bits) keeps mb_bin_clz: the conversion would round.
+__device__ __forceinline__ uint32_t mb_bin(uint32_t v)
+{
+	if (v < GYS_MB_EXACT) return v;
+	return (__builtin_bit_cast(uint32_t, (float)v) >> 17) - 7744u;
 }
 
 struct MergeBP {
@@ -2172,7 +2184,7 @@ __global__ __launch_bounds__(256, (VPT == 16u ? GYS_MB_WAVES16 : 8)) void k_dige
 	// does for 64-bit weights -- the scan of 10^7 services takes 61 instead of 78 ms, r6aj.  A service is listed when more than 1 024 of its buffered
 	// values are a second or longer.)
 	constexpr uint32_t BIG_CAP = GYS_MB_BIG_CAP;
-	__shared__ uint32_t s_big[BIG_CAP]; // values >= GYS_MB_EXACT: index << 20 | value
+	__shared__ __align__(16) uint32_t s_big[BIG_CAP]; // values >= GYS_MB_EXACT: index << 20 | value (read four at a time by the comparison loops)
 	__shared__ uint32_t s_thr[GYS_NBP];          // compacted non-empty old clusters: ceil(sum / count), padded with ~0
 	__shared__ uint32_t s_cpfx[GYS_NBP + 1];     // old weight before compacted cluster c
 	__shared__ uint32_t s_T[GYS_NBP];            // T_j, j = 1..NB-1; [0] = 0, [NB..] = ~0
@@ -2389,12 +2401,34 @@ __global__ __launch_bounds__(256, (VPT == 16u ? GYS_MB_WAVES16 : 8)) void k_dige
 #pragma unroll
 			for (uint32_t k = 0; k < GYS_MB_BPT; ++k) own += bv[k];
 			const uint32_t sc = wave_incl_scan_u32(own);
-			if (lane == 63u) s_ws[wave] = sc;
+			// the list of the non-empty one-value bins for pass 2 (see there) is built HERE: the owner of bins 8t .. 8t + 7 holds their raw counts, so
+			// the waves that own one-value bins (threads 0 .. 127: wave-uniform) scan their non-empty counts as well; the wave totals go to s_wv
+			// (last read behind the first barrier of the merge).  2.969 -> 2.889 ms per window, profiles/r8a_merge_kernel_ab.txt.
+			uint32_t ne_own = 0, ne_sc = 0;
+			if (GYS_MB_BPT * 64u * wave < GYS_MB_EXACT) {
+#pragma unroll
+				for (uint32_t k = 0; k < GYS_MB_BPT; ++k) ne_own += (bv[k] & 0xFFFFu) ? 1u : 0u;
+				ne_sc = wave_incl_scan_u32(ne_own);
+			}
+			if (lane == 63u) {
+				s_ws[wave] = sc;
+				s_wv[wave] = ne_sc;
+			}
 			__syncthreads();
 			uint32_t run = sc - own;
 #pragma unroll
 			for (uint32_t k = 0; k < 3u; ++k)
 				if (k < wave) run += s_ws[k];
+			if (GYS_MB_BPT * 64u * wave < GYS_MB_EXACT && s_nbig <= BIG_CAP / 2u) { // (s_nbig is final behind pass 1's barrier; the list's room: see pass 2)
+				uint16_t *const s_ne = (uint16_t *)(s_big + BIG_CAP / 2u);
+				uint32_t at = ne_sc - ne_own;
+#pragma unroll
+				for (uint32_t k = 0; k < (GYS_MB_EXACT / (GYS_MB_BPT * 64u)) - 1u; ++k)
+					if (k < wave) at += s_wv[k];
+#pragma unroll
+				for (uint32_t k = 0; k < GYS_MB_BPT; ++k)
+					if (bv[k] & 0xFFFFu) s_ne[at++] = (uint16_t)(GYS_MB_BPT * tid + k);
+			}
 			unsigned long long acc0 = 0, acc1 = 0; // GY_HISTOGRAM::add_data for cnt values equal to `bin`, per bucket of the thread's bins
 #pragma unroll
 			for (uint32_t k = 0; k < GYS_MB_BPT; ++k) {
@@ -2421,11 +2455,18 @@ __global__ __launch_bounds__(256, (VPT == 16u ? GYS_MB_WAVES16 : 8)) void k_dige
 		if (has_old) {
 			uint32_t nb = s_bin[mb_bin(thr)] & 0xFFFFu;
 			if (thr >= GYS_MB_EXACT) {
+				// the large values of the threshold's cell below it: lo <= u < thr, as ONE unsigned comparison of u - lo; four list entries per LDS read
+				// (the loop is a chain of LDS round trips, one per entry before: this placement and the large values' below were 1.0 ms of the kernel's
+				// 2.9, profiles/r8a_phase_timing_by_skipping.txt; with both loops in this form 2.988 -> 2.610 ms, profiles/r8a_merge_kernel_ab.txt)
 				const uint32_t sh = (31u - (uint32_t)__clz((int)thr)) - 6u;
-				for (uint32_t j = 0; j < nbig; ++j) {
-					const uint32_t u = s_big[j] & 0xFFFFFu;
-					nb += ((u >> sh) == (thr >> sh) && u < thr) ? 1u : 0u;
+				const uint32_t lo = (thr >> sh) << sh, span = thr - lo;
+				const uint32_t n4 = nbig & ~3u;
+				for (uint32_t j = 0; j < n4; j += 4u) {
+					const uint4 e4 = *(const uint4 *)&s_big[j];
+					nb += ((e4.x & 0xFFFFFu) - lo < span ? 1u : 0u) + ((e4.y & 0xFFFFFu) - lo < span ? 1u : 0u) + ((e4.z & 0xFFFFFu) - lo < span ? 1u : 0u) +
+					      ((e4.w & 0xFFFFFu) - lo < span ? 1u : 0u);
 				}
+				for (uint32_t j = n4; j < nbig; ++j) nb += (s_big[j] & 0xFFFFFu) - lo < span ? 1u : 0u;
 			}
 			const uint32_t mid2 = 2u * (e0 + nb) + c0;
 			uint32_t a = 0;
@@ -2445,35 +2486,20 @@ __global__ __launch_bounds__(256, (VPT == 16u ? GYS_MB_WAVES16 : 8)) void k_dige
 		constexpr uint32_t MBG = SCAN ? 1u : GYS_MB_GROUP; // (the scan form sits at 63 VGPRs: left as it was)
 		// Round 5: of the 1 024 one-value bins a merge touches ~200 - 400 (integer-millisecond response times repeat), spread so that every
 		// wave of every one of the four rounds below has some non-empty bin among its 64 -- each round then runs the 8-step threshold search
-		// for the whole wave.  The non-empty bins are compacted first (four ballots per thread, wave totals through LDS, a 16-bit list in
-		// the unused upper half of the large-value list): ~300 bins are 5 wave-rounds instead of 16.  The kernel is bound by VALU issue
-		// (DESIGN 10): the instructions saved are time saved.  (A merge with more than half of the list's room in large values keeps the plain form.)
+		// for the whole wave.  The non-empty bins are compacted first (a 16-bit list in the unused upper half of the large-value list):
+		// ~300 bins are 5 wave-rounds instead of 16.  The kernel is bound by VALU issue: the instructions saved are time saved.
+		// (A merge with more than half of the list's room in large values keeps the plain form.)
+		//   The list is written by the bin scan above, from the raw counts its threads hold (until then a phase of its own here: two bin words
+		// re-read per bin, four ballots per thread, wave totals and the list behind a barrier each -- table: profiles/r8a_merge_kernel_ab.txt).
+		// It is in bin order per owner instead of per round of 256 bins; the adds into s_oval below are commutative integer adds.
 		const bool compact = MBG == 1u && nbig <= BIG_CAP / 2u;
 		if (compact) {
-			uint16_t *const s_ne = (uint16_t *)(s_big + BIG_CAP / 2u); // [<= 1024] bin numbers
-			const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
-			uint32_t tw = 0, pos[4];
-			bool ne[4];
+			const uint16_t *const s_ne = (const uint16_t *)(s_big + BIG_CAP / 2u); // [<= 1024] bin numbers
+			uint32_t n_ne = 0;
+			if (!(GYS_MB_SKIP & (1 | 8))) {
 #pragma unroll
-			for (uint32_t k = 0; k < 4u; ++k) {
-				const uint32_t b = tid + 256u * k;
-				ne[k] = !(GYS_MB_SKIP & 1) && ((s_bin[b + 1u] ^ s_bin[b]) & 0xFFFFu) != 0u; // (the low halves are running counts: different = the bin holds values)
-				const unsigned long long bal = __ballot(ne[k]);
-				pos[k] = tw + (uint32_t)__popcll(bal & below);
-				tw += (uint32_t)__popcll(bal);
+				for (uint32_t k = 0; k < GYS_MB_EXACT / (GYS_MB_BPT * 64u); ++k) n_ne += s_wv[k];
 			}
-			if (lane == 0u) s_ws[wave] = tw; // (the scan's wave sums were consumed before the barrier above)
-			__syncthreads();
-			uint32_t base = 0, n_ne = 0;
-#pragma unroll
-			for (uint32_t k = 0; k < 4u; ++k) {
-				if (k < wave) base += s_ws[k];
-				n_ne += s_ws[k];
-			}
-#pragma unroll
-			for (uint32_t k = 0; k < 4u; ++k)
-				if (ne[k]) s_ne[base + pos[k]] = (uint16_t)(tid + 256u * k);
-			__syncthreads();
 			for (uint32_t i = tid; i < n_ne; i += 256u) {
 				const uint32_t b = s_ne[i];
 				const uint32_t bw = s_bin[b];
@@ -2532,12 +2558,28 @@ __global__ __launch_bounds__(256, (VPT == 16u ? GYS_MB_WAVES16 : 8)) void k_dige
 		// the (few) large values, one per thread from the list: rank inside the cell by comparison with the other large values, gap by
 		// search over the cluster thresholds
 		for (uint32_t j = tid; j < ((GYS_MB_SKIP & 2) ? 0u : nbig); j += 256u) {
-			const uint32_t me = s_big[j], uv = me & 0xFFFFFu, i = me >> 20;
+			const uint32_t me = s_big[j], uv = me & 0xFFFFFu;
 			const uint32_t sh = (31u - (uint32_t)__clz((int)uv)) - 6u;
 			uint32_t r = s_bin[mb_bin(uv)] & 0xFFFFu;
-			for (uint32_t jj = 0; jj < nbig; ++jj) {
-				const uint32_t e = s_big[jj], u = e & 0xFFFFFu;
-				r += ((u >> sh) == (uv >> sh) && (u < uv || (u == uv && (STREAM ? jj < j : (e >> 20) < i)))) ? 1u : 0u;
+			if (STREAM) {
+				for (uint32_t jj = 0; jj < nbig; ++jj) {
+					const uint32_t e = s_big[jj], u = e & 0xFFFFFu;
+					r += ((u >> sh) == (uv >> sh) && (u < uv || (u == uv && jj < j))) ? 1u : 0u;
+				}
+			} else {
+				// the entries of the value's cell that rank before it: (u, index) < (uv, i) with u >= the cell's first value lo.  An entry rotated left
+				// by 12 bits is {u : 20 | index : 12}, so that is ONE unsigned comparison of key - (lo << 12); four list entries per LDS read
+				const uint32_t base = ((uv >> sh) << sh) << 12, span = ((me << 12) | (me >> 20)) - base;
+				const uint32_t n4 = nbig & ~3u;
+				for (uint32_t jj = 0; jj < n4; jj += 4u) {
+					const uint4 e4 = *(const uint4 *)&s_big[jj];
+					r += ((((e4.x << 12) | (e4.x >> 20)) - base < span) ? 1u : 0u) + ((((e4.y << 12) | (e4.y >> 20)) - base < span) ? 1u : 0u) +
+					     ((((e4.z << 12) | (e4.z >> 20)) - base < span) ? 1u : 0u) + ((((e4.w << 12) | (e4.w >> 20)) - base < span) ? 1u : 0u);
+				}
+				for (uint32_t jj = n4; jj < nbig; ++jj) {
+					const uint32_t e = s_big[jj];
+					r += (((e << 12) | (e >> 20)) - base < span) ? 1u : 0u;
+				}
 			}
 			uint32_t gap = 0;
 #pragma unroll

@@ -92,7 +92,7 @@ __device__ __forceinline__ uint32_t ceil_div_wide(uint64_t sum, uint64_t cnt)
 	return f > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)f;
 }
 
-__device__ __forceinline__ uint32_t rb_bin(uint32_t v) { return mb_bin(v < (1u << 26) ? v : (1u << 26) - 1u); } // (a staged word carries 26 value bits)
+__device__ __forceinline__ uint32_t rb_bin(uint32_t v) { return mb_bin_clz(v < (1u << 26) ? v : (1u << 26) - 1u); } // (a staged word carries 26 value bits)
 
 #if GYS_RB_WAVES
 __global__ __launch_bounds__(GYS_RB_NT, GYS_RB_WAVES) void k_rollup_accum(RollupP q)
@@ -385,7 +385,7 @@ __global__ __launch_bounds__(GYS_RB_NT) void k_rollup_refine(RollupP q)
 		const uint8_t *mark = (const uint8_t *)s_mark;
 		auto put = [&](uint32_t v, uint64_t cn, uint64_t sm) {
 			v = min(v, (1u << 26) - 1u);
-			const uint32_t b = mb_bin(v), m = mark[b];
+			const uint32_t b = mb_bin_clz(v), m = mark[b];
 			if (m) {
 				const uint32_t cell = (m - 1u) * per + rb_cell(v, b, per);
 				atomicAdd(&f_cnt[cell], (unsigned long long)cn);
