@@ -281,6 +281,13 @@ SIGNATURES = {
     "gys_export_global_hist": (C.c_int, [vp, C.POINTER(HistRec)]),
     "gys_export_svc_hll": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
     "gys_export_svc_hll_level": (C.c_int, [vp, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, vp]),
+    "gys_service_blob_bytes": (C.c_uint64, [vp, C.c_uint32]),
+    "gys_pack_services_dev": (C.c_int, [vp, u64p, C.c_uint32, vp, C.c_uint64]),
+    "gys_unpack_services_dev": (C.c_int, [vp, vp, C.c_uint64, u32p, u32p]),
+    "gys_pack_services": (C.c_int, [vp, u64p, C.c_uint32, vp, C.c_uint64]),
+    "gys_unpack_services": (C.c_int, [vp, vp, C.c_uint64, u32p, u32p]),
+    "gys_list_service_ids": (C.c_int, [vp, C.c_uint32, C.c_uint32, u64p, u32p]),
+    "gys_list_host_service_ids": (C.c_int, [vp, mid, u64p, C.c_uint32, u32p]),
     "gys_get_counters": (C.c_int, [vp, C.POINTER(Counters)]),
     "gys_resp_queue_pending": (C.c_int, [vp, u64p]),
     "gys_hist_init_dev": (C.c_int, [vp, C.c_int, vp, C.c_uint32]),

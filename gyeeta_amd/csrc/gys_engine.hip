@@ -42,6 +42,7 @@
 #include "gys_svcquery.hpp"
 #include "gys_rollsel.hpp"
 #include "gys_svcdel.hpp"
+#include "gys_svcpack.hpp"
 #include "gys_tdrank.hpp"
 #include "gys_topk.hpp"
 
@@ -266,6 +267,7 @@ struct gys_ctx {
 	} close_graph[4];
 	uint64_t close_graph_launches = 0;
 	bool have_last = false;
+	bool clock_adopted = false; // gys_unpack_services took a blob's window number and close times (a context that had not closed a window)
 
 	// host-pointer boundary (gys_subq.hpp): the submission queues of gys_ingest_resp_events / _tcp_conn / _listener_state (indexed by
 	// SubQ::Kind), the ring of pinned staging slots of the calls that go on their own, and what both use of this context (bound at gys_create)
@@ -1868,53 +1870,56 @@ try {
 } GYS_CATCH_ALL
 
 // ------------------------------------------------------------------------------------------------ deleting listeners (gys_svcdel.hpp)
-// every per-service array of the context as k_svc_clear segments, with the contents gys_create leaves
-static void svc_clear_segments(gys_ctx *c, std::vector<SvcClearSeg> &segs)
+// every per-service array of the context as k_svc_clear segments, with the contents gys_create leaves and what a service record does with
+// the array (gys_svcpack.hpp: C carried, CH carried + host word, R reset by the unpack, K kept).  layout: also the arrays the configuration
+// provides for but the context has not allocated yet (base nullptr) -- a record's layout depends on the configuration alone.
+static void svc_clear_segments(gys_ctx *c, std::vector<SvcClearSeg> &segs, bool layout = false)
 {
 	const uint64_t S = c->cfg.max_services;
 	const uint4 zero = make_uint4(0u, 0u, 0u, 0u), ones = make_uint4(~0u, ~0u, ~0u, ~0u);
-	auto add = [&](void *base, uint64_t bytes, uint4 fill, uint4 last) {
-		if (base) segs.push_back(SvcClearSeg{(uint8_t *)base, bytes, fill, last});
+	constexpr uint32_t C = GYS_SVCSEG_CARRY, CH = GYS_SVCSEG_CARRY_HOST, R = GYS_SVCSEG_RESET, K = GYS_SVCSEG_KEEP;
+	auto add = [&](void *base, uint64_t bytes, uint4 fill, uint4 last, uint32_t kind) {
+		if (base || layout) segs.push_back(SvcClearSeg{(uint8_t *)base, bytes, fill, last, kind, 0u});
 	};
 	auto hist = [&](gys_hist_rec *base, int64_t minval) { // zero, max_val_seen (the record's last 8 bytes) = minval
-		add(base, sizeof(gys_hist_rec), zero, make_uint4(0u, 0u, (uint32_t)(uint64_t)minval, (uint32_t)((uint64_t)minval >> 32)));
+		add(base, sizeof(gys_hist_rec), zero, make_uint4(0u, 0u, (uint32_t)(uint64_t)minval, (uint32_t)((uint64_t)minval >> 32)), C);
 	};
-	add(c->svc_gid, 8, zero, zero);
-	add(c->svc_host, 4, ones, ones);
+	add(c->svc_gid, 8, zero, zero, K);
+	add(c->svc_host, 4, ones, ones, K);
 	hist(c->hist_win, INT64_MIN);
 	hist(c->hist_all, INT64_MIN);
-	add(c->bitmap, GYS_BM_WORDS * 4, zero, zero);
-	add(c->svc_ctr, 32, zero, zero);
-	add(c->svc_win, 24, zero, zero);
-	add(c->svc_state, 96, zero, zero);
-	add(c->svc_claim, 8, zero, zero);
-	add(c->svc_act, 32, zero, zero);
-	if (c->svc_hll) add(c->svc_hll, 1ull << c->cfg.svc_hll_p, zero, zero);
+	add(c->bitmap, GYS_BM_WORDS * 4, zero, zero, C);
+	add(c->svc_ctr, 32, zero, zero, C);
+	add(c->svc_win, 24, zero, zero, C);
+	add(c->svc_state, 96, zero, zero, CH);
+	add(c->svc_claim, 8, zero, zero, R);
+	add(c->svc_act, 32, zero, zero, C);
+	if (c->svc_hll) add(c->svc_hll, 1ull << c->cfg.svc_hll_p, zero, zero, C);
 	if (c->hl_lvl)
-		for (uint32_t f = 0; f < GYS_HLL_LVL_FILES; ++f) add(hll_level_array(c, f), 1ull << c->cfg.svc_hll_p, zero, zero);
+		for (uint32_t f = 0; f < GYS_HLL_LVL_FILES; ++f) add(hll_level_array(c, f), 1ull << c->cfg.svc_hll_p, zero, zero, C);
 	if (c->cfg.enable_levels) {
-		for (uint32_t j = 0; j < 2 * GYS_LEVEL_RING; ++j) add(c->lvl_snap + (uint64_t)j * S, sizeof(gys_hist_rec), zero, zero);
+		for (uint32_t j = 0; j < 2 * GYS_LEVEL_RING; ++j) add(c->lvl_snap + (uint64_t)j * S, sizeof(gys_hist_rec), zero, zero, C);
 		if (c->cfg.enable_levels == 1) hist(c->lvl_last, INT64_MIN);
-		if (c->cfg.enable_levels == 1 && c->cfg.enable_tdigest) add(c->lvl_last_tag, 4, ones, ones);
-		add(c->lvl_first, 8, zero, zero);
+		if (c->cfg.enable_levels == 1 && c->cfg.enable_tdigest) add(c->lvl_last_tag, 4, ones, ones, C);
+		add(c->lvl_first, 8, zero, zero, C);
 		hist(c->qps_hist, INT32_MIN);
 		hist(c->act_hist, INT32_MIN);
 	}
 	if (c->cfg.enable_tdigest) {
-		add(c->td_sum, GYS_TD_NB * 8ull, zero, zero);
-		add(c->td_cnt, GYS_TD_NB * 4ull, zero, zero);
-		add(c->td_meta, sizeof(TdMeta), zero, zero);
+		add(c->td_sum, GYS_TD_NB * 8ull, zero, zero, C);
+		add(c->td_cnt, GYS_TD_NB * 4ull, zero, zero, C);
+		add(c->td_meta, sizeof(TdMeta), zero, zero, C);
 		const uint4 mm = make_uint4((uint32_t)INT32_MAX, (uint32_t)INT32_MIN, (uint32_t)INT32_MAX, (uint32_t)INT32_MIN);
-		add(c->td_minmax, 8, mm, mm);
-		add(c->td_cur, 4, zero, zero); // (the words of td_pend behind a zero cursor are never read)
-		add(c->td_run, 4, zero, zero);
-		add(c->td_run0, 4, zero, zero);
-		add(c->td_run1, 4, zero, zero);
-		add(c->td_prevm, 4, zero, zero);
-		add(c->resp_win, 4, zero, zero);
+		add(c->td_minmax, 8, mm, mm, C);
+		add(c->td_cur, 4, zero, zero, C); // (the words of td_pend behind a zero cursor are never read)
+		add(c->td_run, 4, zero, zero, R);
+		add(c->td_run0, 4, zero, zero, R);
+		add(c->td_run1, 4, zero, zero, R);
+		add(c->td_prevm, 4, zero, zero, C);
+		add(c->resp_win, 4, zero, zero, C);
 	}
-	add(c->svc_label, 4, ones, ones); // GYS_NO_GROUP
-	add(c->svc_bithist, 2, zero, zero);
+	add(c->svc_label, 4, ones, ones, K); // GYS_NO_GROUP
+	add(c->svc_bithist, 2, zero, zero, C);
 }
 
 // the segment list and the device memory a clear of listed slots needs (staging_bytes: what the caller puts into dev_staging)
@@ -2168,6 +2173,430 @@ uint64_t gys_svc_state_bytes(gys_ctx *c)
 	for (const SvcClearSeg &sg : segs) b += sg.bytes;
 	return b;
 }
+
+// ------------------------------------------------------------------------------------------------ service records (gys_svcpack.hpp)
+namespace {
+
+#define GYS_BLOB_MAGIC 0x42535947u // "GYSB"
+#define GYS_BLOB_VERSION 1u
+#define GYS_BLOB_PIECE (8ull << 20) // the host-pointer forms move the records through the staging buffer in pieces of about this size
+
+// the 64-byte blob header ("service records" in include/gysketch.h gives the offsets)
+struct SvcBlobHdr {
+	uint32_t magic, version;
+	uint32_t enable_tdigest, td_pend_cap, svc_hll_p, svc_hll_levels, enable_levels;
+	uint16_t td_nb, level_ring;
+	uint32_t bm_line_bytes, stride;
+	uint32_t epoch, n;
+	int64_t lvl_t_last, hl_t_last;
+};
+static_assert(sizeof(SvcBlobHdr) == 64, "the blob header is 64 bytes");
+
+// the record layout of this context's configuration: segs with kind / rec_off filled in, and the kernel's parameters but for the list.
+// Carried arrays whose size is a multiple of 16 come first, in list order, then the others (each rounded up to 4 bytes), a pad to 16
+// bytes, the td_pend_cap buffered words (padded to 16 bytes).
+struct SvcRecLayout {
+	std::vector<SvcClearSeg> segs;
+	SvcPackP p{};
+};
+
+int svc_rec_layout(gys_ctx *c, SvcRecLayout &L)
+{
+	L.segs.clear();
+	L.p = SvcPackP{};
+	svc_clear_segments(c, L.segs, true);
+	if (L.segs.size() > GYS_SVCCLEAR_MAXSEG) {
+		set_err("internal error: %zu record segments", L.segs.size());
+		return GYS_ERR_INTERNAL;
+	}
+	uint64_t off = 0;
+	uint32_t cur_off = ~0u;
+	for (int pass = 0; pass < 2; ++pass)
+		for (SvcClearSeg &sg : L.segs) {
+			if (sg.kind < GYS_SVCSEG_CARRY || sg.kind > GYS_SVCSEG_KEEP) { // (an array named in svc_clear_segments without a kind)
+				set_err("internal error: per-service array without a record kind");
+				return GYS_ERR_INTERNAL;
+			}
+			if (sg.kind != GYS_SVCSEG_CARRY && sg.kind != GYS_SVCSEG_CARRY_HOST) continue;
+			if (((sg.bytes & 15ull) == 0) != (pass == 0)) continue;
+			sg.rec_off = (uint32_t)off;
+			if (sg.base && sg.base == (uint8_t *)c->td_cur.p) cur_off = sg.rec_off;
+			off += align_up(sg.bytes, 4);
+		}
+	SvcPackP &p = L.p;
+	p.nsegs = (uint32_t)L.segs.size();
+	p.max_services = c->cfg.max_services;
+	p.pad_off = (uint32_t)off;
+	p.pend_off = (uint32_t)align_up(off, 16);
+	p.stride = p.pend_off;
+	if (c->cfg.enable_tdigest) {
+		if (cur_off == ~0u || c->pend_cap > c->pcap) {
+			set_err("internal error: no cursor in the record layout");
+			return GYS_ERR_INTERNAL;
+		}
+		p.td_pend = c->td_pend;
+		p.td_cur = c->td_cur;
+		p.pcap = c->pcap;
+		p.pend_cap = c->pend_cap;
+		p.cur_off = cur_off;
+		p.stride = (uint32_t)align_up((uint64_t)p.pend_off + 4ull * c->pend_cap, 16);
+	}
+	return GYS_OK;
+}
+
+inline uint64_t blob_ids_bytes(uint32_t n) { return align_up((uint64_t)n * 8, 16); }
+
+void blob_header(gys_ctx *c, const SvcRecLayout &L, uint32_t n, SvcBlobHdr &h)
+{
+	memset(&h, 0, sizeof(h));
+	h.magic = GYS_BLOB_MAGIC;
+	h.version = GYS_BLOB_VERSION;
+	h.enable_tdigest = c->cfg.enable_tdigest ? 1u : 0u;
+	h.td_pend_cap = c->cfg.enable_tdigest ? c->pend_cap : 0u;
+	h.svc_hll_p = c->cfg.svc_hll_p;
+	h.svc_hll_levels = c->cfg.svc_hll_levels ? 1u : 0u;
+	h.enable_levels = c->cfg.enable_levels;
+	h.td_nb = GYS_TD_NB;
+	h.level_ring = GYS_LEVEL_RING;
+	h.bm_line_bytes = GYS_BM_WORDS * 4;
+	h.stride = L.p.stride;
+	h.epoch = c->epoch;
+	h.n = n;
+	h.lvl_t_last = c->lvl_t_last;
+	h.hl_t_last = c->hl_t_last;
+}
+
+// the slots of the ids: GYS_ERR_INVAL for an unknown (unless skip_unknown: GYS_NOSLOT) or repeated id
+int blob_slots(gys_ctx *c, const uint64_t *ids, uint32_t n, bool skip_unknown, std::vector<uint32_t> &slots, uint32_t *nknown)
+{
+	std::unordered_set<uint64_t> seen;
+	seen.reserve(n);
+	slots.resize(n);
+	uint32_t known = 0;
+	for (uint32_t i = 0; i < n; ++i) {
+		if (!seen.insert(ids[i]).second) {
+			set_err("glob_id %016llx occurs twice", (unsigned long long)ids[i]);
+			return GYS_ERR_INVAL;
+		}
+		auto it = c->gid_map_h.find(ids[i]);
+		if (it == c->gid_map_h.end()) {
+			if (!skip_unknown) {
+				set_err("unknown glob_id %016llx", (unsigned long long)ids[i]);
+				return GYS_ERR_INVAL;
+			}
+			slots[i] = GYS_NOSLOT;
+		} else {
+			slots[i] = it->second;
+			known++;
+		}
+	}
+	if (nknown) *nknown = known;
+	return GYS_OK;
+}
+
+// records [first, first + cnt) of a call to / from d_recs (16-byte aligned): the slot (and host) words go through the head of the staging
+// buffer, which the caller has sized (svc_rec_staging) -- d_recs may lie behind them in the same buffer.  Synchronises the stream.
+inline uint64_t svc_rec_words_bytes(uint32_t cnt) { return align_up(2ull * cnt * 4, 256); }
+
+int svc_rec_run(gys_ctx *c, SvcRecLayout &L, bool unpack, const uint32_t *slots, const uint32_t *hosts, uint32_t cnt, uint8_t *d_recs)
+{
+	if (!cnt) return GYS_OK;
+	uint32_t *d_words = (uint32_t *)c->dev_staging.p;
+	HIPCHK(hipMemcpyAsync(d_words, slots, (size_t)cnt * 4, hipMemcpyHostToDevice, c->stream));
+	if (unpack) HIPCHK(hipMemcpyAsync(d_words + cnt, hosts, (size_t)cnt * 4, hipMemcpyHostToDevice, c->stream));
+	HIPCHK(hipMemcpyAsync(c->clr_segs, L.segs.data(), L.segs.size() * sizeof(SvcClearSeg), hipMemcpyHostToDevice, c->stream));
+	SvcPackP p = L.p;
+	p.segs = c->clr_segs;
+	p.n = cnt;
+	p.slots = d_words;
+	p.hosts = d_words + cnt;
+	p.recs = d_recs;
+	{
+		ProfScope ps(c, unpack ? "svc_unpack" : "svc_pack");
+		const dim3 grid(std::min<uint32_t>(cnt, (uint32_t)c->ncu * 8u)), block(GYS_SVCPACK_NT);
+		if (unpack) hipLaunchKernelGGL(k_svc_unpack, grid, block, 0, c->stream, p);
+		else hipLaunchKernelGGL(k_svc_pack, grid, block, 0, c->stream, p);
+		HIPCHK(hipGetLastError());
+	}
+	HIPCHK(hipStreamSynchronize(c->stream)); // (slots / hosts / L.segs are the caller's locals)
+	return GYS_OK;
+}
+
+// the device memory a run needs: the segment list's buffer and the staging buffer
+int svc_rec_prepare(gys_ctx *c, uint64_t staging_bytes)
+{
+	const int rc = c->clr_segs.p ? GYS_OK : c->clr_segs.alloc(GYS_SVCCLEAR_MAXSEG, false);
+	return rc ? rc : ensure_staging(c, staging_bytes, 0);
+}
+
+inline int svc_rec_not_prepared(gys_ctx *c)
+{
+	if (!c->prepared) return GYS_OK;
+	set_err("window prepared: finish the close first");
+	return GYS_ERR_STATE;
+}
+
+// the two history bytes become engine state with the first decision or the first unpack (as in gys_decide_listener_state_dev): allocated
+// and zeroed, which is what a context without them stands for -- before the record layout is built, so that the layout is built once
+int svc_bithist_ensure(gys_ctx *c)
+{
+	if (c->svc_bithist.p) return GYS_OK;
+	const int rc = c->svc_bithist.alloc((size_t)c->cfg.max_services * 2, false);
+	if (rc) return rc;
+	const hipError_t e = hipMemsetAsync(c->svc_bithist, 0, (size_t)c->cfg.max_services * 2, c->stream);
+	if (e != hipSuccess) {
+		c->svc_bithist.release();
+		HIPCHK(e);
+	}
+	return GYS_OK;
+}
+
+// records per piece of the host-pointer forms
+inline uint32_t svc_rec_piece(const SvcRecLayout &L, uint32_t n) { return (uint32_t)std::min<uint64_t>(n, std::max<uint64_t>(1, GYS_BLOB_PIECE / L.p.stride)); }
+
+// everything of an unpack that comes before the first store: header, size, fingerprint, the clock rule, the ids.  adopt: the destination
+// takes the header's window number and close times.
+int blob_validate(gys_ctx *c, const SvcRecLayout &L, const SvcBlobHdr &h, uint64_t blob_bytes, bool *adopt)
+{
+	if (h.magic != GYS_BLOB_MAGIC) {
+		set_err("not a service blob (magic %08x)", h.magic);
+		return GYS_ERR_INVAL;
+	}
+	if (h.version != GYS_BLOB_VERSION) {
+		set_err("service blob of layout version %u, this library reads %u", h.version, GYS_BLOB_VERSION);
+		return GYS_ERR_INVAL;
+	}
+	SvcBlobHdr mine;
+	blob_header(c, L, h.n, mine);
+#define GYS_BLOB_FIELD(f)                                                                                               \
+	if (h.f != mine.f) {                                                                                            \
+		set_err("service blob: " #f " is %llu, this context has %llu", (unsigned long long)h.f, (unsigned long long)mine.f); \
+		return GYS_ERR_STATE;                                                                                   \
+	}
+	GYS_BLOB_FIELD(enable_tdigest)
+	GYS_BLOB_FIELD(td_pend_cap)
+	GYS_BLOB_FIELD(svc_hll_p)
+	GYS_BLOB_FIELD(svc_hll_levels)
+	GYS_BLOB_FIELD(enable_levels)
+	GYS_BLOB_FIELD(td_nb)
+	GYS_BLOB_FIELD(level_ring)
+	GYS_BLOB_FIELD(bm_line_bytes)
+	GYS_BLOB_FIELD(stride)
+#undef GYS_BLOB_FIELD
+	if (blob_bytes != 64ull + blob_ids_bytes(h.n) + (uint64_t)h.n * h.stride) {
+		set_err("service blob of %llu bytes, %u records of %u bytes need %llu", (unsigned long long)blob_bytes, h.n, h.stride,
+			(unsigned long long)(64ull + blob_ids_bytes(h.n) + (uint64_t)h.n * h.stride));
+		return GYS_ERR_INVAL;
+	}
+	*adopt = false;
+	if (h.epoch != c->epoch || h.lvl_t_last != c->lvl_t_last || h.hl_t_last != c->hl_t_last) {
+		if (c->have_last || c->clock_adopted) {
+			set_err("service blob of window %u (closes at %lld / %lld), this context is in window %u (%lld / %lld)", h.epoch, (long long)h.lvl_t_last,
+				(long long)h.hl_t_last, c->epoch, (long long)c->lvl_t_last, (long long)c->hl_t_last);
+			return GYS_ERR_STATE;
+		}
+		if (h.epoch == 0u) {
+			set_err("service blob of window 0");
+			return GYS_ERR_INVAL;
+		}
+		*adopt = true;
+	}
+	return GYS_OK;
+}
+
+// the restore case: a context that has not closed a window takes the source's clock
+int blob_adopt_clock(gys_ctx *c, const SvcBlobHdr &h)
+{
+	HIPCHK(hipMemcpyAsync(c->d_epoch, &h.epoch, 4, hipMemcpyHostToDevice, c->stream)); // the captured close graphs read the window number here
+	HIPCHK(hipStreamSynchronize(c->stream));
+	c->epoch = h.epoch;
+	c->lvl_t_last = h.lvl_t_last;
+	c->hl_t_last = h.hl_t_last;
+	c->hl_roll_epoch = h.epoch - 1u;                          // the window rolled last
+	if (h.lvl_t_last >= 0) c->lvl_last_epoch = h.epoch - 1u;  // the window whose records the level-0 array holds (behind their tags)
+	c->clock_adopted = true;
+	return GYS_OK;
+}
+
+int blob_unpack_begin(gys_ctx *c, const SvcBlobHdr &h, bool adopt)
+{
+	if (adopt) {
+		const int rc = blob_adopt_clock(c, h);
+		if (rc) return rc;
+	}
+	// the carried window accumulators (connection path, response event counts) are folded at the next close like ingested ones
+	c->conn_dirty = true;
+	c->resp_dirty = true;
+	return GYS_OK;
+}
+
+} // namespace
+
+uint64_t gys_service_blob_bytes(gys_ctx *c, uint32_t n)
+{
+	if (!c) return 0;
+	SvcRecLayout L;
+	if (svc_rec_layout(c, L)) return 0;
+	return 64ull + blob_ids_bytes(n) + (uint64_t)n * L.p.stride;
+}
+
+int gys_list_service_ids(gys_ctx *c, uint32_t first_slot, uint32_t nslots, uint64_t *glob_ids, uint32_t *nout)
+try {
+	GYS_ENTER_NOFLUSH(c);
+	if (!c || !nout || (!glob_ids && nslots)) return GYS_ERR_INVAL;
+	*nout = 0;
+	const uint32_t end = (uint32_t)std::min<uint64_t>((uint64_t)first_slot + nslots, c->nsvc);
+	for (uint32_t s = first_slot; s < end; ++s)
+		if (c->svc_host_h[s] != GYS_NOSLOT) glob_ids[(*nout)++] = c->svc_gid_h[s];
+	return GYS_OK;
+} GYS_CATCH_ALL
+
+int gys_list_host_service_ids(gys_ctx *c, const uint8_t machine_id[16], uint64_t *glob_ids, uint32_t cap, uint32_t *nfound)
+try {
+	GYS_ENTER_NOFLUSH(c);
+	if (!c || !machine_id || !nfound || (!glob_ids && cap)) return GYS_ERR_INVAL;
+	*nfound = 0;
+	uint32_t host;
+	const int rc = lookup_host(c, machine_id, &host);
+	if (rc) return rc;
+	std::vector<uint32_t> slots(c->host_lst[host].all_slots);
+	std::sort(slots.begin(), slots.end());
+	for (uint32_t s : slots) {
+		if (*nfound < cap) glob_ids[*nfound] = c->svc_gid_h[s];
+		++*nfound;
+	}
+	return GYS_OK;
+} GYS_CATCH_ALL
+
+static int pack_services(gys_ctx *c, const uint64_t *glob_ids, uint32_t n, uint8_t *blob, uint64_t blob_bytes, bool dev)
+{
+	if (!c || (!glob_ids && n) || !blob) return GYS_ERR_INVAL;
+	int rc = svc_rec_not_prepared(c);
+	if (rc) return rc;
+	SvcRecLayout L;
+	rc = svc_rec_layout(c, L);
+	if (rc) return rc;
+	const uint64_t need = 64ull + blob_ids_bytes(n) + (uint64_t)n * L.p.stride;
+	if (blob_bytes < need) {
+		set_err("blob buffer of %llu bytes, %u services need %llu", (unsigned long long)blob_bytes, n, (unsigned long long)need);
+		return GYS_ERR_INVAL;
+	}
+	if (dev && ((uintptr_t)blob & 15u)) {
+		set_err("the blob buffer must be 16-byte aligned");
+		return GYS_ERR_INVAL;
+	}
+	std::vector<uint32_t> slots;
+	rc = blob_slots(c, glob_ids, n, false, slots, nullptr);
+	if (rc) return rc;
+	const uint32_t piece = dev ? n : svc_rec_piece(L, n);
+	rc = svc_rec_prepare(c, svc_rec_words_bytes(piece) + (dev ? 0ull : (uint64_t)piece * L.p.stride));
+	if (rc) return rc;
+	std::vector<uint8_t> head(64 + blob_ids_bytes(n), 0);
+	SvcBlobHdr h;
+	blob_header(c, L, n, h);
+	memcpy(head.data(), &h, 64);
+	if (n) memcpy(head.data() + 64, glob_ids, (size_t)n * 8);
+	if (dev) {
+		HIPCHK(hipMemcpyAsync(blob, head.data(), head.size(), hipMemcpyHostToDevice, c->stream));
+		HIPCHK(hipStreamSynchronize(c->stream)); // (head is a local; svc_rec_run synchronises only when there are records)
+		return svc_rec_run(c, L, false, slots.data(), nullptr, n, blob + head.size());
+	}
+	memcpy(blob, head.data(), head.size());
+	uint8_t *d_recs = c->dev_staging + svc_rec_words_bytes(piece);
+	for (uint32_t first = 0; first < n; first += piece) {
+		const uint32_t cnt = std::min(piece, n - first);
+		rc = svc_rec_run(c, L, false, slots.data() + first, nullptr, cnt, d_recs);
+		if (rc) return rc;
+		HIPCHK(hipMemcpy(blob + head.size() + (uint64_t)first * L.p.stride, d_recs, (uint64_t)cnt * L.p.stride, hipMemcpyDeviceToHost));
+	}
+	return GYS_OK;
+}
+
+int gys_pack_services_dev(gys_ctx *c, const uint64_t *glob_ids, uint32_t n, void *d_blob, uint64_t blob_bytes)
+try {
+	GYS_ENTER(c);
+	return pack_services(c, glob_ids, n, (uint8_t *)d_blob, blob_bytes, true);
+} GYS_CATCH_ALL
+
+int gys_pack_services(gys_ctx *c, const uint64_t *glob_ids, uint32_t n, void *blob, uint64_t blob_bytes)
+try {
+	GYS_ENTER(c);
+	return pack_services(c, glob_ids, n, (uint8_t *)blob, blob_bytes, false);
+} GYS_CATCH_ALL
+
+static int unpack_services(gys_ctx *c, const uint8_t *blob, uint64_t blob_bytes, uint32_t *napplied, uint32_t *nskipped, bool dev)
+{
+	if (!c || !blob) return GYS_ERR_INVAL;
+	if (napplied) *napplied = 0;
+	if (nskipped) *nskipped = 0;
+	if (blob_bytes < 64) {
+		set_err("service blob of %llu bytes", (unsigned long long)blob_bytes);
+		return GYS_ERR_INVAL;
+	}
+	if (dev && ((uintptr_t)blob & 15u)) {
+		set_err("the blob buffer must be 16-byte aligned");
+		return GYS_ERR_INVAL;
+	}
+	int rc = svc_rec_not_prepared(c);
+	if (rc) return rc;
+	SvcBlobHdr h;
+	if (dev) HIPCHK(hipMemcpy(&h, blob, 64, hipMemcpyDeviceToHost));
+	else memcpy(&h, blob, 64);
+	rc = svc_bithist_ensure(c); // (no state: zeroes are what a context without the array stands for)
+	if (rc) return rc;
+	SvcRecLayout L;
+	rc = svc_rec_layout(c, L); // once: the list names the arrays as they are now and nothing below moves them
+	if (rc) return rc;
+	bool adopt = false;
+	rc = blob_validate(c, L, h, blob_bytes, &adopt);
+	if (rc) return rc;
+	const uint32_t n = h.n;
+	std::vector<uint64_t> ids(n);
+	if (n) {
+		if (dev) HIPCHK(hipMemcpy(ids.data(), blob + 64, (size_t)n * 8, hipMemcpyDeviceToHost));
+		else memcpy(ids.data(), blob + 64, (size_t)n * 8);
+	}
+	std::vector<uint32_t> slots, hosts(n, 0u);
+	uint32_t known = 0;
+	rc = blob_slots(c, ids.data(), n, true, slots, &known);
+	if (rc) return rc;
+	for (uint32_t i = 0; i < n; ++i)
+		if (slots[i] != GYS_NOSLOT) hosts[i] = c->svc_host_h[slots[i]];
+	const uint32_t piece = dev ? n : svc_rec_piece(L, n);
+	rc = svc_rec_prepare(c, svc_rec_words_bytes(piece) + (dev ? 0ull : (uint64_t)piece * L.p.stride));
+	if (rc) return rc;
+	// ---- nothing has been modified so far
+	rc = blob_unpack_begin(c, h, adopt);
+	if (rc) return rc;
+	const uint64_t recs_at = 64ull + blob_ids_bytes(n);
+	if (dev) {
+		rc = svc_rec_run(c, L, true, slots.data(), hosts.data(), n, const_cast<uint8_t *>(blob) + recs_at);
+		if (rc) return rc;
+	} else {
+		uint8_t *d_recs = c->dev_staging + svc_rec_words_bytes(piece);
+		for (uint32_t first = 0; first < n; first += piece) {
+			const uint32_t cnt = std::min(piece, n - first);
+			HIPCHK(hipMemcpyAsync(d_recs, blob + recs_at + (uint64_t)first * L.p.stride, (uint64_t)cnt * L.p.stride, hipMemcpyHostToDevice, c->stream));
+			rc = svc_rec_run(c, L, true, slots.data() + first, hosts.data() + first, cnt, d_recs);
+			if (rc) return rc;
+		}
+	}
+	if (napplied) *napplied = known;
+	if (nskipped) *nskipped = n - known;
+	return GYS_OK;
+}
+
+int gys_unpack_services_dev(gys_ctx *c, const void *d_blob, uint64_t blob_bytes, uint32_t *napplied, uint32_t *nskipped)
+try {
+	GYS_ENTER(c);
+	return unpack_services(c, (const uint8_t *)d_blob, blob_bytes, napplied, nskipped, true);
+} GYS_CATCH_ALL
+
+int gys_unpack_services(gys_ctx *c, const void *blob, uint64_t blob_bytes, uint32_t *napplied, uint32_t *nskipped)
+try {
+	GYS_ENTER(c);
+	return unpack_services(c, (const uint8_t *)blob, blob_bytes, napplied, nskipped, false);
+} GYS_CATCH_ALL
 
 int gys_list_stale_listeners(gys_ctx *c, uint32_t flags, uint32_t max_age_windows, uint64_t *glob_ids, uint32_t cap, uint32_t *nfound)
 try {

@@ -20,10 +20,13 @@
 //   bool web_curr_top_listeners(...) (server/gy_mnodehandle.cc:2706)                             web_curr_top_listeners(machine_id | nullptr, flags, madid, timestr, out)
 //   TCP_SOCK_HANDLER::listener_stats_update(servshr, cpu_issue, mem_issue) (common/gy_socket_stat.cc:3895) listener_stats_update(tnow, qps_multiple, diffsec, d_notify, d_scan)
 //
+//   the re-seeding of a listener's statistics after a restart (handle_listener_req, gy_mconnhdlr.cc:14257)   save_all(path) / load_all(path); a partha that changes ranks: save_partha_services(machine_id, blob) / restore_services(blob, n)
+//
 // PARTHA_INFO is identified by its GY_MACHINE_ID (PARTHA_INFO::machine_id_, the key of partha_tbl_).
 #pragma once
 
 #include <cstdint>
+#include <cstdio>
 #include <ctime>
 #include <functional>
 #include <mutex>
@@ -110,6 +113,98 @@ public:
 			return -1;
 		}
 		return total;
+	}
+
+	// ---- service records ("service records" in gysketch.h): what the reference keeps in Postgres and re-seeds after a restart
+	// (handle_listener_req, server/gy_mconnhdlr.cc:14257) lives in device memory here; these calls copy it out and back in.
+	// One partha's listeners as a blob: a partha that moves to another rank takes this with it (restore_services there, delete_listeners here).
+	bool save_partha_services(const uint8_t machine_id[16], std::vector<uint8_t> &blob) noexcept
+	{
+		std::unique_lock<std::shared_mutex> g(mu_);
+		try {
+			uint32_t n = 0;
+			if (gys_list_host_service_ids(ctx_, machine_id, nullptr, 0, &n) != GYS_OK) return false;
+			std::vector<uint64_t> ids(n ? n : 1);
+			if (gys_list_host_service_ids(ctx_, machine_id, ids.data(), n, &n) != GYS_OK) return false;
+			blob.resize(gys_service_blob_bytes(ctx_, n));
+			return gys_pack_services(ctx_, ids.data(), n, blob.data(), blob.size()) == GYS_OK;
+		} catch (...) {
+			return false;
+		}
+	}
+	// a blob into the listeners registered here (the others are counted in *nskipped); the state of the applied ones is overwritten
+	bool restore_services(const void *blob, size_t nbytes, uint32_t *napplied = nullptr, uint32_t *nskipped = nullptr) noexcept
+	{
+		std::unique_lock<std::shared_mutex> g(mu_);
+		return gys_unpack_services(ctx_, blob, nbytes, napplied, nskipped) == GYS_OK;
+	}
+	// every registered listener to a file: blobs of at most 64 MB over ranges of slots, each behind its length (u64, little-endian).  The
+	// file is written beside `path` (path + ".tmp") and renamed over it when it is complete and flushed: a crash or a failed pack in the
+	// middle of a periodic save leaves the previous checkpoint as it was.  The exclusive lock is held for the whole save -- every blob of a
+	// file has to carry the same window number and close times (a close between two ranges would make load_all refuse the later ones) -- so
+	// ingest calls wait for its duration: save right behind send_cluster_state, to a local disk.
+	bool save_all(const char *path, uint64_t *nservices = nullptr) noexcept
+	{
+		std::unique_lock<std::shared_mutex> g(mu_);
+		FILE *f = nullptr;
+		bool ok = false;
+		std::string tmp;
+		try {
+			tmp = std::string(path) + ".tmp";
+			const uint64_t one = gys_service_blob_bytes(ctx_, 1) - 64u, fit = ((64ull << 20) - 64u) / (one ? one : 1); // (header 64, id 8 + pad, record)
+			const uint32_t per = (uint32_t)(fit ? fit : 1);
+			std::vector<uint64_t> ids(per);
+			std::vector<uint8_t> blob;
+			uint64_t total = 0;
+			f = fopen(tmp.c_str(), "wb");
+			ok = f != nullptr;
+			for (uint32_t first = 0, nsvc = gys_num_services(ctx_); ok && first < nsvc; first += per) {
+				uint32_t n = 0;
+				ok = gys_list_service_ids(ctx_, first, per, ids.data(), &n) == GYS_OK;
+				if (!ok || !n) continue;
+				blob.resize(gys_service_blob_bytes(ctx_, n));
+				const uint64_t len = blob.size();
+				ok = gys_pack_services(ctx_, ids.data(), n, blob.data(), len) == GYS_OK && fwrite(&len, 8, 1, f) == 1 && fwrite(blob.data(), 1, len, f) == len;
+				total += n;
+			}
+			if (ok) ok = fflush(f) == 0;
+			if (nservices) *nservices = total;
+		} catch (...) {
+			ok = false;
+		}
+		if (f && fclose(f) != 0) ok = false;
+		if (ok) ok = rename(tmp.c_str(), path) == 0;
+		if (!ok && !tmp.empty()) (void)remove(tmp.c_str());
+		return ok;
+	}
+	// ... and back, after the hosts and listeners have been registered again; a fresh context continues the file's window count and ring times
+	bool load_all(const char *path, uint64_t *napplied = nullptr, uint64_t *nskipped = nullptr) noexcept
+	{
+		std::unique_lock<std::shared_mutex> g(mu_);
+		FILE *f = nullptr;
+		bool ok = false;
+		try {
+			std::vector<uint8_t> blob;
+			uint64_t na = 0, ns = 0, len = 0;
+			f = fopen(path, "rb");
+			ok = f != nullptr;
+			while (ok && fread(&len, 8, 1, f) == 1) {
+				ok = len >= 64u && len <= (64ull << 20) + 64u;
+				if (!ok) break;
+				blob.resize(len);
+				uint32_t a = 0, s = 0;
+				ok = fread(blob.data(), 1, len, f) == len && gys_unpack_services(ctx_, blob.data(), len, &a, &s) == GYS_OK;
+				na += a;
+				ns += s;
+			}
+			if (ok) ok = feof(f) != 0;
+			if (napplied) *napplied = na;
+			if (nskipped) *nskipped = ns;
+		} catch (...) {
+			ok = false;
+		}
+		if (f) fclose(f);
+		return ok;
 	}
 
 	// MCONN_HANDLER::partha_tcp_conn_info: pone points into the L1 receive buffer, valid only during the call

@@ -103,10 +103,12 @@ __global__ void k_scatter_const_u32(uint32_t *dst, const uint32_t *slots, uint32
 // One per-service array: service s owns [base + s * bytes, base + (s + 1) * bytes).  bytes is a multiple of 16 with a 16-byte aligned
 // base, or a smaller multiple of 4 (dword stores), or 2.  Every 16-byte piece is filled with `fill`, the LAST piece of the service's part with `last` (a
 // histogram record is zero up to max_val_seen, its last 8 bytes); a dword segment takes the words of `fill` in turn.
+// kind / rec_off: what a service record does with the array and where it holds it (gys_svcpack.hpp; k_svc_clear reads neither).
 struct SvcClearSeg {
 	uint8_t *base;
 	uint64_t bytes;
 	uint4 fill, last;
+	uint32_t kind = 0, rec_off = 0;
 };
 #define GYS_SVCCLEAR_NT 256u
 #define GYS_SVCCLEAR_MAXSEG 96u

@@ -3,6 +3,7 @@
 argument meaning; the multi-GPU step (one exchange per window) is an all-reduce of the fixed-size sketch registers
 through torch.distributed (backend "nccl" == RCCL over xGMI on ROCm; "gloo" in the CPU tests)."""
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -164,6 +165,86 @@ class SketchEngine:
         nf = C.c_uint32()
         capi.check(self.L.gys_list_stale_listeners(self.h, flags, max_age_windows, ids.ctypes.data_as(C.POINTER(C.c_uint64)), cap, C.byref(nf)))
         return ids[:min(cap, nf.value)].copy(), nf.value
+
+    # ---------------------------------------------------------------- service records ("service records" in gysketch.h)
+    def list_service_ids(self, first=0, n=None):
+        """gys_list_service_ids: glob ids of the registered (not free) slots of [first, first + n) in slot order (numpy u64)"""
+        n = self.num_services() - first if n is None else n
+        ids, nout = np.zeros(max(n, 1), dtype=np.uint64), C.c_uint32()
+        capi.check(self.L.gys_list_service_ids(self.h, first, max(n, 0), ids.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(nout)))
+        return ids[:nout.value].copy()
+
+    def service_blob_bytes(self, n):
+        return self.L.gys_service_blob_bytes(self.h, n)
+
+    def pack_services(self, glob_ids=None, dev=False):
+        """gys_pack_services / _dev: the blob of the listed services (None: every registered one) as numpy uint8 -- dev: as a torch uint8
+        tensor on the device.  Modifies nothing."""
+        ids = self.list_service_ids() if glob_ids is None else np.ascontiguousarray(glob_ids, dtype=np.uint64)
+        nb = self.service_blob_bytes(len(ids))
+        idp = ids.ctypes.data_as(C.POINTER(C.c_uint64))
+        if dev:
+            blob = self.torch.empty(nb, dtype=self.torch.uint8, device=self.device)
+            self.order()
+            capi.check(self.L.gys_pack_services_dev(self.h, idp, len(ids), C.c_void_p(blob.data_ptr()), nb))
+            return blob
+        blob = np.empty(nb, dtype=np.uint8)
+        capi.check(self.L.gys_pack_services(self.h, idp, len(ids), C.c_void_p(blob.ctypes.data), nb))
+        return blob
+
+    def unpack_services(self, blob):
+        """gys_unpack_services / _dev (a torch tensor on the device takes the device form; anything else is host bytes): overwrites the state
+        of the blob's services that are registered here; returns (applied, skipped)"""
+        na, ns = C.c_uint32(), C.c_uint32()
+        if hasattr(blob, "data_ptr"):
+            self.order()
+            capi.check(self.L.gys_unpack_services_dev(self.h, C.c_void_p(blob.data_ptr()), blob.numel() * blob.element_size(), C.byref(na), C.byref(ns)))
+        else:
+            b = np.ascontiguousarray(np.frombuffer(blob, dtype=np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else blob).view(np.uint8)
+            capi.check(self.L.gys_unpack_services(self.h, C.c_void_p(b.ctypes.data), b.nbytes, C.byref(na), C.byref(ns)))
+        return na.value, ns.value
+
+    STATE_FILE_PIECE = 64 << 20
+
+    def save_state(self, path):
+        """every registered service to a file: blobs of at most 64 MB over ranges of slots, each behind its length as a little-endian u64
+        (the format of the shim's save_all).  Returns the number of services written."""
+        per = max(1, (self.STATE_FILE_PIECE - 64) // (self.service_blob_bytes(1) - 64))
+        total = 0
+        tmp = path + ".tmp"  # written beside the target and renamed over it when complete: a failed save leaves the previous file as it was
+        try:
+            with open(tmp, "wb") as f:
+                for first in range(0, self.num_services(), per):
+                    ids = self.list_service_ids(first, per)
+                    if len(ids):
+                        blob = self.pack_services(ids)
+                        f.write(np.uint64(blob.nbytes).tobytes())
+                        f.write(blob.tobytes())
+                        total += len(ids)
+                f.flush()
+                os.fsync(f.fileno())
+            os.replace(tmp, path)
+        except BaseException:
+            if os.path.exists(tmp):
+                os.remove(tmp)
+            raise
+        return total
+
+    def load_state(self, path):
+        """the blobs of save_state / save_all into the services registered here: (applied, skipped)"""
+        applied = skipped = 0
+        with open(path, "rb") as f:
+            while True:
+                head = f.read(8)
+                if not head:
+                    break
+                nb = int(np.frombuffer(head, dtype="<u8")[0]) if len(head) == 8 else -1
+                blob = f.read(nb) if nb >= 0 else b""
+                if nb < 64 or len(blob) != nb:
+                    raise capi.GysError(capi.ERR_INVAL, "truncated state file %s" % path)
+                a, s = self.unpack_services(blob)
+                applied, skipped = applied + a, skipped + s
+        return applied, skipped
 
     LISTENER_INFO_DT = np.dtype([("glob_id", "<u8"), ("netns", "<u4"), ("port", "<u2"), ("is_any_ip", "u1"), ("addr_is_v6", "u1"), ("comm", "S16"),
                                  ("addr", "u1", (16,))])

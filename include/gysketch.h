@@ -1013,6 +1013,79 @@ int gys_export_svc_hll(gys_ctx *ctx, uint32_t first_slot, uint32_t nslots, uint8
 /* the same rows for a level of the closed windows at time tusec (gys_config.svc_hll_levels; "distinct-flow counts of the closed windows") */
 int gys_export_svc_hll_level(gys_ctx *ctx, int level, uint64_t tusec, uint32_t first_slot, uint32_t nslots, uint8_t *out /* [nslots << svc_hll_p] */);
 
+/* -------------------------------------------------------------------------------------------------------------------
+ * service records: saving, restoring and moving per-service state.  The reference's durable copy of a listener's statistics is Postgres;
+ * after a restart the 5-day statistics are re-seeded (handle_listener_req, server/gy_mconnhdlr.cc:14257) through
+ * GY_HISTOGRAM::get_serialized / update_from_serialized (common/gy_statistics.h:641-673).  Here the state lives in device memory: the
+ * calls below copy it out and back in.  Builder-defined.  The definition is FROZEN.
+ *
+ * A SERVICE RECORD is the service's part of every per-service array of the context, byte for byte (nothing is folded or normalised
+ * first), keyed by glob_id, not by slot.  Its arrays, in record order -- first those whose size is a multiple of 16 bytes:
+ *     open-window histogram record (256), all-time record (256), CONN_BITMAP rows (the bitmap line, 128), connection counters (32),
+ *     kept listener state (96), active-connection counters (32), per-service HLL file (1 << svc_hll_p; svc_hll_p != 0), the 22
+ *     closed-window HLL files (svc_hll_levels: last, 2 x 10 ring, all), with enable_levels: the 2 x 10 level snapshots (256 each), the
+ *     level-0 record (256; enable_levels == 1), the QPS and the active-connection histogram (256 each); with enable_tdigest: cluster
+ *     sums (200 x 8), cluster counts (200 x 4), the 16-byte buffer bookkeeping (npend, nh, nw, win_epoch, hw_epoch);
+ *   then the others, each rounded up to 4 bytes:
+ *     connection window accumulators (24), with enable_levels the level-0 tag (4; enable_levels == 1 with enable_tdigest) and the
+ *     first-close time (8); with enable_tdigest min / max (8), the buffer cursor (4), the value count of the last batch (4), the
+ *     window's response event count (4); the two history bytes of gys_decide_listener_state_dev (2, in a 4-byte word);
+ *   zeroes up to a multiple of 16; with enable_tdigest the service's buffered values: td_pend_cap 4-byte words, of which the first
+ *     `cursor` are the buffer's (the words behind the cursor are never read, are not carried and are zero in the record), padded to 16.
+ * hist_win and the level-0 array change places at every close: the record carries the logical arrays.  NOT in a record: the glob id, the
+ * host and the label of a slot (they belong to the destination's registration and to gys_set_service_groups) and what lives within one
+ * ingest call (run cursors, the claim word of the state records): the unpack leaves the former alone and sets the latter to their initial
+ * values.  The unpack REWRITES one word: the host slot behind the kept 88-byte state (word 23 of the 96-byte entry) becomes the
+ * destination's host slot of the service, in every entry that was ever kept (non-zero id words).  No other word of a record names a slot
+ * or a host slot.
+ *
+ * A BLOB is one pack call's output, little-endian, a persistent format:
+ *     offset  0  u32 magic 0x42535947 ("GYSB")      4  u32 layout version (1)
+ *             8  u32 enable_tdigest (0 / 1)         12  u32 td_pend_cap (the effective value; 0 without t-digest)
+ *            16  u32 svc_hll_p                      20  u32 svc_hll_levels (0 / 1)
+ *            24  u32 enable_levels                  28  u16 GYS_TD_NB, 30 u16 GYS_LEVEL_RING
+ *            32  u32 bitmap line bytes              36  u32 stride: bytes per record, a multiple of 16
+ *            40  u32 epoch: the source's open window number
+ *            44  u32 n: records
+ *            48  i64 lvl_t_last, 56 i64 hl_t_last: the source's last close time (s) of the level rings / of the HLL rings, -1: none
+ *            64  n x u64 glob_id, zero-padded to a multiple of 16 bytes
+ *            then n records of `stride` bytes in the order of the ids.
+ * Offsets 8 .. 39 are the configuration fingerprint that decides the record layout.  max_services, max_hosts, td_buf_values, slot
+ * numbers and host slots are not part of a blob: source and destination may differ in all of them.  A blob carries no checksum: its
+ * integrity between pack and unpack is the caller's.
+ *
+ * CLOCK RULE.  Window numbers inside a record (the buffer bookkeeping, word 22 of the kept state, the level-0 tag) and the ring
+ * arithmetic of the levels mean something only relative to the context's window number and close times.  Words are never translated:
+ *   - a destination that has neither prepared nor closed a window since gys_create (and has not adopted before) ADOPTS the header's epoch,
+ *     lvl_t_last and hl_t_last -- the restore case; its first close then clears exactly the ring buckets whose start was crossed since
+ *     the source's last close, as an uninterrupted engine would.  What it ingested before the unpack under its own window numbers is
+ *     stale afterwards: restore first;
+ *   - any other destination must already have the same three values, else GYS_ERR_STATE and nothing is written -- the migration case:
+ *     ranks of one job close in lockstep and count alike.
+ *
+ * gys_pack_services*: modifies no state.  GYS_ERR_INVAL for an unknown or repeated id, a buffer below gys_service_blob_bytes(ctx, n) or a
+ * device buffer that is not 16-byte aligned; n = 0 writes a valid empty blob.
+ * gys_unpack_services*: OVERWRITES (never merges) the state of every service of the blob whose glob_id is registered in the destination;
+ * the other ids are skipped and counted in *nskipped (*napplied, *nskipped may be NULL).  The whole blob is validated before the first
+ * store: bad magic, bad version, blob_bytes != what n and stride need, a glob_id that occurs twice: GYS_ERR_INVAL; a fingerprint mismatch
+ * (gys_last_error names the field) or the clock rule: GYS_ERR_STATE.  Nothing is modified in any of these cases.
+ * Both go through the submission queues' flush first, run on the context stream and return when the device work is done; between
+ * gys_window_prepare and gys_window_finish they give GYS_ERR_STATE.  The host-pointer forms move the records through the context's
+ * staging buffer in pieces of 8 MB.
+ * Only per-service state moves.  The rank-level registers of the open window stay with the source (global HLL, Count-Min tables, host
+ * summaries, top-N: all at most three windows old), so move a service RIGHT AFTER a close. */
+uint64_t gys_service_blob_bytes(gys_ctx *ctx, uint32_t n); /* header + ids + n records in this context's configuration */
+int gys_pack_services_dev(gys_ctx *ctx, const uint64_t *glob_ids /* HOST */, uint32_t n, void *d_blob, uint64_t blob_bytes);
+int gys_unpack_services_dev(gys_ctx *ctx, const void *d_blob, uint64_t blob_bytes, uint32_t *napplied, uint32_t *nskipped);
+int gys_pack_services(gys_ctx *ctx, const uint64_t *glob_ids, uint32_t n, void *blob /* HOST */, uint64_t blob_bytes);
+int gys_unpack_services(gys_ctx *ctx, const void *blob /* HOST */, uint64_t blob_bytes, uint32_t *napplied, uint32_t *nskipped);
+/* the glob ids of the registered (not free) slots of [first_slot, first_slot + nslots), in slot order: a checkpoint walks the context in
+ * ranges (glob_ids holds nslots entries; the range is cut at gys_num_services) */
+int gys_list_service_ids(gys_ctx *ctx, uint32_t first_slot, uint32_t nslots, uint64_t *glob_ids, uint32_t *nout);
+/* the glob ids of one host's listeners in slot order (what a partha's move to another rank packs): *nfound = all of them and may exceed
+ * cap, the first `cap` are written */
+int gys_list_host_service_ids(gys_ctx *ctx, const uint8_t machine_id[16], uint64_t *glob_ids, uint32_t cap, uint32_t *nfound);
+
 typedef struct {
 	uint64_t resp_events, resp_dropped_range, resp_dropped_nolistener;
 	uint64_t conn_events, conn_unknown_service;
