@@ -21,7 +21,8 @@ class Config(C.Structure):
                 ("enable_tdigest", C.c_uint32), ("svc_hll_p", C.c_uint32), ("resp_path", C.c_uint32),
                 ("max_batch_events", C.c_uint64), ("stream", C.c_void_p), ("reduce_arena", C.c_void_p),
                 ("reduce_arena_bytes", C.c_uint64), ("enable_levels", C.c_uint32), ("td_buf_values", C.c_uint32),
-                ("conn_pair_cms", C.c_uint32), ("td_pend_cap", C.c_uint32), ("svc_hll_levels", C.c_uint32)]
+                ("conn_pair_cms", C.c_uint32), ("td_pend_cap", C.c_uint32), ("svc_hll_levels", C.c_uint32),
+                ("actconn_pair_cap", C.c_uint32)]
 
 
 class ListenerInfo(C.Structure):
@@ -126,6 +127,28 @@ GROUP_NONE, GROUP_HOST, GROUP_CLUSTER, GROUP_LABEL = 0, 1, 2, 3
 RF_ANY_STATE = 1
 
 
+NOSLOT = 0xFFFFFFFF
+ACS_BY_LISTENER, ACS_BY_CLIENT, ACS_BY_HOST, ACS_KIND_LOCAL, ACS_KIND_REMOTE = 1, 2, 4, 8, 16  # GYS_ACS_*
+
+
+class ActconnRow(C.Structure):  # gys_actconn_row, 128 bytes
+    _fields_ = [("listener_glob_id", C.c_uint64), ("cli_aggr_task_id", C.c_uint64), ("ser_comm", C.c_char * 16), ("cli_comm", C.c_char * 16),
+                ("remote_machine_id", C.c_uint8 * 16), ("remote_madhava_id", C.c_uint64), ("bytes_sent", C.c_uint64), ("bytes_received", C.c_uint64),
+                ("cli_delay_msec", C.c_uint32), ("ser_delay_msec", C.c_uint32), ("max_rtt_msec", C.c_float), ("active_conns", C.c_uint32),
+                ("nrows", C.c_uint32), ("window", C.c_uint32), ("slot", C.c_uint32), ("flags", C.c_uint8), ("kind", C.c_uint8), ("pad", C.c_uint8 * 2),
+                ("reserved", C.c_uint64)]
+
+
+class ActconnSel(C.Structure):  # gys_actconn_sel
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("listener_glob_id", C.c_uint64), ("cli_aggr_task_id", C.c_uint64),
+                ("min_bytes", C.c_uint64), ("host_slot", C.c_uint32), ("min_active_conns", C.c_uint32)]
+
+
+class ActconnTblStats(C.Structure):  # gys_actconn_tblstats
+    _fields_ = [("entries", C.c_uint64), ("occupied", C.c_uint64), ("live_keys", C.c_uint64), ("rows_dropped", C.c_uint64),
+                ("rows_bad_key", C.c_uint64), ("rebuilds", C.c_uint64)]
+
+
 class TopkEntry(C.Structure):   # gys_topk_entry
     _fields_ = [("row", C.c_uint32), ("reserved", C.c_uint32), ("value", C.c_double), ("weight", C.c_uint64)]
 
@@ -225,6 +248,11 @@ SIGNATURES = {
     "gys_query_pair_cms": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_int, u64p]),
     "gys_export_pair_cms": (C.c_int, [vp, C.c_int, vp]),
     "gys_export_active_conn_counters": (C.c_int, [vp, C.c_uint32, C.c_uint32, u64p]),
+    "gys_actconn_list_dev": (C.c_int, [vp, C.POINTER(ActconnSel), vp, C.c_uint32, u32p]),
+    "gys_actconn_list": (C.c_int, [vp, C.POINTER(ActconnSel), C.POINTER(ActconnRow), C.c_uint32, u32p, u32p]),
+    "gys_actconn_svc_stats_dev": (C.c_int, [vp, vp]),
+    "gys_actconn_table_stats": (C.c_int, [vp, C.POINTER(ActconnTblStats)]),
+    "gys_json_activeconn": (C.c_int, [vp, C.POINTER(ActconnSel), C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "gys_rccl_unique_id": (C.c_int, [u8p]),
     "gys_rccl_comm_create": (C.c_int, [vp, u8p, C.c_int, C.c_int, C.POINTER(vp)]),
     "gys_rccl_comm_destroy": (C.c_int, [vp]),

@@ -45,6 +45,7 @@
 #include "gys_svcpack.hpp"
 #include "gys_tdrank.hpp"
 #include "gys_topk.hpp"
+#include "gys_actpairs.hpp"
 
 using namespace gys;
 
@@ -255,6 +256,18 @@ struct gys_ctx {
 	DevBuf<unsigned long long> last_act64; // last GYS_ACT_RING windows (a partha reports every 15 s, a window is 5 s; k_act_latch)
 	DevBuf<uint32_t> ring_act32, act_live;
 	DevBuf<unsigned long long> ring_act64;
+	// live (listener, client task group) rows of ACTIVE_CONN_STATS (gys_actpairs.hpp, gys_actpairs_host.hpp; cfg.actconn_pair_cap, 0 = nothing
+	// allocated): two buffers of keys and entries -- ap_cur is the one in use, the other takes the live entries at a rebuild
+	DevBuf<ActPairKey> ap_key[2];
+	DevBuf<ActPairEnt> ap_ent[2];
+	DevBuf<unsigned long long> ap_ctr; // [APC_NUM]
+	DevBuf<uint32_t> ap_row_ent;       // a call's row -> entry list between the passes (grows)
+	DevBuf<gys_actconn_row> ap_rows;   // gys_actconn_list: the rows on the device (grows)
+	DevBuf<unsigned long long> ap_acc; // gys_actconn_svc_stats_dev: the integer sums (grows)
+	uint32_t ap_entries = 0, ap_cur = 0;
+	uint64_t ap_occ_bound = 0; // upper bound of the occupied entries of the buffer in use (+ rows per call; exact after a read-back)
+	uint64_t ap_rebuilds = 0;
+	uint32_t ap_rebuild_epoch = 0; // the window of the last rebuild (entries only die at a window close: no second one before the next)
 	uint32_t epoch = 1;      // current window number (0 = never)
 	bool prepared = false;
 	DevBuf<uint32_t> d_epoch; // device copy of `epoch` for the captured window graph
@@ -1355,6 +1368,8 @@ int conn_fold(gys_ctx *c)
 	return GYS_OK;
 }
 
+int actp_ingest(gys_ctx *c, const uint8_t *d_batch, uint32_t n); // gys_actpairs_host.hpp
+
 int run_actconn(gys_ctx *c, const uint8_t *d_batch, uint32_t n)
 {
 	if (!n) return GYS_OK;
@@ -1370,7 +1385,7 @@ int run_actconn(gys_ctx *c, const uint8_t *d_batch, uint32_t n)
 	ProfScope ps(c, "actconn");
 	hipLaunchKernelGGL(k_actconn_ingest, dim3((n + 255) / 256), dim3(256), 0, c->stream, p);
 	HIPCHK(hipGetLastError());
-	return GYS_OK;
+	return c->ap_entries ? actp_ingest(c, d_batch, n) : GYS_OK;
 }
 
 // builds the window's Count-Min rows of the response path from the per-service event counts ("Count-Min rows of the window" in
@@ -1533,7 +1548,7 @@ try {
 	}
 	if (!cfg->max_hosts || !cfg->max_services || cfg->max_hosts > 65534 || !cfg->max_clusters || cfg->nranks == 0 || cfg->rank >= cfg->nranks ||
 	    (cfg->svc_hll_p && (cfg->svc_hll_p < 4 || cfg->svc_hll_p > 10)) || cfg->svc_hll_levels > 1 || (cfg->svc_hll_levels && !cfg->svc_hll_p) ||
-	    (cfg->td_pend_cap && (cfg->td_pend_cap < 64u || cfg->td_pend_cap > GYS_TD_PEND_CAP_MAX)) ||
+	    (cfg->td_pend_cap && (cfg->td_pend_cap < 64u || cfg->td_pend_cap > GYS_TD_PEND_CAP_MAX)) || cfg->actconn_pair_cap > (1u << 30) ||
 	    (cfg->td_buf_values && (cfg->td_buf_values < (cfg->td_pend_cap ? cfg->td_pend_cap : GYS_TD_PEND_CAP) + 64u || cfg->td_buf_values > GYS_PCAP_MAX))) {
 		set_err("bad config values");
 		return GYS_ERR_INVAL;
@@ -1646,6 +1661,15 @@ try {
 	c->host_seen.reserve(H);
 	if (cfg->svc_hll_p) ALLOC(c->svc_hll, S << cfg->svc_hll_p);
 	if (cfg->svc_hll_levels) ALLOC(c->hl_lvl, ((uint64_t)GYS_HLL_LVL_FILES * S) << cfg->svc_hll_p);
+	if (cfg->actconn_pair_cap) {
+		c->ap_entries = next_pow2(std::max<uint64_t>((uint64_t)cfg->actconn_pair_cap * 2, 16));
+		for (int b = 0; b < 2; ++b) {
+			ALLOC(c->ap_key[b], c->ap_entries);
+			ALLOC(c->ap_ent[b], c->ap_entries);
+			HIPCHK(hipMemset(c->ap_key[b].p, 0xFF, (uint64_t)c->ap_entries * sizeof(ActPairKey)));
+		}
+		ALLOC(c->ap_ctr, APC_NUM);
+	}
 	if (cfg->enable_levels) {
 		ALLOC(c->lvl_snap, 2 * GYS_LEVEL_RING * S);
 		ALLOC(c->lvl_last, cfg->enable_levels == 1 ? S : 1);
@@ -4796,6 +4820,7 @@ try {
 
 } // extern "C"
 
+#include "gys_actpairs_host.hpp"
 #include "gys_json.hpp"
 #include "gys_regex.hpp"
 #include "gys_svcquery_host.hpp"

@@ -438,4 +438,57 @@ try {
 	return json_out(j, buf, buflen, needed);
 } GYS_CATCH_ALL
 
+// the Active Conn query (server/gy_mnodehandle.cc:3699-3735) on the live rows of gys_actpairs.hpp: the kind-0 rows the selection matches in
+// the order of gys_actconn_list, columns of json_db_activeconn_arr (common/gy_json_field_maps.h:1479-1495), values as insert_active_conns
+// prints them (server/gy_mconnhdlr.cc:7869-7873)
+int gys_json_activeconn(gys_ctx *c, const gys_actconn_sel *sel, const char *madhava_id16, const char *timestr, char *buf, size_t buflen, size_t *needed)
+try {
+	GYS_ENTER(c);
+	if (needed) *needed = 0;
+	if (!c) return GYS_ERR_INVAL;
+	ACTP_CHECK();
+	gys_actconn_sel s;
+	int rc = actp_sel(sel, s);
+	if (rc) return rc;
+	std::vector<gys_actconn_row> rows;
+	const bool remote_only = (s.flags & GYS_ACS_KIND_REMOTE) && !(s.flags & GYS_ACS_KIND_LOCAL);
+	s.flags = (s.flags & ~(uint32_t)GYS_ACS_KIND_REMOTE) | GYS_ACS_KIND_LOCAL;
+	uint32_t nmatch = 0;
+	if (!remote_only && (rc = actp_list_host(c, s, c->ap_entries, rows, &nmatch)) != GYS_OK) return rc;
+	JsonBuf j;
+	j.s += '{';
+	j.kstr("madid", madhava_id16 ? madhava_id16 : "", 16);
+	j.arr_open("activeconn");
+	char t[40];
+	for (const gys_actconn_row &r : rows) {
+		uint64_t mid[2];
+		memcpy(mid, r.remote_machine_id, 16);
+		j.obj_open();
+		j.kstr("time", timestr ? timestr : "", 64);
+		snprintf(t, sizeof(t), "%016llx", (unsigned long long)r.listener_glob_id);
+		j.kstr("svcid", t, 16);
+		j.kstr("svcname", r.ser_comm, 16);
+		snprintf(t, sizeof(t), "%016llx", (unsigned long long)r.cli_aggr_task_id);
+		j.kstr("cprocid", t, 16);
+		j.kstr("cname", r.cli_comm, 16);
+		snprintf(t, sizeof(t), "%016llx%016llx", (unsigned long long)mid[0], (unsigned long long)mid[1]);
+		j.kstr("cparid", t, 32);
+		snprintf(t, sizeof(t), "%016llx", (unsigned long long)r.remote_madhava_id);
+		j.kstr("cmadid", t, 16);
+		j.ki("cnetout", (long long)r.bytes_sent);
+		j.ki("cnetin", (long long)r.bytes_received);
+		j.ki("cdelms", (int32_t)r.cli_delay_msec);
+		j.ki("sdelms", (int32_t)r.ser_delay_msec);
+		j.key("rttms");
+		snprintf(t, sizeof(t), "%.3f", (double)r.max_rtt_msec);
+		j.s += t;
+		j.ku("nconns", r.active_conns);
+		j.kb("csvc", (r.flags & 1u) != 0);
+		j.obj_close();
+	}
+	j.arr_close();
+	j.s += '}';
+	return json_out(j, buf, buflen, needed);
+} GYS_CATCH_ALL
+
 } // extern "C"

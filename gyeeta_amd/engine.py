@@ -38,7 +38,7 @@ def mid_buf(machine_id):
 class SketchEngine:
     def __init__(self, max_hosts, max_services, max_clusters=16, enable_tdigest=True, svc_hll_p=0, max_batch_events=1 << 20,
                  rank=0, nranks=1, device=None, torch_arena=True, resp_path=0, enable_levels=False, td_buf_values=0, conn_pair_cms=False, td_pend_cap=0,
-                 svc_hll_levels=0):
+                 svc_hll_levels=0, actconn_pair_cap=0):
         import torch
         self.L = capi.load()
         if not torch.cuda.is_available():
@@ -55,6 +55,7 @@ class SketchEngine:
         cfg.enable_tdigest = 1 if enable_tdigest else 0
         cfg.svc_hll_p = svc_hll_p
         cfg.svc_hll_levels = int(svc_hll_levels)  # the registers of the closed windows for the four levels (needs svc_hll_p)
+        cfg.actconn_pair_cap = int(actconn_pair_cap)  # live (listener, client task group) rows: room for that many keys (0 = off)
         cfg.resp_path = resp_path
         cfg.enable_levels = int(enable_levels)  # False / True / 2 (without the 5-s level)
         cfg.td_buf_values = td_buf_values
@@ -313,6 +314,68 @@ class SketchEngine:
         out = np.zeros((n, 4), dtype=np.uint64)
         capi.check(self.L.gys_export_active_conn_counters(self.h, first, n, out.ctypes.data_as(capi.u64p)))
         return out
+
+    # ---------------------------------------------------------------- live (listener, client task group) rows (actconn_pair_cap)
+    ACTCONN_ROW_DT = np.dtype([("listener_glob_id", "<u8"), ("cli_aggr_task_id", "<u8"), ("ser_comm", "S16"), ("cli_comm", "S16"),
+                               ("remote_machine_id", "<u8", 2), ("remote_madhava_id", "<u8"), ("bytes_sent", "<u8"), ("bytes_received", "<u8"),
+                               ("cli_delay_msec", "<u4"), ("ser_delay_msec", "<u4"), ("max_rtt_msec", "<f4"), ("active_conns", "<u4"), ("nrows", "<u4"),
+                               ("window", "<u4"), ("slot", "<u4"), ("flags", "u1"), ("kind", "u1"), ("pad", "u1", 2), ("reserved", "<u8")])
+
+    @staticmethod
+    def actconn_sel(listener=None, client=None, host_slot=None, kind=None, min_bytes=0, min_active_conns=0):
+        """a gys_actconn_sel: listener / client = the ids to match, host_slot = the local rows of that host's listeners, kind = 0 (local) /
+        1 (remote-listener rows) / None (both)"""
+        s = capi.ActconnSel()
+        s.struct_size = C.sizeof(capi.ActconnSel)
+        if listener is not None:
+            s.flags |= capi.ACS_BY_LISTENER
+            s.listener_glob_id = int(listener)
+        if client is not None:
+            s.flags |= capi.ACS_BY_CLIENT
+            s.cli_aggr_task_id = int(client)
+        if host_slot is not None:
+            s.flags |= capi.ACS_BY_HOST
+            s.host_slot = int(host_slot)
+        if kind is not None:
+            s.flags |= capi.ACS_KIND_REMOTE if kind else capi.ACS_KIND_LOCAL
+        s.min_bytes, s.min_active_conns = int(min_bytes), int(min_active_conns)
+        return s
+
+    def actconn_list(self, sel=None, cap=None):
+        """gys_actconn_list -> (rc, rows as a numpy ACTCONN_ROW_DT array in (listener, client, kind) order, number of matches); rc is
+        capi.ERR_NOMEM (and the array empty) when more rows match than cap.  cap None = the table's entries"""
+        if cap is None:
+            cap = self.actconn_table_stats()["entries"]
+        out = (capi.ActconnRow * max(cap, 1))()
+        nout, nmatch = C.c_uint32(), C.c_uint32()
+        rc = self.L.gys_actconn_list(self.h, C.byref(sel) if sel is not None else None, out, cap, C.byref(nout), C.byref(nmatch))
+        if rc not in (capi.OK, capi.ERR_NOMEM):
+            capi.check(rc)
+        return rc, np.frombuffer(out, dtype=self.ACTCONN_ROW_DT, count=nout.value).copy(), nmatch.value
+
+    def actconn_list_dev(self, sel=None, cap=0):
+        """gys_actconn_list_dev -> (torch uint8 device tensor of cap rows of 128 bytes, the first min(matches, cap) written; number of matches)"""
+        out = self.torch.zeros((max(cap, 1), 128), dtype=self.torch.uint8, device=self.device)
+        nmatch = C.c_uint32()
+        self.order()
+        capi.check(self.L.gys_actconn_list_dev(self.h, C.byref(sel) if sel is not None else None, C.c_void_p(out.data_ptr()), cap, C.byref(nmatch)))
+        return out, nmatch.value
+
+    def actconn_svc_stats_dev(self):
+        """gys_actconn_svc_stats_dev -> torch float64 device tensor [num_services, 4]: live client groups, active connections, bytes, rows"""
+        out = self.torch.zeros((max(self.num_services(), 1), 4), dtype=self.torch.float64, device=self.device)
+        self.order()
+        capi.check(self.L.gys_actconn_svc_stats_dev(self.h, C.c_void_p(out.data_ptr())))
+        self.sync()
+        return out
+
+    def actconn_table_stats(self):
+        st = capi.ActconnTblStats()
+        capi.check(self.L.gys_actconn_table_stats(self.h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in capi.ActconnTblStats._fields_}
+
+    def json_activeconn(self, sel=None, madid="0" * 16, timestr=""):
+        return self._json(self.L.gys_json_activeconn, C.byref(sel) if sel is not None else None, madid.encode(), timestr.encode())
 
     def handle_comm_stream(self, machine_id, stream_bytes):
         """L1 + L2 of madhava for one partha connection: COMM_HEADER-framed messages -> partha_tcp_conn_info / partha_listener_state"""

@@ -105,6 +105,11 @@ typedef struct {
 	                              300 s / 5 days / all; "distinct-flow counts of the closed windows" below); needs svc_hll_p.  22 register files per
 	                              service: 352 B at svc_hll_p = 4 (3.5 GB at 10^7 services), 22.5 KB at 10.  0 = off: nothing is allocated and a
 	                              window close enqueues what it always did */
+	uint32_t actconn_pair_cap; /* N > 0: the ACTIVE_CONN_STATS rows are also kept in an exact table keyed by (listener, client task group, kind) with
+	                              room for N live keys ("live active-connection rows" below; 2 x N entries, rounded up to a power of two, of 128
+	                              bytes, in two buffers).  0 = off: nothing is allocated, gys_ingest_active_conns launches what it always did and
+	                              the calls of that section answer GYS_ERR_STATE.  Not part of the service-record fingerprint: the table is not
+	                              per-service state */
 } gys_config;
 
 /* -------------------------------------------------------------------------------------------------------------------
@@ -307,7 +312,9 @@ int gys_ingest_listener_state_dev(gys_ctx *ctx, const void *d_batch, const uint3
  * arena (all-reduced with the other registers, per window; queries read the per-cell maximum of the last three windows' tables, see
  * gys_query_pair_cms) -- and (ii) exact cumulative per-listener sums.  Remote-listener rows (is_remote_listen_: the listener lives on another
  * madhava, server/gy_mconnhdlr.cc:7888-7925 -> remoteconntbl) are rolled up the same way into a Count-Min pair of their own (gys_query_pair_cms
- * which 6 / 7) and counted (gys_counters.actconn_remote_listen); they name no service of this engine, so there are no per-listener sums for them. */
+ * which 6 / 7) and counted (gys_counters.actconn_remote_listen); they name no service of this engine, so there are no per-listener sums for them.
+ * A Count-Min can only be asked about a pair the caller already knows: with gys_config.actconn_pair_cap the rows of both kinds are also kept,
+ * exactly, in a keyed table that can be enumerated ("Live active-connection rows" below). */
 int gys_ingest_active_conns(gys_ctx *ctx, const uint8_t machine_id[16], const void *batch, uint32_t nitems, const void *pend);
 int gys_ingest_active_conns_dev(gys_ctx *ctx, const void *d_batch, uint32_t nitems);
 
@@ -1012,6 +1019,80 @@ int gys_export_global_hist(gys_ctx *ctx, gys_hist_rec *out); /* all-service resp
 int gys_export_svc_hll(gys_ctx *ctx, uint32_t first_slot, uint32_t nslots, uint8_t *out /* [nslots << svc_hll_p] */);
 /* the same rows for a level of the closed windows at time tusec (gys_config.svc_hll_levels; "distinct-flow counts of the closed windows") */
 int gys_export_svc_hll_level(gys_ctx *ctx, int level, uint64_t tusec, uint32_t first_slot, uint32_t nslots, uint8_t *out /* [nslots << svc_hll_p] */);
+
+/* -------------------------------------------------------------------------------------------------------------------
+ * Live active-connection rows: "who talks to this service?", "what does this client call?" by enumeration.  The reference answers from
+ * activeconntbl / remoteconntbl (rows written by insert_active_conns, server/gy_mconnhdlr.cc:7780-7928; the Active Conn query reads the
+ * rows of the last 25 s, server/gy_mnodehandle.cc:3699-3735; fields json_db_activeconn_arr, common/gy_json_field_maps.h:1479-1495).  With
+ * gys_config.actconn_pair_cap = N > 0 every row gys_ingest_active_conns[_dev] takes also goes into an exact table on the device
+ * (gyeeta_amd/csrc/gys_actpairs.hpp).  Builder-defined, like the Count-Min gauge of gys_query_pair_cms.  The definition is FROZEN.
+ *   KEY     (listener_glob_id_, cli_aggr_task_id_, kind): kind 0 = a local-listener row, 1 = an is_remote_listen_ row.  Local rows are stored
+ *           whether or not the listener is registered (the reference writes them without a lookup, server/gy_mconnhdlr.cc:7818-7821).  A row
+ *           with an id of 0xFFFFFFFFFFFFFFFF (the table's free marker) is not stored: it is counted as rows_bad_key.
+ *   ENTRY   the key's report of the LATEST window in which the key was named.  window = that window number; active_conns (u32), bytes_sent,
+ *           bytes_received (u64) and nrows are SUMS over all rows of the key in that window, across calls; cli_delay_msec, ser_delay_msec and
+ *           max_rtt_msec are MAXIMA (floats compared as non-negative values: a negative or NaN value counts as 0.0f); the flag bits are ORed;
+ *           ser_comm, cli_comm, remote_machine_id and remote_madhava_id come from ONE row, whole: the highest-index row of the last call of
+ *           that window that named the key.  A report in a newer window REPLACES the figures, it does not add to them.
+ *   LIVE    while (open window) - window <= 3: the open window and the three closed before it -- the "last report" rule of
+ *           gys_query_pair_cms which 0 / 1; a report is visible at once (in stream order).  Entries that are not live are never reported.
+ *   gys_delete_listeners does not touch the table: rows of a listener that is not registered read slot == GYS_NOSLOT and age out.
+ *   ROOM    no row is dropped while (live keys) + (the call's new keys) <= actconn_pair_cap: before a call that could fill more than half of
+ *           the entries the live entries are re-inserted into the table's second buffer (a small read-back; gys_actconn_tblstats.rebuilds).
+ *           Beyond that a row that finds no entry is dropped and counted (rows_dropped), all rows of a key alike.
+ * Single rank: the table holds what this context ingested (it is not exchanged at the window boundary).
+ * Every call below answers GYS_ERR_STATE when actconn_pair_cap is 0. */
+#define GYS_NOSLOT 0xFFFFFFFFu
+typedef struct { /* 128 bytes */
+	uint64_t listener_glob_id, cli_aggr_task_id;
+	char ser_comm[16], cli_comm[16];
+	uint8_t remote_machine_id[16];
+	uint64_t remote_madhava_id, bytes_sent, bytes_received;
+	uint32_t cli_delay_msec, ser_delay_msec;
+	float max_rtt_msec;
+	uint32_t active_conns, nrows, window;
+	uint32_t slot; /* kind 0: the listener's service slot NOW, or GYS_NOSLOT (not registered, deleted); kind 1: GYS_NOSLOT */
+	uint8_t flags, kind, pad[2]; /* flags: the ORed flag byte of the rows (bit 0 cli_listener_proc_, bit 1 is_remote_listen_, bit 2 is_remote_cli_) */
+	uint64_t reserved;
+} gys_actconn_row;
+/* which fields of a selection apply; neither KIND flag = both kinds */
+enum { GYS_ACS_BY_LISTENER = 1, GYS_ACS_BY_CLIENT = 2, GYS_ACS_BY_HOST = 4, GYS_ACS_KIND_LOCAL = 8, GYS_ACS_KIND_REMOTE = 16 };
+typedef struct {
+	uint32_t struct_size; /* = sizeof(gys_actconn_sel) */
+	uint32_t flags;       /* GYS_ACS_* */
+	uint64_t listener_glob_id, cli_aggr_task_id;
+	uint64_t min_bytes;   /* bytes_sent + bytes_received >= min_bytes */
+	uint32_t host_slot;   /* GYS_ACS_BY_HOST: the LOCAL rows whose listener is registered on that host */
+	uint32_t min_active_conns;
+} gys_actconn_sel;
+/* the live entries the selection matches (sel NULL = all), compacted into the DEVICE array d_out in any order: min(*nmatch, cap) rows are
+ * written (d_out may be NULL with cap 0: a count).  One small read of the count inside the call.  GYS_ERR_INVAL: NULL nmatch, a wrong
+ * struct_size, unknown flags, cap > 0 without d_out. */
+int gys_actconn_list_dev(gys_ctx *ctx, const gys_actconn_sel *sel, gys_actconn_row *d_out, uint32_t cap, uint32_t *nmatch);
+/* the same on the HOST, ordered by (listener id, client id, kind) ascending.  *nmatch > cap: GYS_ERR_NOMEM, *nmatch is set, *nout = 0 and
+ * nothing else is written. */
+int gys_actconn_list(gys_ctx *ctx, const gys_actconn_sel *sel, gys_actconn_row *out, uint32_t cap, uint32_t *nout, uint32_t *nmatch);
+/* one row per service slot, d_out[slot * 4 + 0 .. 3] (DEVICE) = {live client groups, active connections, bytes sent + received, rows} over the
+ * live LOCAL entries whose listener is registered now: exact integers stored as doubles (accumulated in integers, converted once); free
+ * slots and slots without live entries are 0.  Columns for gys_topk_dev ("the 20 services with the most client groups": d_col = d_out,
+ * stride 4).  Asynchronous on the context stream. */
+int gys_actconn_svc_stats_dev(gys_ctx *ctx, double *d_out /* [gys_num_services * 4] */);
+typedef struct {
+	uint64_t entries;      /* entries of one buffer: a power of two >= 2 x actconn_pair_cap */
+	uint64_t occupied;     /* entries that hold a key, live or not */
+	uint64_t live_keys;    /* live entries now */
+	uint64_t rows_dropped; /* rows that found no entry */
+	uint64_t rows_bad_key; /* rows with the free marker as an id */
+	uint64_t rebuilds;     /* times the live entries moved to the other buffer */
+} gys_actconn_tblstats;
+int gys_actconn_table_stats(gys_ctx *ctx, gys_actconn_tblstats *out);
+/* {"madid":..,"activeconn":[{time,svcid,svcname,cprocid,cname,cparid,cmadid,cnetout,cnetin,cdelms,sdelms,rttms,nconns,csvc}]}: the kind-0 rows
+ * the selection matches, in the order of gys_actconn_list; field names and order = json_db_activeconn_arr (common/gy_json_field_maps.h:
+ * 1479-1495), number formats = the row insert_active_conns prints (server/gy_mconnhdlr.cc:7869-7873: ids as %016lx, cparid = the two
+ * halves of remote_machine_id_, rttms with three decimals, csvc = cli_listener_proc_).  Buffer and *needed as for the other gys_json_*
+ * calls.  The client side's shape (json_db_clientconn_arr) is not produced: kind-1 rows are reachable through the list calls. */
+int gys_json_activeconn(gys_ctx *ctx, const gys_actconn_sel *sel, const char *madhava_id16, const char *timestr, char *buf, size_t buflen,
+			size_t *needed);
 
 /* -------------------------------------------------------------------------------------------------------------------
  * service records: saving, restoring and moving per-service state.  The reference's durable copy of a listener's statistics is Postgres;
