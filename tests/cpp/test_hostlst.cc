@@ -13,6 +13,7 @@
 //     at least host_tbl_capacity(locals) that never shrinks, no key has two entries in a table, every candidate record names the local of
 //     its listener, and the descriptor counter advanced by exactly the parts of each cut.
 // Named cases (the smallest that reach each edge) + seeded random sequences on a small host, a host that gets cut and one that overflows.
+// A second mode (--tables FILE) prints the sub-tables the mirror builds for key lists from a file: the pin of tests/lstkeys.py.
 // Build (g++ -fsanitize=address,undefined) + run: tests/test_hostlst_cpu.py.
 #define GYS_OPAQUE_VGPR(x) asm volatile("" : "+r"(x))
 #define GYS_OPAQUE_LOADED4(a) asm volatile("" : "+r"(a[0]), "+r"(a[1]), "+r"(a[2]), "+r"(a[3]))
@@ -471,10 +472,81 @@ void test_random(uint64_t seed)
 		random_steps(w, rng, 150, 16, 4200);
 	}
 }
+
+// --tables FILE: the registry calls of tests/lstkeys.py's scenarios ("host" / "reg n" + n x "netns(hex) port slot address-kind" / "del n" + n slots / "dump"
+// / "end") through host_lst_insert and host_lst_remove + host_rebuild; every "dump" prints the host's sub-tables, local -> slot lists and candidate records
+// (tests/test_hostlst_cpu.py compares them entry for entry with the Python restatement's prediction)
+int tables_mode(const char *path)
+{
+	FILE *f = fopen(path, "r");
+	if (!f) {
+		printf("cannot read %s\n", path);
+		return 2;
+	}
+	HostListeners hl;
+	uint32_t desc_used = 0;
+	std::vector<uint64_t> key_of_slot;
+	char op[16];
+	unsigned n = 0;
+	while (fscanf(f, "%15s", op) == 1 && strcmp(op, "end") != 0) {
+		if (!strcmp(op, "host")) {
+			hl = HostListeners{};
+			hl.tbl.assign(16, GYS_HOST_TBL_EMPTY); // (as gys_register_host leaves a new host)
+			desc_used = 0;
+			key_of_slot.clear();
+			printf("host\n");
+		} else if (!strcmp(op, "reg") && fscanf(f, "%u", &n) == 1) {
+			std::vector<gys_listener_info> arr;
+			std::vector<uint32_t> sl;
+			for (unsigned i = 0; i < n; ++i) {
+				unsigned netns, port, slot, kind;
+				if (fscanf(f, "%x %u %u %u", &netns, &port, &slot, &kind) != 4 || kind >= A_KINDS) return 2;
+				arr.push_back(listener(netns, (uint16_t)port, (int)kind));
+				sl.push_back(slot);
+				if (key_of_slot.size() <= slot) key_of_slot.resize(slot + 1, 0);
+				key_of_slot[slot] = host_key48(netns, (uint16_t)port);
+			}
+			host_lst_insert(hl, arr.data(), n, sl.data(), desc_used, 1000);
+		} else if (!strcmp(op, "del") && fscanf(f, "%u", &n) == 1) {
+			std::unordered_set<uint32_t> dead;
+			for (unsigned i = 0; i < n; ++i) {
+				unsigned slot;
+				if (fscanf(f, "%u", &slot) != 1) return 2;
+				dead.insert(slot);
+			}
+			std::vector<uint64_t> gone;
+			host_lst_remove(hl, dead, key_of_slot.data(), gone);
+			CHECK(gone.size() == n, "%zu keys gone after %u plain listeners were deleted", gone.size(), n);
+		} else if (!strcmp(op, "dump")) {
+			if (hl.dirty) host_rebuild(hl); // (the engine's flush, before it uploads the tables)
+			CHECK(!hl.overflow, "the host overflowed");
+			const size_t np = hl.sub.empty() ? 1 : hl.sub.size();
+			printf("tables %zu\n", np);
+			for (size_t p = 0; p < np; ++p) {
+				const HostListeners &t = hl.sub.empty() ? hl : hl.sub[p];
+				printf("part %zu %zu %zu\n", p, t.tbl.size(), t.slots.size());
+				for (uint64_t e : t.tbl) printf("%llx ", (unsigned long long)e);
+				printf("\n");
+				for (uint32_t s : t.slots) printf("%u ", s);
+				printf("\n");
+			}
+			printf("cands %zu\n", hl.cands.size());
+			for (const ListenerCand &cd : hl.cands) printf("%u %u %u %u\n", cd.ip32, cd.flags, cd.local, cd.slot);
+		} else {
+			printf("bad line '%s'\n", op);
+			return 2;
+		}
+	}
+	fclose(f);
+	if (fails) return 1;
+	printf("host listener tables ok\n");
+	return 0;
+}
 } // namespace
 
 int main(int argc, char **argv)
 {
+	if (argc > 2 && !strcmp(argv[1], "--tables")) return tables_mode(argv[2]);
 	const uint64_t seed = argc > 1 ? strtoull(argv[1], nullptr, 10) : 1;
 	setvbuf(stdout, nullptr, _IOLBF, 0); // (a sanitizer abort must not take the lines of the failed checks with it)
 	test_sizes();
