@@ -2078,7 +2078,7 @@ __global__ __launch_bounds__(NT) void k_digest_merge(MergeP q)
 //   general kernel through slow_list.
 #ifndef GYS_MB_SKIP
 #define GYS_MB_SKIP 0 // TIMING EXPERIMENTS ONLY (results are wrong): 1 no per-bin pass, 2 no old-cluster / large-value placement, 4 no value pass 1,
-#endif                //   8 no bin scan, 16 no write-back, 32 nothing after the loads
+#endif                //   8 no bin scan, 16 no write-back, 32 nothing after the loads, 64 no old-cluster placement, 128 no large-value placement (2 = 64 + 128)
 #define GYS_MB_EXACT 1024u
 #define GYS_MB_BINS 2048u // 1024 one-value bins + 10 octaves x 64 cells (values < 2^20), padded to 8 bins per thread
 #define GYS_MB_BPT 8u
@@ -2183,13 +2183,23 @@ __global__ __launch_bounds__(256, (VPT == 16u ? GYS_MB_WAVES16 : 8)) void k_dige
 	// the bare value: ties among equal large values rank by list position (equal values are interchangeable).
 	constexpr bool STREAM = VPT > 16u;
 	constexpr uint32_t RV = STREAM ? 8u : VPT; // values a thread holds at a time
+	// The large-value list grouped by cell (every instance but the streamed one, whose entries are bare values).  A large value's entry is
+	// arrival << 20 | value, the arrival number inside its cell being the low half of the bin word before the value's own add (the clusters' adds
+	// touch the high half only).  Behind pass 1's barrier a thread takes its (at most BIG_CAP / 256) entries into registers, behind the bin scan's it
+	// stores each at (values below the cell) - (values below 1 024) + arrival: a cell's values then lie in consecutive entries, the cells in value
+	// order, and the two placement loops read the entries of ONE cell, [start, start + count) from the scanned bin words, instead of the whole list.
+	// One more barrier follows the stores; a merge without large values does not take it.  (Equal values are interchangeable, so ranking them by
+	// arrival in the cell instead of by position in the buffer gives the same clusters.  With the loops over the whole list kept for merges of
+	// fewer than 64 large values, and no barrier there, the kernel was no faster: profiles/r9a_merge_kernel_ab.txt.)
+	constexpr bool GROUP = !STREAM;
+	constexpr uint32_t GE = GYS_MB_BIG_CAP / 256u;
 	__shared__ __align__(16) uint32_t s_bin[GYS_MB_BINS];
 	// (Until round 6 the scan's list held any merge -- 256 VPT entries, 8 KB for buffers of 1 920 values -- which left 6 workgroups per CU where the
 	// merge has 8; with the merge's list and its hand-over -- gys_scan_quantiles_dev sends the listed services through the general path one by one, as it
 	// does for 64-bit weights -- the scan of 10^7 services takes 61 instead of 78 ms, r6aj.  A service is listed when more than 1 024 of its buffered
 	// values are a second or longer.)
 	constexpr uint32_t BIG_CAP = GYS_MB_BIG_CAP;
-	__shared__ __align__(16) uint32_t s_big[BIG_CAP]; // values >= GYS_MB_EXACT: index << 20 | value (read four at a time by the comparison loops)
+	__shared__ __align__(16) uint32_t s_big[BIG_CAP]; // values >= GYS_MB_EXACT: arrival in the cell << 20 | value (STREAM: the bare value)
 	__shared__ uint32_t s_thr[GYS_NBP];          // compacted non-empty old clusters: ceil(sum / count), padded with ~0
 	__shared__ uint32_t s_cpfx[GYS_NBP + 1];     // old weight before compacted cluster c
 	__shared__ uint32_t s_T[GYS_NBP];            // T_j, j = 1..NB-1; [0] = 0, [NB..] = ~0
@@ -2248,14 +2258,20 @@ __global__ __launch_bounds__(256, (VPT == 16u ? GYS_MB_WAVES16 : 8)) void k_dige
 		}
 		uint32_t wd[RV];
 		const uint32_t *const pend = p.td_pend + (size_t)slot * p.pcap;
-		{
+		// The bounds of the merge as scalars.  A thread's k-th value is element tid + 256 k, so a round of 256 elements lies wholly below a bound,
+		// wholly at or above it, or straddles it: that is decided once per round by a scalar compare, and only a straddling round keeps the
+		// per-lane tests (the loads here and pass 1 below).
+		const uint32_t m_s = (uint32_t)__builtin_amdgcn_readfirstlane((int)m), nbuf_s = (uint32_t)__builtin_amdgcn_readfirstlane((int)ent.nbuf);
+		// element base + tid; 0 past the end of the merge
+		const auto load_word = [&](uint32_t base) -> uint32_t {
+			const uint32_t i = base + tid;
+			if (base + 256u <= nbuf_s) return pend[i]; // the whole round lies in the key's buffer
+			uint32_t x = 0;
+			if (base < m_s && i < m) x = i < ent.nbuf ? pend[i] : p.staged[run0 + (i - ent.nbuf)];
+			return x;
+		};
 #pragma unroll
-			for (uint32_t k = 0; k < RV; ++k) {
-				const uint32_t i = tid + 256u * k;
-				wd[k] = 0;
-				if (i < m) wd[k] = i < ent.nbuf ? pend[i] : p.staged[run0 + (i - ent.nbuf)];
-			}
-		}
+		for (uint32_t k = 0; k < RV; ++k) wd[k] = load_word(256u * k);
 		if (GYS_MB_SKIP & 32) { // (the loads stay live: an impossible value writes them out)
 			uint32_t x = c0 ^ (uint32_t)sm0;
 #pragma unroll
@@ -2332,29 +2348,49 @@ __global__ __launch_bounds__(256, (VPT == 16u ? GYS_MB_WAVES16 : 8)) void k_dige
 		if (tid == 0) s_cpfx[nc] = nold;
 		s_T[tid] = (tid >= 1u && tid < GYS_TD_NB) ? (uint32_t)td_threshold(c_td_bnd[tid], (uint64_t)twoN) : (tid ? 0xFFFFFFFFu : 0u);
 		// ---- values, pass 1: bin count (-> arrival order inside the bin), list of large values, window part of the fold
-		const bool fold_scan = !query && nh == 0u; // the all-time deltas of the one-value bins come from the scan
+		const bool fold_scan = !query && __builtin_amdgcn_readfirstlane((int)nh) == 0; // (scalar) the all-time deltas of the one-value bins come from the scan
 		int32_t lmin = INT32_MAX, lmax = INT32_MIN, wmax = INT32_MIN;
+		const uint32_t lean_end = min(m_s, (uint32_t)__builtin_amdgcn_readfirstlane((int)nwin0)); // (scalar) the rounds that end at or below it are lean
 		for (uint32_t cb = 0; cb < (STREAM ? m : 1u); cb += 256u * RV) { // (one round unless STREAM)
 		if (STREAM && cb) { // the next eight values of the thread (the first eight were requested with the clusters)
 #pragma unroll
-			for (uint32_t k = 0; k < RV; ++k) {
-				const uint32_t i = cb + tid + 256u * k;
-				wd[k] = 0;
-				if (i < m) wd[k] = i < ent.nbuf ? pend[i] : p.staged[run0 + (i - ent.nbuf)];
-			}
+			for (uint32_t k = 0; k < RV; ++k) wd[k] = load_word(cb + 256u * k);
 		}
 #pragma unroll
 		for (uint32_t k = 0; k < RV; ++k) {
-			const uint32_t i = cb + tid + 256u * k;
+			const uint32_t base = cb + 256u * k, i = base + tid;
+			if (base >= m_s) break; // (uniform) this round and every later one lie past the merge's values
+			// The lean round: every lane holds a value (base + 256 <= m), nothing of the buffer is folded yet and the scan folds the one-value bins
+			// (fold_scan: nh == 0), none of the round's values belongs to the current window (base + 256 <= nwin0).  What is left per value is its bin
+			// add and the extremes; only a large value goes on to the list and to its all-time bucket.  On the default stream that is every round of
+			// a merge but the last.
+			if (!SCAN && fold_scan && base + 256u <= lean_end) {
+				if (!(GYS_MB_SKIP & 4)) {
+					const uint32_t uv = wd[k] >> GYS_ROW_BITS;
+					lmin = min(lmin, (int32_t)uv);
+					lmax = max(lmax, (int32_t)uv);
+					if (uv >= GYS_MB_EXACT) {
+						const uint32_t arr = atomicAdd(&s_bin[mb_bin(uv)], 1u) & 0xFFFFu;
+						const uint32_t at = atomicAdd(&s_nbig, 1u);
+						if (256u * VPT <= BIG_CAP || at < BIG_CAP) s_big[at] = STREAM ? uv : ((arr << 20) | uv);
+						atomicAdd(&s_fa[resp_bucket((int64_t)uv)], GYS_PACK_ONE | (unsigned long long)uv);
+					} else {
+						atomicAdd(&s_bin[uv], 1u);
+					}
+				}
+				continue;
+			}
 			// (r6ay: adding a wave's 64 values up per (bucket, record) key first -- ballot, count, DPP sum, one lane's add -- instead of one LDS add per
 			// value and record made the streamed instance SLOWER, 0.48 -> 0.92 ms on C5: the instance is bound by its instructions, not by same-address adds)
 			if (!(i >= m || (GYS_MB_SKIP & 4))) {
 			const uint32_t uv = wd[k] >> GYS_ROW_BITS;
-			atomicAdd(&s_bin[mb_bin(uv)], 1u); // (no rank inside the bin is needed: equal values are interchangeable, pass 2 works per bin)
 			const bool big = uv >= GYS_MB_EXACT;
 			if (big) {
+				const uint32_t arr = atomicAdd(&s_bin[mb_bin(uv)], 1u) & 0xFFFFu;
 				const uint32_t at = atomicAdd(&s_nbig, 1u);
-				if (256u * VPT <= BIG_CAP || at < BIG_CAP) s_big[at] = STREAM ? uv : ((i << 20) | uv);
+				if (256u * VPT <= BIG_CAP || at < BIG_CAP) s_big[at] = STREAM ? uv : ((arr << 20) | uv);
+			} else {
+				atomicAdd(&s_bin[uv], 1u); // (no rank inside the bin is needed: equal values are interchangeable, pass 2 works per bin)
 			}
 			if (SCAN && i >= nh_mm) {
 				lmin = min(lmin, (int32_t)uv);
@@ -2395,6 +2431,17 @@ __global__ __launch_bounds__(256, (VPT == 16u ? GYS_MB_WAVES16 : 8)) void k_dige
 			__syncthreads();
 			continue;
 		}
+		// the thread's entries of the large-value list, into registers (wd[] is dead); the list is rewritten in cell order behind the bin scan
+		const uint32_t nbig_s = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_nbig);
+		const bool grouped = GROUP && nbig_s != 0u && !(GYS_MB_SKIP & 8);
+		uint32_t ge[GE];
+#pragma unroll
+		for (uint32_t r = 0; r < GE; ++r) ge[r] = 0;
+		if (grouped) {
+#pragma unroll
+			for (uint32_t r = 0; r < GE; ++r)
+				if (256u * r < nbig_s && tid + 256u * r < nbig_s) ge[r] = s_big[tid + 256u * r];
+		}
 		// ---- one scan over the bins: thread t owns bins [8t, 8t + 8)
 		if (!(GYS_MB_SKIP & 8)) {
 			uint32_t bv[GYS_MB_BPT], own = 0;
@@ -2434,35 +2481,67 @@ __global__ __launch_bounds__(256, (VPT == 16u ? GYS_MB_WAVES16 : 8)) void k_dige
 				for (uint32_t k = 0; k < GYS_MB_BPT; ++k)
 					if (bv[k] & 0xFFFFu) s_ne[at++] = (uint16_t)(GYS_MB_BPT * tid + k);
 			}
-			unsigned long long acc0 = 0, acc1 = 0; // GY_HISTOGRAM::add_data for cnt values equal to `bin`, per bucket of the thread's bins
+			// GY_HISTOGRAM::add_data for the values of the thread's one-value bins, per bucket of its bins: cnt x {1 : 24 | bin : 40} summed over the bins
+			// below bk_chg (acc0) and from it on (acc1).  With bin = 8 tid + k the two halves are {sum of cnt : 24 | 8 tid x sum of cnt + sum of k cnt : 40}
+			// (at most 16 384 values below 1 024: the sum half stays below 2^24), the sum of all counts is the low half of `own`, and only a thread whose
+			// bins meet a bucket boundary (at most 15 of the 128) splits them: no 64-bit add, full-rate multiplies by constants, no mask per bin held
+			// across the merge loop.  (The compiler had already sunk the packed form under this condition, so the waves of the cells never ran it:
+			// profiles/r9a_isa_census_parent.txt.)
+			if (fold_scan && GYS_MB_BPT * tid < GYS_MB_EXACT) { // (a thread's 8 bins are all one-value bins or all cells: 1024 = 8 x 128)
+				uint32_t chg = bk_chg;
+				GYS_OPAQUE_VGPR(chg); // (otherwise the eight `k < bk_chg` lane masks are loop-invariant and live in SGPRs spilled to VGPR lanes)
+				const uint32_t s0 = own & 0xFFFFu;
+				uint32_t s1 = 0;
+#pragma unroll
+				for (uint32_t k = 1; k < GYS_MB_BPT; ++k) s1 += k * (bv[k] & 0xFFFFu);
+				uint32_t a0 = s0, a1 = s1;
+				if (chg < GYS_MB_BPT) {
+					a0 = 0;
+					a1 = 0;
+#pragma unroll
+					for (uint32_t k = 0; k < GYS_MB_BPT - 1u; ++k) {
+						const uint32_t c = k < chg ? (bv[k] & 0xFFFFu) : 0u;
+						a0 += c;
+						a1 += k * c;
+					}
+				}
+				const uint32_t bin0 = GYS_MB_BPT * tid, z0 = s0 - a0;
+				const unsigned long long acc0 = ((unsigned long long)(a0 << 8) << 32) | (unsigned long long)(bin0 * a0 + a1);
+				const unsigned long long acc1 = ((unsigned long long)(z0 << 8) << 32) | (unsigned long long)(bin0 * z0 + (s1 - a1));
+				if (acc0) atomicAdd(&s_fa[bk_first], acc0);
+				if (acc1) atomicAdd(&s_fa[bk_first + 1u], acc1);
+			}
 #pragma unroll
 			for (uint32_t k = 0; k < GYS_MB_BPT; ++k) {
-				const uint32_t bin = GYS_MB_BPT * tid + k;
 				// {values in lower bins : 16 | clusters with threshold in this or a lower bin : 16}
 				const uint32_t raw = bv[k];
 				bv[k] = (run & 0xFFFFu) | (((run >> 16) + (raw >> 16)) << 16);
 				run += raw;
-				const uint32_t cnt = raw & 0xFFFFu; // cnt x {1 : 24 | bin : 40}: cnt <= 1024 and bin < 1024, the halves cannot meet
-				const unsigned long long d = ((unsigned long long)(cnt << 8) << 32) | (unsigned long long)(cnt * bin);
-				if (k < bk_chg) acc0 += d; else acc1 += d;
 			}
 			((uint4 *)s_bin)[2u * tid] = make_uint4(bv[0], bv[1], bv[2], bv[3]);
 			((uint4 *)s_bin)[2u * tid + 1u] = make_uint4(bv[4], bv[5], bv[6], bv[7]);
-			if (fold_scan && GYS_MB_BPT * tid < GYS_MB_EXACT) { // (a thread's 8 bins are all one-value bins or all cells: 1024 = 8 x 128)
-				if (acc0) atomicAdd(&s_fa[bk_first], acc0);
-				if (acc1) atomicAdd(&s_fa[bk_first + 1u], acc1);
-			}
 		}
 		__syncthreads();
 		const uint32_t nbig = s_nbig;
+		const uint32_t nsmall = s_bin[GYS_MB_EXACT] & 0xFFFFu; // values below 1 024: the scanned word of the first cell
+		if (grouped) {
+#pragma unroll
+			for (uint32_t r = 0; r < GE; ++r)
+				if (256u * r < nbig_s && tid + 256u * r < nbig_s) s_big[(s_bin[mb_bin(ge[r] & 0xFFFFFu)] & 0xFFFFu) - nsmall + (ge[r] >> 20)] = ge[r];
+			__syncthreads();
+		}
 		// ---- old clusters: preceded by the old weight before them and by the values below their mean
-		const bool has_old = c0 && !(GYS_MB_SKIP & 2);
+		const bool has_old = c0 && !(GYS_MB_SKIP & (2 | 64));
 		if (has_old) {
 			uint32_t nb = s_bin[mb_bin(thr)] & 0xFFFFu;
 			if (thr >= GYS_MB_EXACT) {
 				// the large values of the threshold's cell below it: lo <= u < thr, as ONE unsigned comparison of u - lo; four list entries per LDS read
 				// (the loop is a chain of LDS round trips, one per entry before: this placement and the large values' below were 1.0 ms of the kernel's
 				// 2.9, profiles/r8a_phase_timing_by_skipping.txt; with both loops in this form 2.988 -> 2.610 ms, profiles/r8a_merge_kernel_ab.txt)
+				if (GROUP) { // the entries of the threshold's cell only (none without large values)
+					const uint32_t st = nb - nsmall, cn = (s_bin[mb_bin(thr) + 1u] & 0xFFFFu) - nb;
+					for (uint32_t j = 0; j < cn; ++j) nb += (s_big[st + j] & 0xFFFFFu) < thr ? 1u : 0u;
+				} else { // (STREAM)
 				const uint32_t sh = (31u - (uint32_t)__clz((int)thr)) - 6u;
 				const uint32_t lo = (thr >> sh) << sh, span = thr - lo;
 				const uint32_t n4 = nbig & ~3u;
@@ -2472,6 +2551,7 @@ __global__ __launch_bounds__(256, (VPT == 16u ? GYS_MB_WAVES16 : 8)) void k_dige
 					      ((e4.w & 0xFFFFFu) - lo < span ? 1u : 0u);
 				}
 				for (uint32_t j = n4; j < nbig; ++j) nb += (s_big[j] & 0xFFFFFu) - lo < span ? 1u : 0u;
+				}
 			}
 			const uint32_t mid2 = 2u * (e0 + nb) + c0;
 			uint32_t a = 0;
@@ -2562,28 +2642,29 @@ __global__ __launch_bounds__(256, (VPT == 16u ? GYS_MB_WAVES16 : 8)) void k_dige
 		}
 		// the (few) large values, one per thread from the list: rank inside the cell by comparison with the other large values, gap by
 		// search over the cluster thresholds
-		for (uint32_t j = tid; j < ((GYS_MB_SKIP & 2) ? 0u : nbig); j += 256u) {
-			const uint32_t me = s_big[j], uv = me & 0xFFFFFu;
+		for (uint32_t j = tid; j < ((GYS_MB_SKIP & (2 | 128)) ? 0u : nbig); j += 256u) {
+			uint32_t me;
+			if (GROUP) { // (its own entries, from the registers: the list is in cell order now)
+				me = ge[0];
+#pragma unroll
+				for (uint32_t r = 0; r + 1u < GE; ++r) ge[r] = ge[r + 1u];
+			} else {
+				me = s_big[j];
+			}
+			const uint32_t uv = me & 0xFFFFFu;
 			const uint32_t sh = (31u - (uint32_t)__clz((int)uv)) - 6u;
 			uint32_t r = s_bin[mb_bin(uv)] & 0xFFFFu;
-			if (STREAM) {
+			if (GROUP) {
+				// the entries of its cell that rank before it: (u, arrival) < (uv, its arrival); an entry rotated left by 12 bits is {u : 20 | arrival : 12}
+				const uint32_t st = r - nsmall, cn = (s_bin[mb_bin(uv) + 1u] & 0xFFFFu) - r, key = (me << 12) | (me >> 20);
+				for (uint32_t jj = 0; jj < cn; ++jj) {
+					const uint32_t e = s_big[st + jj];
+					r += (((e << 12) | (e >> 20)) < key) ? 1u : 0u;
+				}
+			} else { // (STREAM: bare values; ties among equal values rank by list position)
 				for (uint32_t jj = 0; jj < nbig; ++jj) {
 					const uint32_t e = s_big[jj], u = e & 0xFFFFFu;
 					r += ((u >> sh) == (uv >> sh) && (u < uv || (u == uv && jj < j))) ? 1u : 0u;
-				}
-			} else {
-				// the entries of the value's cell that rank before it: (u, index) < (uv, i) with u >= the cell's first value lo.  An entry rotated left
-				// by 12 bits is {u : 20 | index : 12}, so that is ONE unsigned comparison of key - (lo << 12); four list entries per LDS read
-				const uint32_t base = ((uv >> sh) << sh) << 12, span = ((me << 12) | (me >> 20)) - base;
-				const uint32_t n4 = nbig & ~3u;
-				for (uint32_t jj = 0; jj < n4; jj += 4u) {
-					const uint4 e4 = *(const uint4 *)&s_big[jj];
-					r += ((((e4.x << 12) | (e4.x >> 20)) - base < span) ? 1u : 0u) + ((((e4.y << 12) | (e4.y >> 20)) - base < span) ? 1u : 0u) +
-					     ((((e4.z << 12) | (e4.z >> 20)) - base < span) ? 1u : 0u) + ((((e4.w << 12) | (e4.w >> 20)) - base < span) ? 1u : 0u);
-				}
-				for (uint32_t jj = n4; jj < nbig; ++jj) {
-					const uint32_t e = s_big[jj];
-					r += (((e << 12) | (e >> 20)) - base < span) ? 1u : 0u;
 				}
 			}
 			uint32_t gap = 0;
