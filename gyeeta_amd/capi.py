@@ -149,6 +149,28 @@ class ActconnTblStats(C.Structure):  # gys_actconn_tblstats
                 ("rows_bad_key", C.c_uint64), ("rebuilds", C.c_uint64)]
 
 
+SES_BY_SRC, SES_BY_DST = 1, 2  # GYS_SES_*
+DEP_CALLEES, DEP_CALLERS, DEP_BOTH = 1, 2, 3  # GYS_DEP_*
+
+
+class SvcEdge(C.Structure):  # gys_svc_edge, 64 bytes
+    _fields_ = [("src_slot", C.c_uint32), ("dst_slot", C.c_uint32), ("src_glob_id", C.c_uint64), ("dst_glob_id", C.c_uint64),
+                ("cli_aggr_task_id", C.c_uint64), ("bytes_sent", C.c_uint64), ("bytes_received", C.c_uint64), ("active_conns", C.c_uint32),
+                ("nrows", C.c_uint32), ("window", C.c_uint32), ("kind", C.c_uint8), ("flags", C.c_uint8), ("pad", C.c_uint8 * 2)]
+
+
+class SvcEdgeSel(C.Structure):  # gys_svc_edge_sel
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("src_glob_id", C.c_uint64), ("dst_glob_id", C.c_uint64)]
+
+
+class SvcGraphStats(C.Structure):  # gys_svcgraph_stats_t
+    _fields_ = [("live_rows", C.c_uint64), ("rows_no_listener", C.c_uint64), ("rows_no_client", C.c_uint64), ("edges", C.c_uint64),
+                ("bound_services", C.c_uint64), ("bound_tasks", C.c_uint64)]
+
+
+assert C.sizeof(SvcEdge) == 64 and C.sizeof(SvcEdgeSel) == 24
+
+
 class TopkEntry(C.Structure):   # gys_topk_entry
     _fields_ = [("row", C.c_uint32), ("reserved", C.c_uint32), ("value", C.c_double), ("weight", C.c_uint64)]
 
@@ -253,6 +275,12 @@ SIGNATURES = {
     "gys_actconn_svc_stats_dev": (C.c_int, [vp, vp]),
     "gys_actconn_table_stats": (C.c_int, [vp, C.POINTER(ActconnTblStats)]),
     "gys_json_activeconn": (C.c_int, [vp, C.POINTER(ActconnSel), C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "gys_set_listener_tasks": (C.c_int, [vp, u64p, u64p, C.c_uint32]),
+    "gys_svc_edges_dev": (C.c_int, [vp, C.POINTER(SvcEdgeSel), vp, C.c_uint32, u32p]),
+    "gys_svc_edges": (C.c_int, [vp, C.POINTER(SvcEdgeSel), C.POINTER(SvcEdge), C.c_uint32, u32p, u32p]),
+    "gys_svcgraph_stats": (C.c_int, [vp, C.POINTER(SvcGraphStats)]),
+    "gys_svc_deps_dev": (C.c_int, [vp, u64p, C.c_uint32, C.c_uint32, C.c_uint32, vp, u32p]),
+    "gys_svc_deps": (C.c_int, [vp, u64p, C.c_uint32, C.c_uint32, C.c_uint32, u64p, u32p, C.c_uint32, u32p, u32p]),
     "gys_rccl_unique_id": (C.c_int, [u8p]),
     "gys_rccl_comm_create": (C.c_int, [vp, u8p, C.c_int, C.c_int, C.POINTER(vp)]),
     "gys_rccl_comm_destroy": (C.c_int, [vp]),

@@ -46,6 +46,8 @@
 #include "gys_tdrank.hpp"
 #include "gys_topk.hpp"
 #include "gys_actpairs.hpp"
+#include "gys_svcdeps.hpp"
+#include "gys_svcdeps_host.hpp"
 
 using namespace gys;
 
@@ -268,6 +270,17 @@ struct gys_ctx {
 	uint64_t ap_occ_bound = 0; // upper bound of the occupied entries of the buffer in use (+ rows per call; exact after a read-back)
 	uint64_t ap_rebuilds = 0;
 	uint32_t ap_rebuild_epoch = 0; // the window of the last rebuild (entries only die at a window close: no second one before the next)
+	// service dependency graph (gys_svcdeps.hpp, gys_svcdeps_engine.hpp): per slot the task group the listener is bound to (0 = none; identity,
+	// like svc_comm: not part of a service record); task_gen counts the calls that can change the task -> services list (a binding, a delete,
+	// a registration), dep_tasks / dep_task_* are the list built at dep_tasks_gen and its copy on the device; the rest is scratch (grows)
+	std::vector<uint64_t> svc_task_h;
+	uint64_t task_gen = 0, dep_tasks_gen = ~0ull;
+	TaskLists dep_tasks;
+	DevBuf<uint64_t> dep_task_id;
+	DevBuf<uint32_t> dep_task_off, dep_task_slot, dep_roots, dep_hops;
+	DevBuf<uint2> dep_pairs, dep_hits;
+	DevBuf<gys_svc_edge> dep_rows;
+	DevBuf<unsigned long long> dep_ctr; // [DPC_NUM] (allocated by the first graph call)
 	uint32_t epoch = 1;      // current window number (0 = never)
 	bool prepared = false;
 	DevBuf<uint32_t> d_epoch; // device copy of `epoch` for the captured window graph
@@ -2033,9 +2046,11 @@ try {
 		c->svc_port_h[s] = 0;
 		c->svc_host_h[s] = GYS_NOSLOT;
 		c->svc_key_h[s] = 0;
+		c->svc_task_h[s] = 0;
 		c->free_slots.insert(s);
 	}
 	c->registry_gen++;
+	c->task_gen++;
 	if (ndeleted) *ndeleted = nd;
 	{
 		// (a host whose upload fails here stays marked dirty: host_lst_add and the next delete rebuild its tables from the mirror first)
@@ -2093,6 +2108,7 @@ static int register_fresh(gys_ctx *c, uint32_t host, const gys_listener_info *ar
 	c->svc_port_h.resize(top);
 	c->svc_host_h.resize(top);
 	c->svc_key_h.resize(top);
+	c->svc_task_h.resize(top, 0ull);
 	for (uint32_t i = 0; i < n; ++i) {
 		const uint32_t s = sl[i];
 		c->gid_map_h[arr[i].glob_id] = s;
@@ -2102,10 +2118,12 @@ static int register_fresh(gys_ctx *c, uint32_t host, const gys_listener_info *ar
 		c->svc_port_h[s] = arr[i].port;
 		c->svc_host_h[s] = host;
 		c->svc_key_h[s] = host_key48(arr[i].netns, arr[i].port);
+		c->svc_task_h[s] = 0;
 		c->free_slots.erase(s);
 	}
 	c->nsvc = top;
 	c->registry_gen++;
+	c->task_gen++;
 	return GYS_OK;
 }
 
@@ -4821,6 +4839,7 @@ try {
 } // extern "C"
 
 #include "gys_actpairs_host.hpp"
+#include "gys_svcdeps_engine.hpp"
 #include "gys_json.hpp"
 #include "gys_regex.hpp"
 #include "gys_svcquery_host.hpp"

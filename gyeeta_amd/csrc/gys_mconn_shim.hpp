@@ -80,6 +80,51 @@ public:
 		std::unique_lock<std::shared_mutex> g(mu_);
 		return gys_register_listeners_slots(ctx_, machine_id, arr, n, slots) == GYS_OK;
 	}
+	// NEW_LISTENER::ser_aggr_task_id_ (common/gy_comm_proto.h:1538; kept per listener by handle_listener_req, gy_mconnhdlr.cc:13912-13966): the
+	// process group each listener runs in, 0 = none -- what the service dependency graph joins the active-connection rows' client ids to
+	bool set_listener_tasks(const uint64_t *glob_ids, const uint64_t *ser_aggr_task_ids, uint32_t n) noexcept
+	{
+		std::unique_lock<std::shared_mutex> g(mu_);
+		return gys_set_listener_tasks(ctx_, glob_ids, ser_aggr_task_ids, n) == GYS_OK;
+	}
+	// the service flow map's edges ("u calls v"; sel NULL = all), ordered by (src_slot, dst_slot, kind): a count, then the rows
+	bool svc_edges(const gys_svc_edge_sel *sel, std::vector<gys_svc_edge> &out) noexcept
+	{
+		std::unique_lock<std::shared_mutex> g(mu_);
+		try {
+			uint32_t nout = 0, nmatch = 0;
+			if (gys_svc_edges_dev(ctx_, sel, nullptr, 0, &nmatch) != GYS_OK) return false;
+			out.resize(nmatch);
+			if (gys_svc_edges(ctx_, sel, out.data(), nmatch, &nout, &nmatch) != GYS_OK) return false;
+			out.resize(nout);
+			return true;
+		} catch (...) {
+			return false;
+		}
+	}
+	// what lies within max_hops (0 = any number) calls of the services `roots` in direction dir (GYS_DEP_CALLEES / _CALLERS / _BOTH): ids and
+	// distances ordered by (hops, slot).  The ids go into gys_svc_filter.svcids for the roll-ups of "everything downstream of X".
+	bool svc_deps(const uint64_t *roots, uint32_t nroots, uint32_t dir, uint32_t max_hops, std::vector<uint64_t> &glob_ids, std::vector<uint32_t> &hops) noexcept
+	{
+		std::unique_lock<std::shared_mutex> g(mu_);
+		try {
+			const uint32_t cap = gys_num_services(ctx_);
+			uint32_t nout = 0, nreached = 0;
+			glob_ids.resize(cap);
+			hops.resize(cap);
+			if (gys_svc_deps(ctx_, roots, nroots, dir, max_hops, glob_ids.data(), hops.data(), cap, &nout, &nreached) != GYS_OK) return false;
+			glob_ids.resize(nout);
+			hops.resize(nout);
+			return true;
+		} catch (...) {
+			return false;
+		}
+	}
+	bool svcgraph_stats(gys_svcgraph_stats_t *out) noexcept
+	{
+		std::unique_lock<std::shared_mutex> g(mu_);
+		return gys_svcgraph_stats(ctx_, out) == GYS_OK;
+	}
 	// a LISTEN_FLAG_DELETE record's effect in the reference (gy_mconnhdlr.cc:11195-11248): the listeners leave the engine, their slots become free
 	bool delete_listeners(const uint64_t *glob_ids, uint32_t n, uint32_t *ndeleted = nullptr) noexcept
 	{

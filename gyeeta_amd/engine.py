@@ -377,6 +377,83 @@ class SketchEngine:
     def json_activeconn(self, sel=None, madid="0" * 16, timestr=""):
         return self._json(self.L.gys_json_activeconn, C.byref(sel) if sel is not None else None, madid.encode(), timestr.encode())
 
+    # ---------------------------------------------------------------- service dependency graph (actconn_pair_cap; "Service dependency graph")
+    SVC_EDGE_DT = np.dtype([("src_slot", "<u4"), ("dst_slot", "<u4"), ("src_glob_id", "<u8"), ("dst_glob_id", "<u8"), ("cli_aggr_task_id", "<u8"),
+                            ("bytes_sent", "<u8"), ("bytes_received", "<u8"), ("active_conns", "<u4"), ("nrows", "<u4"), ("window", "<u4"),
+                            ("kind", "u1"), ("flags", "u1"), ("pad", "u1", 2)])
+
+    def set_listener_tasks(self, glob_ids, aggr_task_ids):
+        """gys_set_listener_tasks -> rc (capi.OK, or capi.ERR_INVAL for an unknown id: nothing was changed); task id 0 clears a binding"""
+        g = np.ascontiguousarray(glob_ids, dtype=np.uint64)
+        t = np.ascontiguousarray(aggr_task_ids, dtype=np.uint64)
+        assert len(g) == len(t)
+        rc = self.L.gys_set_listener_tasks(self.h, g.ctypes.data_as(capi.u64p), t.ctypes.data_as(capi.u64p), len(g))
+        if rc not in (capi.OK, capi.ERR_INVAL):
+            capi.check(rc)
+        return rc
+
+    @staticmethod
+    def svc_edge_sel(src=None, dst=None):
+        """a gys_svc_edge_sel: src / dst = the glob_id of the calling / the called service"""
+        s = capi.SvcEdgeSel()
+        s.struct_size = C.sizeof(capi.SvcEdgeSel)
+        if src is not None:
+            s.flags |= capi.SES_BY_SRC
+            s.src_glob_id = int(src)
+        if dst is not None:
+            s.flags |= capi.SES_BY_DST
+            s.dst_glob_id = int(dst)
+        return s
+
+    def svc_edges(self, sel=None, cap=None):
+        """gys_svc_edges -> (rc, edges as a numpy SVC_EDGE_DT array in (src_slot, dst_slot, kind) order, number of matches); rc is
+        capi.ERR_NOMEM (and the array empty) when more edges match than cap.  cap None = as many as match"""
+        ref = C.byref(sel) if sel is not None else None
+        if cap is None:
+            cap = self.svc_edges_dev(sel, 0)[1]
+        out = (capi.SvcEdge * max(cap, 1))()
+        nout, nmatch = C.c_uint32(), C.c_uint32()
+        rc = self.L.gys_svc_edges(self.h, ref, out, cap, C.byref(nout), C.byref(nmatch))
+        if rc not in (capi.OK, capi.ERR_NOMEM):
+            capi.check(rc)
+        return rc, np.frombuffer(out, dtype=self.SVC_EDGE_DT, count=nout.value).copy(), nmatch.value
+
+    def svc_edges_dev(self, sel=None, cap=0):
+        """gys_svc_edges_dev -> (torch uint8 device tensor of cap rows of 64 bytes, the first min(matches, cap) written; number of matches)"""
+        out = self.torch.zeros((max(cap, 1), 64), dtype=self.torch.uint8, device=self.device)
+        nmatch = C.c_uint32()
+        self.order()
+        capi.check(self.L.gys_svc_edges_dev(self.h, C.byref(sel) if sel is not None else None, C.c_void_p(out.data_ptr()), cap, C.byref(nmatch)))
+        return out, nmatch.value
+
+    def svcgraph_stats(self):
+        st = capi.SvcGraphStats()
+        capi.check(self.L.gys_svcgraph_stats(self.h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in capi.SvcGraphStats._fields_}
+
+    def svc_deps_dev(self, roots, direction=capi.DEP_CALLEES, max_hops=0):
+        """gys_svc_deps_dev -> (torch int32 device tensor [num_services]: hops per slot, -1 (GYS_NOSLOT) where not reached; services reached)"""
+        r = np.ascontiguousarray(roots, dtype=np.uint64)
+        out = self.torch.zeros(max(self.num_services(), 1), dtype=self.torch.int32, device=self.device)
+        n = C.c_uint32()
+        self.order()
+        capi.check(self.L.gys_svc_deps_dev(self.h, r.ctypes.data_as(capi.u64p), len(r), direction, max_hops, C.c_void_p(out.data_ptr()), C.byref(n)))
+        return out, n.value
+
+    def svc_deps(self, roots, direction=capi.DEP_CALLEES, max_hops=0, cap=None):
+        """gys_svc_deps -> (rc, glob_ids, hops, services reached) ordered by (hops, slot); rc is capi.ERR_NOMEM (and the arrays empty) when
+        more services are reached than cap.  cap None = num_services"""
+        r = np.ascontiguousarray(roots, dtype=np.uint64)
+        if cap is None:
+            cap = self.num_services()
+        ids, hops = np.zeros(max(cap, 1), dtype=np.uint64), np.zeros(max(cap, 1), dtype=np.uint32)
+        nout, n = C.c_uint32(), C.c_uint32()
+        rc = self.L.gys_svc_deps(self.h, r.ctypes.data_as(capi.u64p), len(r), direction, max_hops, ids.ctypes.data_as(capi.u64p),
+                                 hops.ctypes.data_as(capi.u32p), cap, C.byref(nout), C.byref(n))
+        if rc not in (capi.OK, capi.ERR_NOMEM):
+            capi.check(rc)
+        return rc, ids[:nout.value].copy(), hops[:nout.value].copy(), n.value
+
     def handle_comm_stream(self, machine_id, stream_bytes):
         """L1 + L2 of madhava for one partha connection: COMM_HEADER-framed messages -> partha_tcp_conn_info / partha_listener_state"""
         buf = np.frombuffer(stream_bytes, dtype=np.uint8)

@@ -1095,6 +1095,68 @@ int gys_json_activeconn(gys_ctx *ctx, const gys_actconn_sel *sel, const char *ma
 			size_t *needed);
 
 /* -------------------------------------------------------------------------------------------------------------------
+ * Service dependency graph: "what is downstream / upstream of X, within N hops?"  The reference's service flow map joins
+ * activeconn.cprocid to svcprocmap (json_db_svcprocmap_arr, common/gy_json_field_maps.h:1626-1633); a listener's process group arrives
+ * as NEW_LISTENER::ser_aggr_task_id_ (common/gy_comm_proto.h:1538).  Here the join runs on the device over the live active-connection
+ * rows above (gyeeta_amd/csrc/gys_svcdeps.hpp).  Builder-defined.  The definition is FROZEN.
+ *   BINDING a registered listener may be bound to ONE task group (gys_set_listener_tasks; 0 = none).  The binding is identity, like the
+ *           label: host state, not part of a service record (gys_service_blob_bytes / gys_svc_state_bytes do not move), not carried by
+ *           gys_pack_services.  gys_delete_listeners clears it; a slot handed out again starts unbound.
+ *   EDGE    for every LIVE entry (listener id L, client id T, kind k) of the row table -- kind 0 and kind 1 alike: a kind-1 row carries
+ *           the local client's task group and the remote listener's id -- with L registered NOW as slot v and T != 0: one edge u -> v
+ *           ("u calls v") for EVERY registered slot u bound to T.  The edge is keyed (u, v, k) and carries the entry's figures unsplit
+ *           (bytes_sent, bytes_received, active_conns, nrows, window, the ORed flag byte: bit 0 cli_listener_proc_ is reported, it gates
+ *           nothing); a pair (u, v) with a row of each kind is two edges.  u == v is an edge like any other.
+ *   STATS   a live row whose listener is not registered counts as rows_no_listener; a live row whose client id is 0 or is bound to no
+ *           registered listener counts as rows_no_client; a row can count as both.  Neither gives an edge.
+ *   HOPS    hops[slot] = the least number of edges from any root to the slot along the chosen direction, 0 for a root, GYS_NOSLOT for a
+ *           slot that is not reached or free.  Parallel edges and kinds make no difference to a distance.
+ * The graph is derived per call from the table, the registry and the bindings as they are at the call: nothing is cached but the
+ * task -> services list (rebuilt after a binding, a delete or a registration).  Single rank, like the table.
+ * Every call below answers GYS_ERR_STATE when actconn_pair_cap is 0. */
+/* glob_ids[i] is bound to aggr_task_ids[i] (0 clears).  Everything is checked before anything changes: an unknown id gives GYS_ERR_INVAL
+ * and nothing is changed; an id named twice keeps its later value. */
+int gys_set_listener_tasks(gys_ctx *ctx, const uint64_t *glob_ids, const uint64_t *aggr_task_ids, uint32_t n);
+typedef struct { /* 64 bytes */
+	uint32_t src_slot, dst_slot;
+	uint64_t src_glob_id, dst_glob_id, cli_aggr_task_id, bytes_sent, bytes_received;
+	uint32_t active_conns, nrows, window;
+	uint8_t kind, flags, pad[2];
+} gys_svc_edge;
+enum { GYS_SES_BY_SRC = 1, GYS_SES_BY_DST = 2 };
+typedef struct {
+	uint32_t struct_size; /* = sizeof(gys_svc_edge_sel) */
+	uint32_t flags;       /* GYS_SES_*; an id that is not registered matches nothing */
+	uint64_t src_glob_id, dst_glob_id;
+} gys_svc_edge_sel;
+/* the edges the selection matches (sel NULL = all), into the DEVICE array d_out in any order: min(*nmatch, cap) rows are written (d_out may
+ * be NULL with cap 0: a count).  One small read of the count inside the call.  GYS_ERR_INVAL: NULL nmatch, a wrong struct_size, unknown
+ * flags, cap > 0 without d_out.  More than 2^32 - 1 edges: GYS_ERR_NOMEM. */
+int gys_svc_edges_dev(gys_ctx *ctx, const gys_svc_edge_sel *sel, gys_svc_edge *d_out, uint32_t cap, uint32_t *nmatch);
+/* the same on the HOST, ordered by (src_slot, dst_slot, kind) ascending.  *nmatch > cap: GYS_ERR_NOMEM, *nmatch is set, *nout = 0 and
+ * nothing else is written. */
+int gys_svc_edges(gys_ctx *ctx, const gys_svc_edge_sel *sel, gys_svc_edge *out, uint32_t cap, uint32_t *nout, uint32_t *nmatch);
+typedef struct {
+	uint64_t live_rows;        /* live entries of the row table */
+	uint64_t rows_no_listener; /* ... whose listener is not registered */
+	uint64_t rows_no_client;   /* ... whose client id is 0 or bound to no registered listener */
+	uint64_t edges;
+	uint64_t bound_services;   /* registered listeners with a binding */
+	uint64_t bound_tasks;      /* distinct task groups among them */
+} gys_svcgraph_stats_t;
+int gys_svcgraph_stats(gys_ctx *ctx, gys_svcgraph_stats_t *out);
+enum { GYS_DEP_CALLEES = 1, GYS_DEP_CALLERS = 2, GYS_DEP_BOTH = 3 }; /* follow u -> v / follow edges backwards / either way at every step */
+/* d_hops[slot] (DEVICE, gys_num_services words) = HOPS from the services root_ids (HOST array) names; max_hops 0 = no limit, otherwise
+ * slots further away stay GYS_NOSLOT.  Unknown root ids are skipped (with no known root nothing is reached); a root named twice counts
+ * once.  *nreached = the slots reached, roots included.  One small read per few levels inside the call.  GYS_ERR_INVAL: dir outside
+ * 1 .. 3, NULL d_hops, NULL nreached, NULL root_ids with nroots != 0. */
+int gys_svc_deps_dev(gys_ctx *ctx, const uint64_t *root_ids, uint32_t nroots, uint32_t dir, uint32_t max_hops, uint32_t *d_hops, uint32_t *nreached);
+/* the same on the HOST: the reached services' ids and distances ordered by (hops, slot) ascending.  *nreached > cap: GYS_ERR_NOMEM,
+ * *nreached is set, *nout = 0 and nothing else is written. */
+int gys_svc_deps(gys_ctx *ctx, const uint64_t *root_ids, uint32_t nroots, uint32_t dir, uint32_t max_hops, uint64_t *glob_ids, uint32_t *hops, uint32_t cap,
+		 uint32_t *nout, uint32_t *nreached);
+
+/* -------------------------------------------------------------------------------------------------------------------
  * service records: saving, restoring and moving per-service state.  The reference's durable copy of a listener's statistics is Postgres;
  * after a restart the 5-day statistics are re-seeded (handle_listener_req, server/gy_mconnhdlr.cc:14257) through
  * GY_HISTOGRAM::get_serialized / update_from_serialized (common/gy_statistics.h:641-673).  Here the state lives in device memory: the
