@@ -171,6 +171,14 @@ class SvcGraphStats(C.Structure):  # gys_svcgraph_stats_t
 assert C.sizeof(SvcEdge) == 64 and C.sizeof(SvcEdgeSel) == 24
 
 
+class SvcComponent(C.Structure):  # gys_svc_component, 64 bytes
+    _fields_ = [("root_slot", C.c_uint32), ("nservices", C.c_uint32), ("root_glob_id", C.c_uint64), ("nedges", C.c_uint64), ("nrows", C.c_uint64),
+                ("active_conns", C.c_uint64), ("bytes_sent", C.c_uint64), ("bytes_received", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+assert C.sizeof(SvcComponent) == 64
+
+
 class TopkEntry(C.Structure):   # gys_topk_entry
     _fields_ = [("row", C.c_uint32), ("reserved", C.c_uint32), ("value", C.c_double), ("weight", C.c_uint64)]
 
@@ -281,6 +289,9 @@ SIGNATURES = {
     "gys_svcgraph_stats": (C.c_int, [vp, C.POINTER(SvcGraphStats)]),
     "gys_svc_deps_dev": (C.c_int, [vp, u64p, C.c_uint32, C.c_uint32, C.c_uint32, vp, u32p]),
     "gys_svc_deps": (C.c_int, [vp, u64p, C.c_uint32, C.c_uint32, C.c_uint32, u64p, u32p, C.c_uint32, u32p, u32p]),
+    "gys_svc_components_dev": (C.c_int, [vp, vp, u32p, u32p]),
+    "gys_svc_components": (C.c_int, [vp, C.c_uint32, C.POINTER(SvcComponent), C.c_uint32, u32p, u32p, u32p]),
+    "gys_label_service_components": (C.c_int, [vp, C.c_uint32, u32p]),
     "gys_rccl_unique_id": (C.c_int, [u8p]),
     "gys_rccl_comm_create": (C.c_int, [vp, u8p, C.c_int, C.c_int, C.POINTER(vp)]),
     "gys_rccl_comm_destroy": (C.c_int, [vp]),

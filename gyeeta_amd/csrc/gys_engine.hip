@@ -48,6 +48,7 @@
 #include "gys_actpairs.hpp"
 #include "gys_svcdeps.hpp"
 #include "gys_svcdeps_host.hpp"
+#include "gys_svccomp.hpp"
 
 using namespace gys;
 
@@ -281,6 +282,11 @@ struct gys_ctx {
 	DevBuf<uint2> dep_pairs, dep_hits;
 	DevBuf<gys_svc_edge> dep_rows;
 	DevBuf<unsigned long long> dep_ctr; // [DPC_NUM] (allocated by the first graph call)
+	// service components (gys_svccomp.hpp, gys_svccomp_engine.hpp): scratch of one call (grows) -- the union-find's parents, the flattened
+	// partition, the components' sizes, a listed root's place in the list, the list itself, the listed components' sums, the counter words
+	DevBuf<uint32_t> cc_parent, cc_comp, cc_size, cc_index;
+	DevBuf<uint2> cc_list;
+	DevBuf<unsigned long long> cc_acc, cc_ctr; // [listed][GYS_CC_ACC], [CCC_NUM]
 	uint32_t epoch = 1;      // current window number (0 = never)
 	bool prepared = false;
 	DevBuf<uint32_t> d_epoch; // device copy of `epoch` for the captured window graph
@@ -4840,6 +4846,7 @@ try {
 
 #include "gys_actpairs_host.hpp"
 #include "gys_svcdeps_engine.hpp"
+#include "gys_svccomp_engine.hpp"
 #include "gys_json.hpp"
 #include "gys_regex.hpp"
 #include "gys_svcquery_host.hpp"

@@ -59,6 +59,24 @@ __host__ __device__ __forceinline__ uint32_t dep_task_find(const uint64_t *ids, 
 	return (lo < n && ids[lo] == id) ? lo : GYS_DEP_NOTASK;
 }
 
+// the join of one live entry: dst = the listener's slot now (GYS_NOSLOT: not registered), the client group's services are
+// task_slot[t0 .. t0 + m), m = the edges the entry gives (0 without a listener slot); returns "the client group owns no service"
+// (k_dep_edges and k_cc_rows of gys_svccomp.hpp share it)
+__device__ __forceinline__ bool dep_join(const DepEdgeP &p, const ActPairKey &k, uint32_t &dst, uint32_t &t0, uint32_t &m)
+{
+	dst = tbl_lookup(p.gid, k.lid);
+	if (dst >= p.nsvc) dst = GYS_NOSLOT;
+	t0 = m = 0u;
+	const uint32_t ti = k.cid ? dep_task_find(p.task_id, p.ntask, k.cid) : GYS_DEP_NOTASK;
+	if (ti != GYS_DEP_NOTASK) {
+		t0 = p.task_off[ti];
+		m = p.task_off[ti + 1u] - t0;
+	}
+	const bool nocli = m == 0u;
+	if (dst == GYS_NOSLOT) m = 0u;
+	return nocli;
+}
+
 template <bool FULL>
 __global__ __launch_bounds__(256) void k_dep_edges(DepEdgeP p)
 {
@@ -74,15 +92,7 @@ __global__ __launch_bounds__(256) void k_dep_edges(DepEdgeP p)
 		uint32_t dst = GYS_NOSLOT, t0 = 0, m = 0;
 		bool nocli = false, one = false;
 		if (live) {
-			dst = tbl_lookup(p.gid, k.lid);
-			if (dst >= p.nsvc) dst = GYS_NOSLOT;
-			const uint32_t ti = k.cid ? dep_task_find(p.task_id, p.ntask, k.cid) : GYS_DEP_NOTASK;
-			if (ti != GYS_DEP_NOTASK) {
-				t0 = p.task_off[ti];
-				m = p.task_off[ti + 1u] - t0;
-			}
-			nocli = m == 0u;
-			if (dst == GYS_NOSLOT) m = 0u;
+			nocli = dep_join(p, k, dst, t0, m);
 			if (m && (p.sel_flags & GYS_SES_BY_DST) && dst != p.dst_slot) m = 0u;
 			if (m && (p.sel_flags & GYS_SES_BY_SRC)) { // (src_slot is bound to src_task: it is one of the m callers exactly when the row's client is that task)
 				one = true;

@@ -454,6 +454,39 @@ class SketchEngine:
             capi.check(rc)
         return rc, ids[:nout.value].copy(), hops[:nout.value].copy(), n.value
 
+    # ---------------------------------------------------------------- service components (actconn_pair_cap; "Service components")
+    SVC_COMPONENT_DT = np.dtype([("root_slot", "<u4"), ("nservices", "<u4"), ("root_glob_id", "<u8"), ("nedges", "<u8"), ("nrows", "<u8"),
+                                 ("active_conns", "<u8"), ("bytes_sent", "<u8"), ("bytes_received", "<u8"), ("reserved", "<u8")])
+
+    def svc_components_dev(self, counts=True):
+        """gys_svc_components_dev -> (torch int32 device tensor [num_services]: the lowest slot of the slot's component, -1 (GYS_NOSLOT) for a
+        free slot; components; components with two members or more).  counts=False skips the two counting launches: (tensor, None, None)"""
+        out = self.torch.zeros(max(self.num_services(), 1), dtype=self.torch.int32, device=self.device)
+        nc, nl = C.c_uint32(), C.c_uint32()
+        self.order()
+        capi.check(self.L.gys_svc_components_dev(self.h, C.c_void_p(out.data_ptr()), C.byref(nc) if counts else None, C.byref(nl) if counts else None))
+        return (out, nc.value, nl.value) if counts else (out, None, None)
+
+    def svc_components(self, min_services=0, cap=None):
+        """gys_svc_components -> (rc, components as a numpy SVC_COMPONENT_DT array ordered by (nservices descending, root_slot), matching
+        components, all components); rc is capi.ERR_NOMEM (and the array empty) when more match than cap.  cap None = num_services"""
+        if cap is None:
+            cap = self.num_services()
+        out = (capi.SvcComponent * max(cap, 1))()
+        nout, nmatch, ncomp = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        rc = self.L.gys_svc_components(self.h, min_services, out, cap, C.byref(nout), C.byref(nmatch), C.byref(ncomp))
+        if rc not in (capi.OK, capi.ERR_NOMEM):
+            capi.check(rc)
+        return rc, np.frombuffer(out, dtype=self.SVC_COMPONENT_DT, count=nout.value).copy(), nmatch.value, ncomp.value
+
+    def label_service_components(self, min_services=2):
+        """gys_label_service_components -> the labels in use: every service's label (GYS_GROUP_LABEL) becomes the root slot of its component
+        where that has >= min_services members, GYS_NO_GROUP elsewhere.  A snapshot: the labels do not follow the graph"""
+        n = C.c_uint32()
+        capi.check(self.L.gys_label_service_components(self.h, min_services, C.byref(n)))
+        self._label_domain = max(getattr(self, "_label_domain", 0), self.num_services())  # (a root slot is a label: see set_service_groups)
+        return n.value
+
     def handle_comm_stream(self, machine_id, stream_bytes):
         """L1 + L2 of madhava for one partha connection: COMM_HEADER-framed messages -> partha_tcp_conn_info / partha_listener_state"""
         buf = np.frombuffer(stream_bytes, dtype=np.uint8)

@@ -1157,6 +1157,62 @@ int gys_svc_deps(gys_ctx *ctx, const uint64_t *root_ids, uint32_t nroots, uint32
 		 uint32_t *nout, uint32_t *nreached);
 
 /* -------------------------------------------------------------------------------------------------------------------
+ * Service components: "which services form one application?" -- the question in front of "what is within N hops of X".  The reference
+ * merges service groups that share a related listener into one effective cluster id on the CPU (SHCONN_HANDLER::coalesce_svc_mesh_locked,
+ * server/gy_shconnhdlr.cc:4827-4912: a serial two-pass hash walk) and serves it as "svcmeshclust".  Here the weakly connected components
+ * of the dependency graph are computed on the device in a fixed number of launches whatever the graph's diameter
+ * (gyeeta_amd/csrc/gys_svccomp.hpp: a lock-free union-find over the edge pairs).  Builder-defined.  The definition is FROZEN.
+ * The graph is exactly the one "Service dependency graph" above defines, at the moment of the call: the same live rule, registry, bindings.
+ *   COMPONENT two registered slots are in one component when a path of edges joins them, each edge taken in either direction.  Kinds
+ *             and parallel edges make no difference; an edge u == v joins nothing; a registered slot with no edge to another slot is a
+ *             component of its own.
+ *   COMP      comp[slot] = the LOWEST slot number in the slot's component (so comp[comp[s]] == comp[s], and a component's root is one of
+ *             its members); GYS_NOSLOT for a free slot.  The result is a function of the graph alone: no launch shape and no order of the
+ *             device's atomics can change a bit of it.
+ *   COUNTS    ncomp = the components (the registered slots with comp[s] == s); nlinked = those with at least two members.
+ *   FIGURES   of a component, each summed modulo 2^64: nservices = its members; nrows = the live table entries that give at least one
+ *             edge (all edges of such an entry end at the entry's listener slot v; the entry belongs to comp[v]); nedges = the sum of those
+ *             entries' edge counts (self edges count); active_conns, bytes_sent, bytes_received = summed ONCE PER ENTRY, not once per
+ *             edge: an entry whose client group owns 70 listeners is one flow, not 70.  Rows that give no edge (rows_no_listener,
+ *             rows_no_client) belong to no component.
+ * Nothing is cached between calls.  Single rank, like the table.  Every call below answers GYS_ERR_STATE when actconn_pair_cap is 0.
+ * MEMBERS of the component of service X need no call of their own: they are what gys_svc_deps(X, GYS_DEP_BOTH, 0) reaches.
+ * TOP COMPONENTS by a roll-up figure need none either -- the labels, a grouped roll-up, the selection.  "The 20 applications with the
+ * worst p99":
+ *     gys_label_service_components(ctx, 2, &ngroups);                                              label = component root, linked ones only
+ *     gys_rollup_filtered_dev(ctx, &all, GYS_RF_ANY_STATE, GYS_GROUP_LABEL, -1, 0, rows, ngroups, &nrows, d_slabs, NULL, NULL);
+ *                                                                                                  one slab per component, rows[r].group = its root slot
+ *     q = 0.99;  gys_tdigest_slab_quantiles_dev(ctx, d_slabs, nrows, &q, 1, d_p99);                d_p99[r]
+ *     gys_tdigest_slab_ranks_dev(ctx, d_slabs, nrows, &x, 1, d_below, d_total);                    d_total[r]: components without data drop out
+ *     gys_topk_dev(ctx, d_p99, 1, nrows, NULL, d_total, 1, GYS_TOPK_LARGEST, 20, out, &n, NULL);   rows[out[i].row].group = the root slot
+ * and likewise with d_est ("most distinct clients per application") or the gys_hist_rollup_*_filtered_dev family ("5-minute histogram
+ * per application"). */
+/* d_comp (DEVICE, gys_num_services words) = COMP of every slot.  ncomp / nlinked may be NULL: the counts cost two more launches, and are
+ * computed only when one is asked for.  One small read of the counter words inside the call besides the two of the edge build; the
+ * launches and reads of a call do not depend on the graph.  No engine state is modified.  GYS_ERR_INVAL: NULL d_comp.  With no
+ * registered service nothing is written and the counts are 0. */
+int gys_svc_components_dev(gys_ctx *ctx, uint32_t *d_comp, uint32_t *ncomp, uint32_t *nlinked);
+typedef struct { /* 64 bytes */
+	uint32_t root_slot, nservices;
+	uint64_t root_glob_id, nedges, nrows, active_conns, bytes_sent, bytes_received, reserved /* 0 */;
+} gys_svc_component;
+/* the components with nservices >= min_services (0 and 1: all) on the HOST, ordered by (nservices descending, root_slot ascending), with
+ * their FIGURES.  *nmatch = such components, *ncomp (may be NULL) = all components.  *nmatch > cap: GYS_ERR_NOMEM, *nmatch and *ncomp
+ * are set, *nout = 0 and nothing else is written.  No engine state is modified.  GYS_ERR_INVAL: NULL nout or nmatch, cap > 0 without out. */
+int gys_svc_components(gys_ctx *ctx, uint32_t min_services, gys_svc_component *out, uint32_t cap, uint32_t *nout, uint32_t *nmatch,
+		       uint32_t *ncomp);
+/* The components as roll-up groups: the label (gys_set_service_groups, GYS_GROUP_LABEL) of EVERY slot below gys_num_services becomes
+ * comp[slot] when its component has >= min_services members and GYS_NO_GROUP otherwise (free slots included) -- the labels are then
+ * exactly what gys_set_service_groups would have left for the same assignment, and whatever label a slot carried before is gone.
+ * *ngroups (may be NULL) = the labels in use, i.e. the components with >= min_services members.  The label array is allocated and cleared
+ * on first use as gys_set_service_groups does; the label domain is raised to at least gys_num_services (a root slot is below max_services:
+ * every rule of the labels holds).  The one call of the three that modifies engine state.
+ * The labels are a SNAPSHOT: they do not follow the graph.  Rows that expire, new rows and new bindings change the components, not the
+ * labels, until the call is made again; a later gys_delete_listeners or registration treats these labels as it treats caller-set ones
+ * (a deleted service's label is cleared, a new one starts at GYS_NO_GROUP), so a group may lose the member whose slot names it. */
+int gys_label_service_components(gys_ctx *ctx, uint32_t min_services, uint32_t *ngroups);
+
+/* -------------------------------------------------------------------------------------------------------------------
  * service records: saving, restoring and moving per-service state.  The reference's durable copy of a listener's statistics is Postgres;
  * after a restart the 5-day statistics are re-seeded (handle_listener_req, server/gy_mconnhdlr.cc:14257) through
  * GY_HISTOGRAM::get_serialized / update_from_serialized (common/gy_statistics.h:641-673).  Here the state lives in device memory: the
