@@ -179,6 +179,27 @@ class SvcComponent(C.Structure):  # gys_svc_component, 64 bytes
 assert C.sizeof(SvcComponent) == 64
 
 
+GES_BY_SRC, GES_BY_DST, GES_NO_SELF = 1, 2, 4  # GYS_GES_*
+GF_LDS_KEYS = 512  # GYS_GF_LDS_KEYS
+
+
+class GroupEdge(C.Structure):  # gys_group_edge, 64 bytes
+    _fields_ = [("src_group", C.c_uint32), ("dst_group", C.c_uint32), ("nedges", C.c_uint64), ("nrows", C.c_uint64), ("active_conns", C.c_uint64),
+                ("bytes_sent", C.c_uint64), ("bytes_received", C.c_uint64), ("last_window", C.c_uint32), ("kinds", C.c_uint8), ("flags", C.c_uint8),
+                ("pad", C.c_uint8 * 2), ("reserved", C.c_uint64)]
+
+
+class GroupEdgeSel(C.Structure):  # gys_group_edge_sel
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("src_group", C.c_uint32), ("dst_group", C.c_uint32)]
+
+
+class GroupFlowStats(C.Structure):  # gys_group_flow_stats
+    _fields_ = [("edges", C.c_uint64), ("edges_no_group", C.c_uint64), ("group_edges", C.c_uint64), ("self_group_edges", C.c_uint64)]
+
+
+assert C.sizeof(GroupEdge) == 64 and C.sizeof(GroupEdgeSel) == 16 and C.sizeof(GroupFlowStats) == 32
+
+
 class TopkEntry(C.Structure):   # gys_topk_entry
     _fields_ = [("row", C.c_uint32), ("reserved", C.c_uint32), ("value", C.c_double), ("weight", C.c_uint64)]
 
@@ -292,6 +313,10 @@ SIGNATURES = {
     "gys_svc_components_dev": (C.c_int, [vp, vp, u32p, u32p]),
     "gys_svc_components": (C.c_int, [vp, C.c_uint32, C.POINTER(SvcComponent), C.c_uint32, u32p, u32p, u32p]),
     "gys_label_service_components": (C.c_int, [vp, C.c_uint32, u32p]),
+    "gys_group_edges_dev": (C.c_int, [vp, C.c_int, C.POINTER(GroupEdgeSel), vp, C.c_uint32, u32p, C.POINTER(GroupFlowStats)]),
+    "gys_group_edges": (C.c_int, [vp, C.c_int, C.POINTER(GroupEdgeSel), C.POINTER(GroupEdge), C.c_uint32, u32p, u32p, C.POINTER(GroupFlowStats)]),
+    "gys_group_deps_dev": (C.c_int, [vp, C.c_int, u32p, C.c_uint32, C.c_uint32, C.c_uint32, vp, u32p, u32p]),
+    "gys_group_deps": (C.c_int, [vp, C.c_int, u32p, C.c_uint32, C.c_uint32, C.c_uint32, u32p, u32p, C.c_uint32, u32p, u32p]),
     "gys_rccl_unique_id": (C.c_int, [u8p]),
     "gys_rccl_comm_create": (C.c_int, [vp, u8p, C.c_int, C.c_int, C.POINTER(vp)]),
     "gys_rccl_comm_destroy": (C.c_int, [vp]),

@@ -49,6 +49,7 @@
 #include "gys_svcdeps.hpp"
 #include "gys_svcdeps_host.hpp"
 #include "gys_svccomp.hpp"
+#include "gys_groupflow.hpp"
 
 using namespace gys;
 
@@ -287,6 +288,13 @@ struct gys_ctx {
 	DevBuf<uint32_t> cc_parent, cc_comp, cc_size, cc_index;
 	DevBuf<uint2> cc_list;
 	DevBuf<unsigned long long> cc_acc, cc_ctr; // [listed][GYS_CC_ACC], [CCC_NUM]
+	// group flow map (gys_groupflow.hpp, gys_groupflow_engine.hpp): scratch of one call (grows; nothing before the first call) -- the keyed
+	// table (keys, GYS_GF_ACC words each), the first-of-group flags of the task -> services list and their hash-minimum table, the rows of
+	// the host form, the group pairs and distances of the search, the counter words
+	DevBuf<unsigned long long> gf_keys, gf_acc, gf_hkey, gf_ctr; // [entries], [entries][GYS_GF_ACC], [flag table], [GFC_NUM]
+	DevBuf<uint32_t> gf_first, gf_hmin, gf_hops;
+	DevBuf<uint2> gf_pairs;
+	DevBuf<gys_group_edge> gf_rows;
 	uint32_t epoch = 1;      // current window number (0 = never)
 	bool prepared = false;
 	DevBuf<uint32_t> d_epoch; // device copy of `epoch` for the captured window graph
@@ -4847,6 +4855,7 @@ try {
 #include "gys_actpairs_host.hpp"
 #include "gys_svcdeps_engine.hpp"
 #include "gys_svccomp_engine.hpp"
+#include "gys_groupflow_engine.hpp"
 #include "gys_json.hpp"
 #include "gys_regex.hpp"
 #include "gys_svcquery_host.hpp"

@@ -99,6 +99,27 @@ int dep_edges_run(gys_ctx *c, DepEdgeP p, void *out, uint32_t cap, uint64_t *ned
 	return GYS_OK;
 }
 
+// the levels of the search over `ne` pairs of indices below `n` (slots; the group flow map searches its group pairs over the domain), a few
+// per read of the "changed" word; a level that claims nothing ends the search (at most n - 1 levels claim)
+int dep_levels_run(gys_ctx *c, const uint2 *pairs, uint64_t ne, uint32_t *d_hops, uint32_t n, uint32_t dir, uint32_t max_hops)
+{
+	const uint32_t last = max_hops ? std::min(max_hops, n) : n;
+	const uint32_t egrid = std::max(1u, (uint32_t)std::min<uint64_t>((ne + 255u) / 256u, (uint64_t)c->ncu * 8));
+	ProfScope ps(c, "dep_levels");
+	for (uint32_t level = 0; level < last;) {
+		HIPCHK(hipMemsetAsync(c->dep_ctr.p + DPC_CHANGED, 0, sizeof(unsigned long long), c->stream));
+		const uint32_t upto = std::min(last, level + 4u);
+		for (; level < upto; ++level)
+			hipLaunchKernelGGL(k_dep_level, dim3(egrid), dim3(256), 0, c->stream, pairs, ne, d_hops, n, level, dir, c->dep_ctr.p + DPC_CHANGED);
+		HIPCHK(hipGetLastError());
+		unsigned long long changed = 0;
+		HIPCHK(hipMemcpyAsync(&changed, c->dep_ctr.p + DPC_CHANGED, sizeof(changed), hipMemcpyDeviceToHost, c->stream));
+		HIPCHK(hipStreamSynchronize(c->stream));
+		if (!changed) break;
+	}
+	return GYS_OK;
+}
+
 // the reached slots of c->dep_hops / d_hops from the roots; *nreached = their number
 int dep_traverse(gys_ctx *c, const uint64_t *root_ids, uint32_t nroots, uint32_t dir, uint32_t max_hops, uint32_t *d_hops, uint32_t *nreached)
 {
@@ -133,33 +154,19 @@ int dep_traverse(gys_ctx *c, const uint64_t *root_ids, uint32_t nroots, uint32_t
 			set_err("the edge count moved between the passes (%llu, %llu)", (unsigned long long)ne, (unsigned long long)ne2);
 			return GYS_ERR_INTERNAL;
 		}
-		// levels, a few per read of the "changed" word; a level that claims nothing ends the search (at most nsvc - 1 levels claim)
-		const uint32_t last = max_hops ? std::min(max_hops, c->nsvc) : c->nsvc;
-		const uint32_t egrid = std::max(1u, (uint32_t)std::min<uint64_t>((ne + 255u) / 256u, (uint64_t)c->ncu * 8));
-		ProfScope ps(c, "dep_levels");
-		for (uint32_t level = 0; level < last;) {
-			HIPCHK(hipMemsetAsync(c->dep_ctr.p + DPC_CHANGED, 0, sizeof(unsigned long long), c->stream));
-			const uint32_t upto = std::min(last, level + 4u);
-			for (; level < upto; ++level)
-				hipLaunchKernelGGL(k_dep_level, dim3(egrid), dim3(256), 0, c->stream, (const uint2 *)c->dep_pairs.p, ne, d_hops, c->nsvc, level, dir, c->dep_ctr.p + DPC_CHANGED);
-			HIPCHK(hipGetLastError());
-			unsigned long long changed = 0;
-			HIPCHK(hipMemcpyAsync(&changed, c->dep_ctr.p + DPC_CHANGED, sizeof(changed), hipMemcpyDeviceToHost, c->stream));
-			HIPCHK(hipStreamSynchronize(c->stream));
-			if (!changed) break;
-		}
+		if ((rc = dep_levels_run(c, (const uint2 *)c->dep_pairs.p, ne, d_hops, c->nsvc, dir, max_hops)) != GYS_OK) return rc;
 	}
 	return GYS_OK;
 }
 
-// the reached slots of d_hops: counted, and with `hits` compacted into c->dep_hits (room for `cap`)
-int dep_collect(gys_ctx *c, const uint32_t *d_hops, uint2 *d_hits, uint32_t cap, uint32_t *nreached)
+// the reached of the `n` words of d_hops: counted, and with d_hits compacted into it (room for `cap`)
+int dep_collect(gys_ctx *c, const uint32_t *d_hops, uint32_t n, uint2 *d_hits, uint32_t cap, uint32_t *nreached)
 {
 	*nreached = 0;
-	if (!c->nsvc) return GYS_OK;
+	if (!n) return GYS_OK;
 	HIPCHK(hipMemsetAsync(c->dep_ctr.p + DPC_REACHED, 0, sizeof(unsigned long long), c->stream));
-	const uint32_t sgrid = std::max(1u, (uint32_t)std::min<uint64_t>(((uint64_t)c->nsvc + 255u) / 256u, (uint64_t)c->ncu * 8));
-	hipLaunchKernelGGL(k_dep_collect, dim3(sgrid), dim3(256), 0, c->stream, d_hops, c->nsvc, d_hits, d_hits ? cap : 0u, c->dep_ctr.p + DPC_REACHED);
+	const uint32_t sgrid = std::max(1u, (uint32_t)std::min<uint64_t>(((uint64_t)n + 255u) / 256u, (uint64_t)c->ncu * 8));
+	hipLaunchKernelGGL(k_dep_collect, dim3(sgrid), dim3(256), 0, c->stream, d_hops, n, d_hits, d_hits ? cap : 0u, c->dep_ctr.p + DPC_REACHED);
 	HIPCHK(hipGetLastError());
 	unsigned long long cnt = 0;
 	HIPCHK(hipMemcpyAsync(&cnt, c->dep_ctr.p + DPC_REACHED, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
@@ -280,7 +287,7 @@ try {
 	ACTP_CHECK();
 	const int rc = dep_traverse(c, root_ids, nroots, dir, max_hops, d_hops, nreached);
 	if (rc) return rc;
-	return dep_collect(c, d_hops, nullptr, 0u, nreached);
+	return dep_collect(c, d_hops, c->nsvc, nullptr, 0u, nreached);
 } GYS_CATCH_ALL
 
 int gys_svc_deps(gys_ctx *c, const uint64_t *root_ids, uint32_t nroots, uint32_t dir, uint32_t max_hops, uint64_t *glob_ids, uint32_t *hops, uint32_t cap,
@@ -297,7 +304,7 @@ try {
 	if ((rc = dep_traverse(c, root_ids, nroots, dir, max_hops, c->dep_hops.p, nreached)) != GYS_OK) return rc;
 	const uint32_t dcap = std::min(cap, c->nsvc);
 	if ((rc = c->dep_hits.grow(std::max(dcap, 1u), c->stream)) != GYS_OK) return rc;
-	if ((rc = dep_collect(c, c->dep_hops.p, c->dep_hits.p, dcap, nreached)) != GYS_OK) return rc;
+	if ((rc = dep_collect(c, c->dep_hops.p, c->nsvc, c->dep_hits.p, dcap, nreached)) != GYS_OK) return rc;
 	if (*nreached > cap) {
 		set_err("%u services reached, room for %u", *nreached, cap);
 		return GYS_ERR_NOMEM;

@@ -487,6 +487,77 @@ class SketchEngine:
         self._label_domain = max(getattr(self, "_label_domain", 0), self.num_services())  # (a root slot is a label: see set_service_groups)
         return n.value
 
+    # ---------------------------------------------------------------- group flow map (actconn_pair_cap; "Group flow map")
+    GROUP_EDGE_DT = np.dtype([("src_group", "<u4"), ("dst_group", "<u4"), ("nedges", "<u8"), ("nrows", "<u8"), ("active_conns", "<u8"),
+                              ("bytes_sent", "<u8"), ("bytes_received", "<u8"), ("last_window", "<u4"), ("kinds", "u1"), ("flags", "u1"),
+                              ("pad", "u1", 2), ("reserved", "<u8")])
+
+    @staticmethod
+    def group_edge_sel(src=None, dst=None, no_self=False):
+        """a gys_group_edge_sel: src / dst = the calling / the called group; no_self leaves out the rows with src_group == dst_group"""
+        s = capi.GroupEdgeSel()
+        s.struct_size = C.sizeof(capi.GroupEdgeSel)
+        if src is not None:
+            s.flags |= capi.GES_BY_SRC
+            s.src_group = int(src)
+        if dst is not None:
+            s.flags |= capi.GES_BY_DST
+            s.dst_group = int(dst)
+        if no_self:
+            s.flags |= capi.GES_NO_SELF
+        return s
+
+    def group_edges_dev(self, group_by, sel=None, cap=0):
+        """gys_group_edges_dev -> (torch uint8 device tensor of cap rows of 64 bytes, the first min(matches, cap) written in any order;
+        number of matches; the gys_group_flow_stats of the whole map as a dict)"""
+        out = self.torch.zeros((max(cap, 1), 64), dtype=self.torch.uint8, device=self.device)
+        nmatch, st = C.c_uint32(), capi.GroupFlowStats()
+        self.order()
+        capi.check(self.L.gys_group_edges_dev(self.h, group_by, C.byref(sel) if sel is not None else None, C.c_void_p(out.data_ptr()), cap, C.byref(nmatch),
+                                              C.byref(st)))
+        return out, nmatch.value, {k: getattr(st, k) for k, _ in capi.GroupFlowStats._fields_}
+
+    def group_edges(self, group_by, sel=None, cap=None):
+        """gys_group_edges -> (rc, group edges as a numpy GROUP_EDGE_DT array in (src_group, dst_group) order, number of matches, stats);
+        rc is capi.ERR_NOMEM (and the array empty) when more match than cap.  cap None = as many as match"""
+        ref = C.byref(sel) if sel is not None else None
+        if cap is None:
+            cap = self.group_edges_dev(group_by, sel, 0)[1]
+        out = (capi.GroupEdge * max(cap, 1))()
+        nout, nmatch, st = C.c_uint32(), C.c_uint32(), capi.GroupFlowStats()
+        rc = self.L.gys_group_edges(self.h, group_by, ref, out, cap, C.byref(nout), C.byref(nmatch), C.byref(st))
+        if rc not in (capi.OK, capi.ERR_NOMEM):
+            capi.check(rc)
+        return rc, np.frombuffer(out, dtype=self.GROUP_EDGE_DT, count=nout.value).copy(), nmatch.value, {k: getattr(st, k) for k, _ in capi.GroupFlowStats._fields_}
+
+    def _group_domain_cap(self, group_by):
+        cfg = self.cfg
+        return max(int(cfg.max_services if group_by == capi.GROUP_LABEL else cfg.max_clusters if group_by == capi.GROUP_CLUSTER else cfg.max_hosts), 1)
+
+    def group_deps_dev(self, group_by, roots, direction=capi.DEP_CALLEES, max_hops=0):
+        """gys_group_deps_dev -> (torch int32 device tensor [domain]: hops per group, -1 (GYS_NOSLOT) where not reached; groups reached)"""
+        r = np.ascontiguousarray(roots, dtype=np.uint32)
+        out = self.torch.zeros(self._group_domain_cap(group_by), dtype=self.torch.int32, device=self.device)
+        nd, n = C.c_uint32(), C.c_uint32()
+        self.order()
+        capi.check(self.L.gys_group_deps_dev(self.h, group_by, r.ctypes.data_as(capi.u32p), len(r), direction, max_hops, C.c_void_p(out.data_ptr()), C.byref(nd),
+                                             C.byref(n)))
+        return out[:nd.value], n.value
+
+    def group_deps(self, group_by, roots, direction=capi.DEP_CALLEES, max_hops=0, cap=None):
+        """gys_group_deps -> (rc, groups, hops, groups reached) ordered by (hops, group); rc is capi.ERR_NOMEM (and the arrays empty) when
+        more groups are reached than cap.  cap None = the largest domain the grouping can have"""
+        r = np.ascontiguousarray(roots, dtype=np.uint32)
+        if cap is None:
+            cap = self._group_domain_cap(group_by)
+        groups, hops = np.zeros(max(cap, 1), dtype=np.uint32), np.zeros(max(cap, 1), dtype=np.uint32)
+        nout, n = C.c_uint32(), C.c_uint32()
+        rc = self.L.gys_group_deps(self.h, group_by, r.ctypes.data_as(capi.u32p), len(r), direction, max_hops, groups.ctypes.data_as(capi.u32p),
+                                   hops.ctypes.data_as(capi.u32p), cap, C.byref(nout), C.byref(n))
+        if rc not in (capi.OK, capi.ERR_NOMEM):
+            capi.check(rc)
+        return rc, groups[:nout.value].copy(), hops[:nout.value].copy(), n.value
+
     def handle_comm_stream(self, machine_id, stream_bytes):
         """L1 + L2 of madhava for one partha connection: COMM_HEADER-framed messages -> partha_tcp_conn_info / partha_listener_state"""
         buf = np.frombuffer(stream_bytes, dtype=np.uint8)

@@ -1213,6 +1213,77 @@ int gys_svc_components(gys_ctx *ctx, uint32_t min_services, gys_svc_component *o
 int gys_label_service_components(gys_ctx *ctx, uint32_t min_services, uint32_t *ngroups);
 
 /* -------------------------------------------------------------------------------------------------------------------
+ * Group flow map: "which cluster talks to which cluster, and how many bytes?  Which hosts does this host depend on?  Which applications
+ * feed this one?" -- the dependency graph rolled up to the groups every other roll-up of the library answers for.  It is the view the
+ * reference's flow dashboards open with, before anyone drills down to a service.  Here it is a keyed aggregation on the device over the
+ * edges of the join (gyeeta_amd/csrc/gys_groupflow.hpp).  Builder-defined.  The definition is FROZEN.
+ * The graph is exactly the one "Service dependency graph" above defines, at the moment of the call: the same live rule, registry and
+ * bindings, and both kinds of row.
+ *   GROUP       of a slot: the rule of gys_rollup_filtered_dev.  group_by is GYS_GROUP_HOST (the slot's host slot), _CLUSTER (its host's
+ *               cluster index) or _LABEL (its label); the domains are the registered hosts, the clusters, and the label domain (every
+ *               label set so far is below it).  A slot whose group is GYS_NO_GROUP is in no group: a slot with no label, and a label at
+ *               or above the domain.  GYS_GROUP_NONE is refused with GYS_ERR_INVAL.  If no label was ever set and group_by is _LABEL,
+ *               the call returns GYS_OK with zero rows.
+ *   GROUP EDGE  (gu, gv) exists when at least one service edge u -> v has group(u) = gu and group(v) = gv, both real groups.  Kinds and
+ *               parallel edges fall into the same group edge.  gu == gv is a group edge like any other: intra-group traffic.
+ *   FIGURES     of a group edge, all integers, sums modulo 2^64 -- they do not depend on the order of the device's atomics, and every
+ *               comparison is exact.  nedges = the service edges that map to it.  nrows = the live table ENTRIES that contribute.
+ *               active_conns, bytes_sent, bytes_received = summed ONCE PER ENTRY AND GROUP EDGE: an entry (L, T, k) has one listener slot
+ *               v and m caller slots; it adds its figures once to each DISTINCT (group(u), group(v)) among its m edges, not m times (the
+ *               rule of the components: "an entry whose client group owns 70 listeners is one flow, not 70" -- a process group with three
+ *               listeners on one host is otherwise counted three times in every HOST and CLUSTER map).  last_window = the maximum of the
+ *               entries' window.  kinds: bit 0 is set when a kind-0 entry contributes, bit 1 for a kind-1 entry.  flags = the entries'
+ *               flag bytes ORed.
+ *   STATS       edges = all service edges (gys_svcgraph_stats.edges); edges_no_group = service edges with an end in no group;
+ *               group_edges = the distinct (gu, gv) pairs; self_group_edges = those with gu == gv.
+ *   GROUP HOPS  hops[g] = the least number of group edges with gu != gv from any root group to g along the chosen direction (GYS_DEP_*);
+ *               0 for a root, GYS_NOSLOT for a group that is not reached.  A root group below the domain is at 0 even if it has no
+ *               service; a root at or above the domain is skipped.
+ * Nothing is cached between calls, nothing is allocated before the first call, no engine state is modified.  A call makes a fixed number
+ * of small reads whatever the graph holds (the search: one more per few levels).  Single rank, like the table.  Every call below answers
+ * GYS_ERR_STATE when actconn_pair_cap is 0.
+ * GYS_GF_LDS_KEYS: the accumulation sums the equal keys of a tile of 256 table entries in an on-chip table of this many distinct
+ * (gu, gv) pairs before anything goes to device memory; a tile that yields more pairs sends the rest to device memory directly.  It
+ * changes no result. */
+#define GYS_GF_LDS_KEYS 512u
+typedef struct { /* 64 bytes */
+	uint32_t src_group, dst_group;
+	uint64_t nedges, nrows, active_conns, bytes_sent, bytes_received;
+	uint32_t last_window;
+	uint8_t kinds, flags, pad[2];
+	uint64_t reserved; /* 0 */
+} gys_group_edge;
+enum { GYS_GES_BY_SRC = 1, GYS_GES_BY_DST = 2, GYS_GES_NO_SELF = 4 };
+typedef struct {
+	uint32_t struct_size; /* = sizeof(gys_group_edge_sel) */
+	uint32_t flags;       /* GYS_GES_*; a group that does not exist matches nothing; _NO_SELF leaves out the rows with src_group == dst_group */
+	uint32_t src_group, dst_group;
+} gys_group_edge_sel;
+typedef struct {
+	uint64_t edges, edges_no_group, group_edges, self_group_edges;
+} gys_group_flow_stats;
+/* the group edges the selection matches (sel NULL = all), into the DEVICE array d_out in any order: min(*nmatch, cap) rows are written
+ * (d_out may be NULL with cap 0: a count).  The selection applies to the rows returned; *stats (may be NULL) always describes the whole
+ * map.  GYS_ERR_INVAL: NULL nmatch, group_by outside GYS_GROUP_HOST .. _LABEL, a wrong struct_size, unknown flags, cap > 0 without
+ * d_out.  More than 2^32 - 1 service edges or more than 2^30 possible group edges: GYS_ERR_NOMEM. */
+int gys_group_edges_dev(gys_ctx *ctx, int group_by, const gys_group_edge_sel *sel, gys_group_edge *d_out, uint32_t cap, uint32_t *nmatch,
+			gys_group_flow_stats *stats);
+/* the same on the HOST, ordered by (src_group, dst_group) ascending.  *nmatch > cap: GYS_ERR_NOMEM, *nmatch and *stats are set,
+ * *nout = 0 and nothing else is written. */
+int gys_group_edges(gys_ctx *ctx, int group_by, const gys_group_edge_sel *sel, gys_group_edge *out, uint32_t cap, uint32_t *nout,
+		    uint32_t *nmatch, gys_group_flow_stats *stats);
+/* d_hops[g] (DEVICE, one word per group of the domain: at most gys_config.max_hosts words for _HOST, max_clusters for _CLUSTER,
+ * max_services for _LABEL) = GROUP HOPS from the groups root_groups (HOST array) names; max_hops 0 = no limit, otherwise groups further away stay
+ * GYS_NOSLOT.  A root named twice counts once.  *ndomain (may be NULL) = the words written, *nreached = the groups reached, roots
+ * included.  GYS_ERR_INVAL: dir outside 1 .. 3, NULL d_hops, NULL nreached, NULL root_groups with nroots != 0, a bad group_by. */
+int gys_group_deps_dev(gys_ctx *ctx, int group_by, const uint32_t *root_groups, uint32_t nroots, uint32_t dir, uint32_t max_hops,
+		       uint32_t *d_hops, uint32_t *ndomain, uint32_t *nreached);
+/* the same on the HOST: the reached groups and their distances ordered by (hops, group) ascending.  *nreached > cap: GYS_ERR_NOMEM,
+ * *nreached is set, *nout = 0 and nothing else is written. */
+int gys_group_deps(gys_ctx *ctx, int group_by, const uint32_t *root_groups, uint32_t nroots, uint32_t dir, uint32_t max_hops, uint32_t *groups,
+		   uint32_t *hops, uint32_t cap, uint32_t *nout, uint32_t *nreached);
+
+/* -------------------------------------------------------------------------------------------------------------------
  * service records: saving, restoring and moving per-service state.  The reference's durable copy of a listener's statistics is Postgres;
  * after a restart the 5-day statistics are re-seeded (handle_listener_req, server/gy_mconnhdlr.cc:14257) through
  * GY_HISTOGRAM::get_serialized / update_from_serialized (common/gy_statistics.h:641-673).  Here the state lives in device memory: the
