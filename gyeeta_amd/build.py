@@ -7,7 +7,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libgysketch.so")
 SOURCES = ["gys_engine.hip"]
-DEPS = ["gys_engine.hip", "gys_devmem.hpp", "gys_subq.hpp", "gys_kernels.hpp", "gys_rollup.hpp", "gys_rollup_host.hpp", "gys_groups.hpp", "gys_resp_plan.hpp", "gys_hostlst.hpp", "gys_hllroll.hpp", "gys_histroll.hpp", "gys_huge.hpp", "gys_device.hpp", "gys_json.hpp", "gys_svcquery.hpp", "gys_svcquery_host.hpp", "gys_rollsel.hpp", "gys_rollsel_host.hpp", "gys_svcdel.hpp", "gys_svcpack.hpp", "gys_tdrank.hpp", "gys_topk.hpp", "gys_topk_host.hpp", "gys_actpairs.hpp", "gys_actpairs_host.hpp", "gys_svcdeps.hpp", "gys_svcdeps_host.hpp", "gys_svcdeps_engine.hpp", "gys_svccomp.hpp", "gys_svccomp_engine.hpp", "gys_groupflow.hpp", "gys_groupflow_engine.hpp", "gys_regex.hpp", "gys_mconn_shim.hpp", "../../include/gysketch.h", "../../include/gys_tdigest_tbl.h"]
+DEPS = ["gys_engine.hip", "gys_devmem.hpp", "gys_subq.hpp", "gys_kernels.hpp", "gys_rollup.hpp", "gys_rollup_host.hpp", "gys_groups.hpp", "gys_resp_plan.hpp", "gys_hostlst.hpp", "gys_hllroll.hpp", "gys_histroll.hpp", "gys_huge.hpp", "gys_device.hpp", "gys_json.hpp", "gys_svcquery.hpp", "gys_svcquery_host.hpp", "gys_rollsel.hpp", "gys_rollsel_host.hpp", "gys_svcdel.hpp", "gys_svcpack.hpp", "gys_tdrank.hpp", "gys_topk.hpp", "gys_topk_host.hpp", "gys_actpairs.hpp", "gys_actpairs_host.hpp", "gys_svcdeps.hpp", "gys_svcdeps_host.hpp", "gys_svcdeps_engine.hpp", "gys_svccomp.hpp", "gys_svccomp_engine.hpp", "gys_groupflow.hpp", "gys_groupflow_engine.hpp", "gys_svcresol.hpp", "gys_svcresol_engine.hpp", "gys_regex.hpp", "gys_mconn_shim.hpp", "../../include/gysketch.h", "../../include/gys_tdigest_tbl.h"]
 
 
 def hipcc():

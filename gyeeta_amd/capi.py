@@ -200,6 +200,29 @@ class GroupFlowStats(C.Structure):  # gys_group_flow_stats
 assert C.sizeof(GroupEdge) == 64 and C.sizeof(GroupEdgeSel) == 16 and C.sizeof(GroupFlowStats) == 32
 
 
+RESOL_MAX_TIERS = 8  # GYS_RESOL_MAX_TIERS
+RS_NONE, RS_SOURCE, RS_RESOLVED, RS_CARRIER, RS_UNRESOLVED = 0, 1, 2, 3, 4  # GYS_RS_*
+
+
+class SvcResol(C.Structure):  # gys_svc_resol, 16 bytes
+    _fields_ = [("src_slot", C.c_uint32), ("via_slot", C.c_uint32), ("role", C.c_uint8), ("tier", C.c_uint8), ("state", C.c_uint8), ("issue", C.c_uint8),
+                ("nresolved", C.c_uint32)]
+
+
+class SvcResolStats(C.Structure):  # gys_svc_resol_stats
+    _fields_ = [("with_state", C.c_uint64), ("sources", C.c_uint64), ("resolved", C.c_uint64), ("unresolved", C.c_uint64), ("carriers", C.c_uint64),
+                ("edges", C.c_uint64), ("resolved_at_tier", C.c_uint64 * 8)]
+
+
+class SvcResolRow(C.Structure):  # gys_svc_resol_row, 48 bytes
+    _fields_ = [("glob_id", C.c_uint64), ("src_glob_id", C.c_uint64), ("via_glob_id", C.c_uint64), ("slot", C.c_uint32), ("src_slot", C.c_uint32),
+                ("via_slot", C.c_uint32), ("nresolved", C.c_uint32), ("role", C.c_uint8), ("tier", C.c_uint8), ("state", C.c_uint8), ("issue", C.c_uint8),
+                ("src_state", C.c_uint8), ("src_issue", C.c_uint8), ("pad", C.c_uint8 * 2)]
+
+
+assert C.sizeof(SvcResol) == 16 and C.sizeof(SvcResolStats) == 112 and C.sizeof(SvcResolRow) == 48
+
+
 class TopkEntry(C.Structure):   # gys_topk_entry
     _fields_ = [("row", C.c_uint32), ("reserved", C.c_uint32), ("value", C.c_double), ("weight", C.c_uint64)]
 
@@ -317,6 +340,8 @@ SIGNATURES = {
     "gys_group_edges": (C.c_int, [vp, C.c_int, C.POINTER(GroupEdgeSel), C.POINTER(GroupEdge), C.c_uint32, u32p, u32p, C.POINTER(GroupFlowStats)]),
     "gys_group_deps_dev": (C.c_int, [vp, C.c_int, u32p, C.c_uint32, C.c_uint32, C.c_uint32, vp, u32p, u32p]),
     "gys_group_deps": (C.c_int, [vp, C.c_int, u32p, C.c_uint32, C.c_uint32, C.c_uint32, u32p, u32p, C.c_uint32, u32p, u32p]),
+    "gys_svc_resolve_issues_dev": (C.c_int, [vp, vp, C.c_uint32, vp, vp, C.POINTER(SvcResolStats)]),
+    "gys_svc_resolve_issues": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(SvcResolRow), C.c_uint32, u32p, u32p, C.POINTER(SvcResolStats)]),
     "gys_rccl_unique_id": (C.c_int, [u8p]),
     "gys_rccl_comm_create": (C.c_int, [vp, u8p, C.c_int, C.c_int, C.POINTER(vp)]),
     "gys_rccl_comm_destroy": (C.c_int, [vp]),

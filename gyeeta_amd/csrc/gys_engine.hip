@@ -50,6 +50,7 @@
 #include "gys_svcdeps_host.hpp"
 #include "gys_svccomp.hpp"
 #include "gys_groupflow.hpp"
+#include "gys_svcresol.hpp"
 
 using namespace gys;
 
@@ -295,6 +296,13 @@ struct gys_ctx {
 	DevBuf<uint32_t> gf_first, gf_hmin, gf_hops;
 	DevBuf<uint2> gf_pairs;
 	DevBuf<gys_group_edge> gf_rows;
+	// issue resolution (gys_svcresol.hpp, gys_svcresol_engine.hpp): scratch of one call (grows; nothing before the first call) -- per slot the
+	// search's word (tier, class, state, issue), the 64-bit minimum (source << 32 | via) and a source's count of resolved slots; the records
+	// and the rows of the host form; the counter words
+	DevBuf<uint32_t> ri_word, ri_nres;
+	DevBuf<unsigned long long> ri_best, ri_ctr; // [nsvc], [RSC_NUM]
+	DevBuf<gys_svc_resol> ri_rec;
+	DevBuf<gys_svc_resol_row> ri_rows;
 	uint32_t epoch = 1;      // current window number (0 = never)
 	bool prepared = false;
 	DevBuf<uint32_t> d_epoch; // device copy of `epoch` for the captured window graph
@@ -4856,6 +4864,7 @@ try {
 #include "gys_svcdeps_engine.hpp"
 #include "gys_svccomp_engine.hpp"
 #include "gys_groupflow_engine.hpp"
+#include "gys_svcresol_engine.hpp"
 #include "gys_json.hpp"
 #include "gys_regex.hpp"
 #include "gys_svcquery_host.hpp"

@@ -558,6 +558,61 @@ class SketchEngine:
             capi.check(rc)
         return rc, groups[:nout.value].copy(), hops[:nout.value].copy(), n.value
 
+    # ---------------------------------------------------------------- issue resolution (actconn_pair_cap; "Issue resolution")
+    SVC_RESOL_DT = np.dtype([("src_slot", "<u4"), ("via_slot", "<u4"), ("role", "u1"), ("tier", "u1"), ("state", "u1"), ("issue", "u1"), ("nresolved", "<u4")])
+    SVC_RESOL_ROW_DT = np.dtype([("glob_id", "<u8"), ("src_glob_id", "<u8"), ("via_glob_id", "<u8"), ("slot", "<u4"), ("src_slot", "<u4"), ("via_slot", "<u4"),
+                                 ("nresolved", "<u4"), ("role", "u1"), ("tier", "u1"), ("state", "u1"), ("issue", "u1"), ("src_state", "u1"), ("src_issue", "u1"),
+                                 ("pad", "u1", 2)])
+
+    def _decisions_dev(self, dec):
+        """dec: None, a torch device tensor of gys_listener_decision records, or a numpy DECISION_DT array (copied to the device)"""
+        if dec is None or isinstance(dec, self.torch.Tensor):
+            return dec
+        assert dec.dtype == self.DECISION_DT and len(dec) == self.num_services()
+        return self.torch.from_numpy(np.frombuffer(np.ascontiguousarray(dec).tobytes(), dtype=np.uint8).copy()).to(self.device)
+
+    @staticmethod
+    def _resol_stats(st):
+        d = {k: getattr(st, k) for k, _ in capi.SvcResolStats._fields_}
+        d["resolved_at_tier"] = list(st.resolved_at_tier)
+        return d
+
+    def resolve_issues_dev(self, dec=None, max_tiers=0, impact=True):
+        """gys_svc_resolve_issues_dev -> (torch uint8 device tensor [num_services, 16]: the gys_svc_resol record of every slot; torch float64
+        device tensor [num_services]: nresolved of a source, NaN elsewhere (None with impact=False); the gys_svc_resol_stats as a dict).
+        dec = the decisions that replace the kept states (see _decisions_dev)"""
+        n = max(self.num_services(), 1)
+        d_dec = self._decisions_dev(dec)
+        out = self.torch.zeros((n, 16), dtype=self.torch.uint8, device=self.device)
+        imp = self.torch.zeros(n, dtype=self.torch.float64, device=self.device) if impact else None
+        st = capi.SvcResolStats()
+        self.order()
+        capi.check(self.L.gys_svc_resolve_issues_dev(self.h, C.c_void_p(d_dec.data_ptr()) if d_dec is not None else None, max_tiers, C.c_void_p(out.data_ptr()),
+                                                     C.c_void_p(imp.data_ptr()) if impact else None, C.byref(st)))
+        return out, imp, self._resol_stats(st)
+
+    def resolve_issues_np(self, dec=None, max_tiers=0):
+        """resolve_issues_dev copied to the host -> (numpy SVC_RESOL_DT array [num_services], numpy float64 impact column, stats)"""
+        out, imp, st = self.resolve_issues_dev(dec, max_tiers)
+        self.sync()
+        n = self.num_services()
+        return np.frombuffer(out.cpu().numpy().tobytes(), dtype=self.SVC_RESOL_DT)[:n].copy(), imp.cpu().numpy()[:n].copy(), st
+
+    def resolve_issues(self, dec=None, max_tiers=0, role_mask=0, cap=None):
+        """gys_svc_resolve_issues -> (rc, rows as a numpy SVC_RESOL_ROW_DT array in slot order, number of matches, stats); role_mask bit r
+        lists role r (0 = roles 1 .. 4); rc is capi.ERR_NOMEM (and the array empty) when more match than cap.  cap None = num_services"""
+        if cap is None:
+            cap = self.num_services()
+        d_dec = self._decisions_dev(dec)
+        out = (capi.SvcResolRow * max(cap, 1))()
+        nout, nmatch, st = C.c_uint32(), C.c_uint32(), capi.SvcResolStats()
+        self.order()
+        rc = self.L.gys_svc_resolve_issues(self.h, C.c_void_p(d_dec.data_ptr()) if d_dec is not None else None, max_tiers, role_mask, out, cap, C.byref(nout),
+                                           C.byref(nmatch), C.byref(st))
+        if rc not in (capi.OK, capi.ERR_NOMEM):
+            capi.check(rc)
+        return rc, np.frombuffer(out, dtype=self.SVC_RESOL_ROW_DT, count=nout.value).copy(), nmatch.value, self._resol_stats(st)
+
     def handle_comm_stream(self, machine_id, stream_bytes):
         """L1 + L2 of madhava for one partha connection: COMM_HEADER-framed messages -> partha_tcp_conn_info / partha_listener_state"""
         buf = np.frombuffer(stream_bytes, dtype=np.uint8)

@@ -307,3 +307,44 @@ def synth_active_conns(rng, n, host, svcs_per_host, ntasks=40, remote_listen_fra
     rec["active_conns"] = rng.integers(1, 200, n)
     rec["flags"] = np.where(rng.random(n) < remote_listen_frac, ACTIVE_FLAG_REMOTE_LISTEN, 0) | np.where(rng.random(n) < 0.1, ACTIVE_FLAG_CLI_LISTENER_PROC, 0)
     return rec
+
+
+# comm::MM_LISTENER_ISSUE_RESOL (common/gy_comm_proto.h:2588-2662): what one madhava tells another about an issue source and the listeners it
+# took down -- 48 fixed bytes followed by ndownstreams_ DOWNSTREAM_ONE of 12 bytes (alignment 1: the id is a byte buffer) and padding_len_
+# bytes up to a multiple of 8.  The reference's "downstream" listeners are the CALLERS the issue reached ("Issue resolution" in gysketch.h).
+MM_LISTENER_ISSUE_RESOL = np.dtype([("issue_src_glob_id", "<u8"), ("issue_src_madhava_id", "<u8"), ("issue_src_time_usec", "<u8"), ("issue_src_comm", "S16"),
+                                    ("ndownstreams", "<u2"), ("src_is_load_balanced", "u1"), ("src_state", "u1"), ("src_issue", "u1"), ("issue_bit_hist", "u1"),
+                                    ("padding_len", "u1"), ("tail_pad", "u1")])
+DOWNSTREAM_ONE = np.dtype([("downstream_glob_id_buf", "u1", 8), ("downstream_state", "u1"), ("downstream_issue", "u1"), ("downstream_issue_bit_hist", "u1"),
+                           ("src_upstream_tier", "u1")])
+assert MM_LISTENER_ISSUE_RESOL.itemsize == 48 and DOWNSTREAM_ONE.itemsize == 12
+MAX_DOWNSTREAM_IDS = 2048
+MAX_DOWNSTREAM_TIERS = 8
+RS_SOURCE, RS_RESOLVED, RS_CARRIER = 1, 2, 3  # GYS_RS_*
+
+
+def resol_messages(rows, madhava_id=0, time_usec=0, comm=b""):
+    """the host form's rows (SketchEngine.resolve_issues: SVC_RESOL_ROW_DT, sources and what they reached) as MM_LISTENER_ISSUE_RESOL
+    elements: per source, by slot, one element followed by the RESOLVED and CARRIER rows attributed to it as DOWNSTREAM_ONE in (tier, slot)
+    order, src_upstream_tier_ = tier, padded to 8.  A source that reached nothing gives no element (the reference skips an empty list);
+    one with more than MAX_DOWNSTREAM_IDS gives several.  The issue history bytes are not the resolution's: 0.
+    -> (payload bytes, number of elements)"""
+    rows = np.asarray(rows)
+    down = rows[(rows["role"] == RS_RESOLVED) | (rows["role"] == RS_CARRIER)]
+    down = down[np.lexsort((down["slot"], down["tier"], down["src_slot"]))]
+    out, nmsg = bytearray(), 0
+    for src in np.sort(rows[rows["role"] == RS_SOURCE], order="slot"):
+        lo, hi = np.searchsorted(down["src_slot"], src["slot"], "left"), np.searchsorted(down["src_slot"], src["slot"], "right")
+        for first in range(lo, hi, MAX_DOWNSTREAM_IDS):
+            part = down[first:min(hi, first + MAX_DOWNSTREAM_IDS)]
+            hdr = np.zeros(1, dtype=MM_LISTENER_ISSUE_RESOL)
+            hdr["issue_src_glob_id"], hdr["issue_src_madhava_id"], hdr["issue_src_time_usec"] = src["glob_id"], madhava_id, time_usec
+            hdr["issue_src_comm"], hdr["ndownstreams"], hdr["src_state"], hdr["src_issue"] = comm, len(part), src["state"], src["issue"]
+            one = np.zeros(len(part), dtype=DOWNSTREAM_ONE)
+            one["downstream_glob_id_buf"] = part["glob_id"].astype("<u8").view(np.uint8).reshape(-1, 8)
+            one["downstream_state"], one["downstream_issue"], one["src_upstream_tier"] = part["state"], part["issue"], part["tier"]
+            act = 48 + 12 * len(part)
+            hdr["padding_len"] = -act % 8
+            out += hdr.tobytes() + one.tobytes() + b"\0" * (-act % 8)
+            nmsg += 1
+    return bytes(out), nmsg

@@ -1284,6 +1284,78 @@ int gys_group_deps(gys_ctx *ctx, int group_by, const uint32_t *root_groups, uint
 		   uint32_t *hops, uint32_t cap, uint32_t *nout, uint32_t *nreached);
 
 /* -------------------------------------------------------------------------------------------------------------------
+ * Issue resolution: "400 services are red -- which 5 are the cause, and what did each one take down?"  One of the issue sources
+ * gys_decide_listener_state_dev returns is ISSUE_DEPENDENT_SERVER_LISTENER (= 7, common/gy_json_field_maps.h:419-434): "I am slow because
+ * something I call is slow".  The reference resolves those every 5 s inside MCONN_HANDLER::partha_listener_state: a listener that is Bad
+ * or worse with any OTHER issue is a source (server/gy_mconnhdlr.cc:11325-11349); from it handle_dependency_issue (:10866-10990) walks
+ * the listeners of the process groups that depend on it, recursing through those that are Bad with the dependent-listener issue, or OK
+ * (:10946-10947), for at most MM_LISTENER_ISSUE_RESOL::MAX_DOWNSTREAM_TIERS = 8 tiers (common/gy_comm_proto.h:2588-2660), and records
+ * the source, the tier and the neighbour the issue came through (LISTENER_ISSUE_RESOL, server/gy_msocket.h:28-35) -- a serial recursive
+ * hash walk per source.  Here it is a labelled multi-source search on the device over the edge pairs of the join
+ * (gyeeta_amd/csrc/gys_svcresol.hpp).  Builder-defined.  The definition is FROZEN.
+ * The graph is exactly the one "Service dependency graph" above defines, at the moment of the call: the same live rule, registry and
+ * bindings, both kinds of row, single rank.
+ * NAMING.  An issue travels from a callee v to its callers u: along the edges u -> v BACKWARDS, the GYS_DEP_CALLERS direction.  In this
+ * library a callee is downstream of its caller; the reference's words are the other way round (it calls the source "upstream" and the
+ * affected listeners its "downstreams").
+ *   STATE     of a slot: (state, issue) = bytes 79 and 80 (curr_state_, curr_issue_) of the slot's kept 88-byte LISTENER_STATE_NOTIFY
+ *             record, when that record is CURRENT -- the rule of the service queries: it was kept in the open window or the one before,
+ *             it is not marked deleted (a LISTEN_FLAG_DELETE record), and it names this slot's id and host.  With d_dec (a device array
+ *             of gys_listener_decision x gys_num_services, as gys_decide_listener_state_dev leaves it) (state, issue) = d_dec[slot].state
+ *             and .issue for every REGISTERED slot instead, whatever is kept.  A free slot, a slot without a current record and a
+ *             state above 5 have NO STATE.
+ *   CLASS     SOURCE: state >= 3 (Bad, Severe, Down) and issue != 7.  DEPENDENT: state >= 3 and issue == 7.  CARRIER: state == 2 (OK).
+ *             Everything else is OPAQUE (Idle, Good, no state).  Only DEPENDENT and CARRIER slots take an issue on and pass it further;
+ *             a SOURCE or OPAQUE slot on a path blocks it, and a SOURCE is never attributed to another source.
+ *   TIER      tier 0 = the SOURCE slots, each its own source.  A DEPENDENT or CARRIER slot u that is not yet attributed gets tier t + 1
+ *             when some edge u -> v exists with v attributed at tier t.  Tiers go up to max_tiers: 0 means GYS_RESOL_MAX_TIERS, 1 .. 8 are
+ *             taken as given.  Self edges, parallel edges and kinds make no difference.
+ *   TIE       among all candidates (source of v, v) at u's tier the lowest source slot wins, then the lowest v.  The result is a function
+ *             of the graph and the states alone: no launch shape and no order of the device's atomics can change a bit of it.
+ *   ROLE      GYS_RS_NONE (0): OPAQUE, or a CARRIER that was not reached;  GYS_RS_SOURCE (1);  GYS_RS_RESOLVED (2): a DEPENDENT that was
+ *             reached;  GYS_RS_CARRIER (3): a CARRIER that was reached;  GYS_RS_UNRESOLVED (4): a DEPENDENT not reached within max_tiers.
+ *   RECORD    per slot, gys_svc_resol: src_slot / via_slot = the source and the callee the issue came through, GYS_NOSLOT where there
+ *             is none (a source: src_slot = itself, via_slot = GYS_NOSLOT); tier = 0 for every role but RESOLVED and CARRIER; state and
+ *             issue as above, 0 where the slot has no state; nresolved = for a SOURCE the RESOLVED slots attributed to it (its blast
+ *             radius: carriers are not counted), otherwise 0.
+ *   STATS     with_state = the slots with a state; sources, resolved, unresolved, carriers = the slots of that role; edges = all service
+ *             edges (gys_svcgraph_stats.edges); resolved_at_tier[t - 1] = the RESOLVED slots at tier t.
+ * A call runs a FIXED list of launches -- seed, two per tier (a pass over the pairs, a pass over the slots), finish -- and reads the
+ * counter words once behind them, besides the two reads of the edge build: no read inside the search, no "changed" word.  Nothing is
+ * cached between calls, nothing is allocated before the first call, no engine state is modified.  Every call below answers
+ * GYS_ERR_STATE when actconn_pair_cap is 0.  Not here: attribution across ranks, the reference's 2-s memory of a previous resolution
+ * (:11352-11371; a call resolves the states as they are) and its per-related-group any_state_ok_bad_ shortcut.
+ * TOP SOURCES need no call of their own.  "The 10 root causes with the most affected services":
+ *     gys_svc_resolve_issues_dev(ctx, NULL, 0, d_out, d_impact, NULL);                       d_impact[slot] = nresolved of a source, NaN elsewhere
+ *     gys_topk_dev(ctx, d_impact, 1, gys_num_services(ctx), NULL, NULL, 0, GYS_TOPK_LARGEST, 10, out, &n, NULL);   out[i].row = the source's slot */
+#define GYS_RESOL_MAX_TIERS 8u
+enum { GYS_RS_NONE = 0, GYS_RS_SOURCE = 1, GYS_RS_RESOLVED = 2, GYS_RS_CARRIER = 3, GYS_RS_UNRESOLVED = 4 };
+typedef struct { /* 16 bytes */
+	uint32_t src_slot, via_slot;
+	uint8_t role, tier, state, issue;
+	uint32_t nresolved;
+} gys_svc_resol;
+typedef struct {
+	uint64_t with_state, sources, resolved, unresolved, carriers, edges, resolved_at_tier[8];
+} gys_svc_resol_stats;
+/* d_out[slot] (DEVICE, gys_num_services records, 16-byte aligned: a record leaves in one store) = RECORD of every slot.
+ * d_impact (DEVICE, gys_num_services doubles, or NULL): (double)nresolved for a SOURCE and NaN for every other slot -- a column
+ * gys_topk_dev takes as it is (it leaves NaNs out).  *stats (HOST, may be NULL).  GYS_ERR_INVAL: NULL or misaligned d_out,
+ * max_tiers > 8.  With no registered service nothing is written and the stats are 0. */
+int gys_svc_resolve_issues_dev(gys_ctx *ctx, const gys_listener_decision *d_dec /* DEVICE or NULL = kept states */, uint32_t max_tiers,
+			       gys_svc_resol *d_out, double *d_impact, gys_svc_resol_stats *stats);
+typedef struct { /* 48 bytes */
+	uint64_t glob_id, src_glob_id, via_glob_id; /* 0 where there is none */
+	uint32_t slot, src_slot, via_slot, nresolved;
+	uint8_t role, tier, state, issue, src_state, src_issue, pad[2];
+} gys_svc_resol_row;
+/* the slots whose role is in role_mask (bit r = list role r; 0 = roles 1 .. 4) on the HOST, ordered by slot ascending; d_dec is a DEVICE
+ * array as above.  *nmatch > cap: GYS_ERR_NOMEM, *nmatch and *stats are set, *nout = 0 and nothing else is written.  GYS_ERR_INVAL: NULL
+ * nout or nmatch, cap > 0 without out, max_tiers > 8, role bits above 4. */
+int gys_svc_resolve_issues(gys_ctx *ctx, const gys_listener_decision *d_dec, uint32_t max_tiers, uint32_t role_mask, gys_svc_resol_row *out,
+			   uint32_t cap, uint32_t *nout, uint32_t *nmatch, gys_svc_resol_stats *stats);
+
+/* -------------------------------------------------------------------------------------------------------------------
  * service records: saving, restoring and moving per-service state.  The reference's durable copy of a listener's statistics is Postgres;
  * after a restart the 5-day statistics are re-seeded (handle_listener_req, server/gy_mconnhdlr.cc:14257) through
  * GY_HISTOGRAM::get_serialized / update_from_serialized (common/gy_statistics.h:641-673).  Here the state lives in device memory: the
